@@ -36,6 +36,8 @@ CONFIGS = {
 }                                                                   # (60.6 GB key per GPU, trap_gen ~10 s; run with --gpus 8 --config c5)
 PEAK_F64_MFMA_TFLOPS = 78.6   # MI355X datasheet FP64 matrix; measured 77.3 by tools/probe_mfma_f64.hip (profiles/r01_probe_mfma_f64.log)
 PEAK_HBM_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_BYTES = 64 * 10**6        # --dump-outputs: the .npy files together stay within this
+DUMP_SEED = 2024               # --dump-outputs: the rows sampled when the whole output does not fit
 
 
 def parse_args(argv=None):
@@ -58,7 +60,12 @@ def parse_args(argv=None):
     ap.add_argument("--emulate-world", type=int, default=0, help="with --force-dist: size the gather's buffers as rank 0 of a job of this many ranks would (C5 readiness: 8)")
     ap.add_argument("--multi-handle", action="store_true", help="torch-free scaling mode: ONE process drives --gpus devices through psfp_samp_p_multi (host buffers, one worker thread per handle)")
     ap.add_argument("--launch-timeout", type=float, default=0.0, help="seconds after which the self-launcher stops every rank (0 = none)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the preimages of the last timed step (rank 0's rows) to DIR/*.npy as float64: "
+                    "a fixed, seeded sample of rows within 64 MB in all, their global indices and the sum of every row (see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the timed window over the number of steps)")
+    return args
 
 
 def main():
@@ -118,6 +125,8 @@ def rank_main(args):
                      gather=multi and not args.no_gather, force_dist=args.force_dist, alloc_world=args.emulate_world, verify_gather=args.verify_gather)
     psf, scheme, n, q, r, s, m, B, u, e = (run[k] for k in ("psf", "scheme", "n", "q", "r", "s", "m", "B", "u", "e"))
     stream, first_index, kern_ms, elapsed, valid, do_gather = (run[k] for k in ("stream", "first_index", "kern_ms", "elapsed", "valid", "do_gather"))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, e, first_index)      # e holds the last timed step's rows: the latency legs below write buffers of their own
 
     # latency of ONE call with few preimages -- the reference's unit of work (psf.rs:48-80: one samp_p call = one preimage; benches/psf.rs:38,63-65,90-92)
     # and the regime where reading the key from HBM once, not the FP64 pipe, is the roof.  Outside the timed region of the metric.
@@ -319,6 +328,34 @@ def run_config(cfg, batch, steps, warmup, local_rank, rank, world, multi, dev, s
             "rank_elapsed": rank_elapsed, "ranks_seen": ranks_seen, "gather_info": gather_info, "np_form": np_form, "gather_verified": gather_verified}
 
 
+def dump_outputs(out_dir, e, first_index):
+    """--dump-outputs: what the last timed step handed its caller -- the B x m integer preimages e, a torch tensor on the device or a numpy array -- as float64
+    .npy files, so that two builds run with the same arguments (same key, targets and seeds) can be compared output for output:
+      e.npy           the rows of a fixed, seeded sample (all rows when B x m fits), in ascending order
+      e_rows.npy      the global preimage index of each of those rows
+      e_row_sums.npy  the sum of every row of the batch, so that the rows the sample leaves out are compared too
+    float64 holds these integers exactly (checked before writing).  Together the files stay within DUMP_BYTES."""
+    import numpy as np
+    B, m = e.shape
+    header = 128                                                     # bytes of one .npy header (numpy pads it to a multiple of 64)
+    keep = max(1, min(B, (DUMP_BYTES - 8 * B - 3 * header) // (8 * (m + 1))))
+    rows = np.arange(B) if keep == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=keep, replace=False))
+    if isinstance(e, np.ndarray):
+        sample, sums = e[rows], e.sum(axis=1)
+    else:
+        import torch
+        sample = e.index_select(0, torch.from_numpy(rows).to(e.device)).cpu().numpy()
+        sums = e.sum(dim=1).cpu().numpy()
+    outs = {"e": sample, "e_rows": rows + first_index, "e_row_sums": sums}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outs.items():
+        f = a.astype(np.float64)
+        if not (f.astype(np.int64) == a).all():
+            raise ValueError(f"--dump-outputs: {name} holds integers that float64 cannot represent exactly")
+        np.save(os.path.join(out_dir, name + ".npy"), f)
+    print(f"[bench] --dump-outputs: {keep} of {B} rows (m = {m}), their indices and every row's sum in {out_dir}", file=sys.stderr)
+
+
 def nearest_plane_form(psf):
     """The kernels the last PSFGPV / PSFGPVRing samp_p call really launched for the walk of gpv.rs:160, from the handle (psfgpv_get_nearest_plane_form)."""
     try:
@@ -428,6 +465,8 @@ def multi_handle_main(args):
     chk = min(B, 256)                                # A e = u on the first rows of every handle's share, the domain check on the same rows
     rows = np.unique(np.concatenate([np.arange(d * (B // args.gpus), d * (B // args.gpus) + min(chk, B // args.gpus)) for d in range(args.gpus)]))
     valid = bool((handles[0].f_a(e[rows]) == u[rows]).all()) and bool(handles[0].check_domain(e[rows]).all())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, e, 0)
     last = windows[-1]
     out = {"metric": f"preimages/sec for samp_p ({args.config}, psfp_samp_p_multi: one process, host buffers, PCIe inclusive)",
            "value": round(B * args.steps / elapsed, 2), "unit": "preimages/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
