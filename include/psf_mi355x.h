@@ -257,6 +257,19 @@ psf_status psfp_get_multi_timing(const psfp_handle*, double* launched_ms, double
  * Asynchronous with respect to the host; errors detected on device are reported by psfp_last_status. */
 psf_status psfp_samp_p_dev(psfp_handle*, uint64_t seed, uint64_t first_index, size_t B,
                            const uint64_t* d_u, int64_t* d_e, void* stream);
+/* count independent samp_p_dev calls in one submission.  Batch i: seeds[i], first_indices[i], targets d_u + i*B*n,
+ * preimages d_e + i*B*m (m = psfp_m / psfgpv_m; for the ring type d = n(k+2)).  The bytes are those of
+ *   for (i = 0; i < count; ++i) X_samp_p_dev(h, seeds[i], first_indices[i], B, d_u + i*B*n, d_e + i*B*m, stream);
+ * Ordered on `stream` like samp_p_dev: it starts behind the work enqueued before it, and work enqueued after it sees every batch.
+ * seeds / first_indices are host arrays; the call returns once everything is enqueued.  count == 0 or B == 0: PSF_OK, nothing enqueued.
+ * Every check runs before anything is enqueued; asynchronous host-pointer calls in flight are drained first.  X_last_status afterwards: PSF_ERR_SAMPLER
+ * if the sampler failed in ANY batch.  The nearest-plane types run batches that take one launch per 64-row block (C4) on two lanes (a second set
+ * of per-batch buffers, allocated by the first such call with count >= 2, and two streams of the handle): one batch's solve, projection and
+ * recombination overlap the other lane's walk.  Batches that fit the one-launch walk (C2) gain nothing from that and run in order on `stream`, as do
+ * all batches with timing enabled (psfgpv_enable_timing; get_timing then describes the last batch).  psfp_samp_p_dev_many runs the batches in order
+ * on `stream` (PSF_ERR_UNSUPPORTED under the experiments build's PSF_PIPELINE=1). */
+psf_status psfp_samp_p_dev_many(psfp_handle*, size_t count, const uint64_t* seeds, const uint64_t* first_indices, size_t B,
+                                const uint64_t* d_u, int64_t* d_e, void* stream);
 psf_status psfp_samp_d_dev(psfp_handle*, uint64_t seed, uint64_t first_index, size_t B, int64_t* d_e, void* stream);
 psf_status psfp_f_a_dev(psfp_handle*, size_t B, const int64_t* d_e, uint64_t* d_u, uint8_t* d_ok, void* stream);
 /* synchronises the stream of the last *_dev call and returns the device-side status of that call */
@@ -321,6 +334,9 @@ psf_status psfgpv_export_key(const psfgpv_handle*, uint64_t* A, int8_t* R, int32
 psf_status psfgpv_samp_d(psfgpv_handle*, uint64_t seed, uint64_t first_index, size_t B, int64_t* e);         /* gpv.rs:113-116 */
 psf_status psfgpv_samp_p(psfgpv_handle*, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* u, int64_t* e);
 psf_status psfgpv_samp_p_dev(psfgpv_handle*, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_e, void* stream);
+/* as psfp_samp_p_dev_many; psfgpv_get_nearest_plane_form reports the form shared by the batches, its reruns count covers every batch */
+psf_status psfgpv_samp_p_dev_many(psfgpv_handle*, size_t count, const uint64_t* seeds, const uint64_t* first_indices, size_t B,
+                                  const uint64_t* d_u, int64_t* d_e, void* stream);
 /* gpv.rs:152-161 on host buffers without waiting (the transport of psfp_samp_p_async: rows narrowed to int32 on the device, chunk transfers by the DMA engines into
  * per-call pinned rings, widened into e by worker threads): returns once the work is enqueued (u may be reused), e[] is complete when psfgpv_wait returns.  At most two
  * calls in flight per handle; the rows of call i cross PCIe while call i + 1 walks.  psfgpv_wait returns the first non-OK status of the outstanding calls, oldest first:
@@ -385,6 +401,9 @@ psf_status psfring_export_key(const psfring_handle*, uint64_t* a, int64_t* r, in
 psf_status psfring_samp_d(psfring_handle*, uint64_t seed, uint64_t first_index, size_t B, int64_t* sigma);            /* :118-122 */
 psf_status psfring_samp_p(psfring_handle*, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* u, int64_t* sigma);
 psf_status psfring_samp_p_dev(psfring_handle*, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_sigma, void* stream);
+/* as psfgpv_samp_p_dev_many */
+psf_status psfring_samp_p_dev_many(psfring_handle*, size_t count, const uint64_t* seeds, const uint64_t* first_indices, size_t B,
+                                   const uint64_t* d_u, int64_t* d_sigma, void* stream);
 /* gpv_ring.rs:160-212 without waiting: as psfgpv_samp_p_async / psfgpv_wait */
 psf_status psfring_samp_p_async(psfring_handle*, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* u, int64_t* sigma);
 psf_status psfring_wait(psfring_handle*);

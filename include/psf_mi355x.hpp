@@ -94,6 +94,12 @@ class PSFPerturbation {
     check(psfp_samp_p_async(h_, seed, first_index, B, u.data(), e.data()), "samp_p_async");
   }
   void wait() { check(psfp_wait(h_), "wait"); }
+  // count = seeds.size() independent samp_p_dev calls in one submission on device buffers (d_u: count * B * n targets, d_e: count * B * m entries), ordered on `stream`
+  // (a hipStream_t, nullptr = default); the bytes of the loop of single calls (include/psf_mi355x.h)
+  void samp_p_dev_many(const uint64_t* d_u, int64_t* d_e, size_t B, const std::vector<uint64_t>& seeds, const std::vector<uint64_t>& first_indices, void* stream = nullptr) {
+    if (seeds.size() != first_indices.size()) throw PsfError(PSF_ERR_PARAM, "samp_p_dev_many");
+    check(psfp_samp_p_dev_many(h_, seeds.size(), seeds.data(), first_indices.data(), B, d_u, d_e, stream), "samp_p_dev_many");
+  }
   MatZq f_a(const MatZ& sigma) {                                                                  // :366-369
     if (sigma.empty() || sigma.size() % m() != 0) throw PsfError(PSF_ERR_DOMAIN, "f_a");
     const size_t B = sigma.size() / m();
@@ -156,6 +162,12 @@ class PSFGPV {
     check(psfgpv_samp_p_async(h_, seed, first_index, B, u.data(), e.data()), "samp_p_async");
   }
   void wait() { check(psfgpv_wait(h_), "wait"); }
+  // count = seeds.size() independent samp_p_dev calls in one submission on device buffers (d_u: count * B * n targets, d_e: count * B * m entries), ordered on `stream`
+  // (a hipStream_t, nullptr = default); the bytes of the loop of single calls (include/psf_mi355x.h)
+  void samp_p_dev_many(const uint64_t* d_u, int64_t* d_e, size_t B, const std::vector<uint64_t>& seeds, const std::vector<uint64_t>& first_indices, void* stream = nullptr) {
+    if (seeds.size() != first_indices.size()) throw PsfError(PSF_ERR_PARAM, "samp_p_dev_many");
+    check(psfgpv_samp_p_dev_many(h_, seeds.size(), seeds.data(), first_indices.data(), B, d_u, d_e, stream), "samp_p_dev_many");
+  }
   MatZq f_a(const MatZ& sigma) {                                                                   // :190-193
     if (sigma.empty() || sigma.size() % m() != 0) throw PsfError(PSF_ERR_DOMAIN, "f_a");
     const size_t B = sigma.size() / m();
@@ -215,6 +227,12 @@ class PSFGPVRing {
     check(psfring_samp_p_async(h_, seed, first_index, B, u.data(), sg.data()), "samp_p_async");
   }
   void wait() { check(psfring_wait(h_), "wait"); }
+  // count = seeds.size() independent samp_p_dev calls in one submission on device buffers (d_u: count * B * n targets, d_sg: count * B * (k + 2) * n entries), ordered on `stream`
+  // (a hipStream_t, nullptr = default); the bytes of the loop of single calls (include/psf_mi355x.h)
+  void samp_p_dev_many(const uint64_t* d_u, int64_t* d_sg, size_t B, const std::vector<uint64_t>& seeds, const std::vector<uint64_t>& first_indices, void* stream = nullptr) {
+    if (seeds.size() != first_indices.size()) throw PsfError(PSF_ERR_PARAM, "samp_p_dev_many");
+    check(psfring_samp_p_dev_many(h_, seeds.size(), seeds.data(), first_indices.data(), B, d_u, d_sg, stream), "samp_p_dev_many");
+  }
   MatZq f_a(const MatZ& sigma) {                                                                    // :243-247
     const size_t d = polys() * n();
     if (sigma.empty() || sigma.size() % d != 0) throw PsfError(PSF_ERR_DOMAIN, "f_a");

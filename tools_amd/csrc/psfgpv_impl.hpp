@@ -3,6 +3,25 @@
 // psfp_handle created with r = 1 (then s*r = s and the domain bound s^2 m r^2 = s^2 m, gpv.rs:113-116, :219-224).
 
 #include <algorithm>
+// Everything one batch of the nearest plane writes: a lane.  Lane 0 serves every call; samp_p_dev_many runs the odd batches of a launch-per-block walk on lane 1
+// (allocated by the first such many-call of two or more batches), so that one batch's solve, projection and recombination overlap the other lane's walk.
+struct NpLane {
+  size_t bcap = 0, ld = 0;
+  double* dTm = nullptr;              // running projections, dpad x ld
+  double* dZf = nullptr;              // z as f64, chunk stream (ld / 128) x nkb
+  int8_t* dZ8 = nullptr; size_t zplane = 0;          // three digit planes of z, [dpad / 16][ld][16] each
+  unsigned char* dZocc = nullptr;     // which 128 x 128 tiles of z digits 1 and 2 hold anything: [2][ld / 128][nrb] (k_np_occ_z, per call)
+  double* dC0p = nullptr;             // -sol on the pivots, chunk stream (ld / 128) x nkc
+  uint64_t* dSol = nullptr;           // n x ld
+  double* dC1 = nullptr;              // two-pass walk: -e1, chunk stream (ld / 128) x nkd
+  int64_t* dE1 = nullptr;             // two-pass walk: e1, bcap x dim
+  unsigned* dWalk = nullptr;          // k_np_walk: [group][block] counters of published z | [group][block] flags of completed rows | abort word
+  size_t walk_words = 0;
+  int* dFlags = nullptr;              // [0] sampler failure [1] second digit of some z in use [2] third digit [3] |z| beyond three digits; [4..7]: the same for the second pass;
+                                      // [8..9] a 64-bit count of walks re-run by k_np_walk_solo (never cleared)
+  int* dFail = nullptr;               // failure words of the base handle the call clears (psfp_last_status reads them): lane 0 only
+};
+
 struct psfgpv_handle {
   psfp_handle* base = nullptr;
   double s = 0;
@@ -22,25 +41,15 @@ struct psfgpv_handle {
   double* dBpiv = nullptr;            // b~_i on the pivot columns, fragment order
   int8_t* dB8 = nullptr;              // two digit planes of the basis, transposed, dpad x dpad each
   bool basis_hi = false, basis_generic = false;
-  // per batch
-  size_t bcap = 0, ld = 0;
-  double* dTm = nullptr;              // running projections, dpad x ld
-  double* dZf = nullptr;              // z as f64, chunk stream (ld / 128) x nkb
-  int8_t* dZ8 = nullptr; size_t zplane = 0;          // three digit planes of z, [dpad / 16][ld][16] each
   unsigned char* dBocc = nullptr;     // which 128 x 128 tiles of the basis digit planes hold anything: [2][nrb][nrb] (k_np_occ_basis, per key)
-  unsigned char* dZocc = nullptr;     // the same for z digits 1 and 2: [2][ld / 128][nrb] (k_np_occ_z, per call)
   int np_combine = 1;                 // PSF_NP_COMBINE: 1 / unset = one fused launch over the occupied tiles (k_np_combine8_fused), 0 = one launch per digit pair
-  double* dC0p = nullptr;             // -sol on the pivots, chunk stream (ld / 128) x nkc
-  uint64_t* dSol = nullptr;           // n x ld
-  int* dFlags = nullptr;              // [0] sampler failure [1] second digit of some z in use [2] third digit [3] |z| beyond three digits; [4..7]: the same for the second pass
+  // per batch: lane 0 for every call, lane 1 beside it for samp_p_dev_many
+  NpLane ln[2];
+  int last_lanes = 1;                 // lanes the last call wrote (psfgpv_last_status reads the failure words of both after a many-call)
   // two-pass walk for large moduli (q sqrt(n) > 2^13 s): the first pass only finds a short coset representative e1, the second samples around it
   bool two_pass = false;
   size_t nkd = 0;                     // K chunks of all d coordinates
   double* dBfull = nullptr;           // b~_i on every coordinate, fragment order (A operand of the second projection)
-  double* dC1 = nullptr;              // -e1, chunk stream (ld / 128) x nkd
-  int64_t* dE1 = nullptr;             // e1, bcap x dim
-  unsigned* dWalk = nullptr;          // k_np_walk: [group][block] counters of published z | [group][block] flags of completed rows | abort word
-  size_t walk_words = 0;
   int np_walk = -1;                   // PSF_NP_WALK: 0 = one launch per block (k_np_step); 1 / unset = the whole walk in one launch (k_np_walk: updater workgroups, T in
                                       // registers) where it fits, launches otherwise; 3 = k_np_walk2 (helper waves update T in memory) for every batch that is resident
   int cus = 0;                        // compute units of the device
@@ -50,7 +59,8 @@ struct psfgpv_handle {
   int last_parts = 1;                 // column ranges the last call walked side by side (np_split)
   int split_delay_us = 0;             // the second half starts this much behind the first
   int np_split = 0;                   // experiments build: 0 never, 1 whenever the shape allows, 2 for large batches (>= 3072) only
-  hipStream_t sh[2] = {nullptr, nullptr};                  // the two halves of a large batch walk side by side on these (equal priority, non-blocking)
+  hipStream_t sh[2] = {nullptr, nullptr};                  // non-blocking, equal priority: the lanes of samp_p_dev_many (created with lane 1); the experiments
+                                                           // build also walks the two halves of a large batch side by side on them
   hipEvent_t evFork = nullptr, evHalf[2] = {nullptr, nullptr};
   int np_g = 0;                       // PSF_NP_G: preimages per wave of the sampler (0 = by batch size)
   int np_immediate = -1;              // PSF_NP_IMMEDIATE: 1 = every block updates all the rows below it in the launch that follows, 0 = panel-deferred far update, -1 = by batch size
@@ -173,40 +183,41 @@ static psf_status gpv_build_solver(psfgpv_handle* g) {
   return PSF_OK;
 }
 
-static void free_np_batch(psfgpv_handle* g) {
-  hipFree(g->dTm); hipFree(g->dZf); hipFree(g->dZ8); hipFree(g->dC0p); hipFree(g->dSol); hipFree(g->dC1); hipFree(g->dE1); hipFree(g->dWalk); hipFree(g->dZocc);
-  g->dZocc = nullptr;
-  g->dTm = g->dZf = g->dC0p = g->dC1 = nullptr; g->dZ8 = nullptr; g->dSol = nullptr; g->dE1 = nullptr; g->dWalk = nullptr;
-  g->bcap = 0;
+static void free_np_batch(NpLane& L) {
+  hipFree(L.dTm); hipFree(L.dZf); hipFree(L.dZ8); hipFree(L.dC0p); hipFree(L.dSol); hipFree(L.dC1); hipFree(L.dE1); hipFree(L.dWalk); hipFree(L.dZocc);
+  L.dZocc = nullptr;
+  L.dTm = L.dZf = L.dC0p = L.dC1 = nullptr; L.dZ8 = nullptr; L.dSol = nullptr; L.dE1 = nullptr; L.dWalk = nullptr;
+  L.bcap = 0;
 }
-static psf_status ensure_np_batch(psfgpv_handle* g, size_t B) {
-  if (B <= g->bcap) return PSF_OK;
+// synchronises the device when it (re)allocates: never between the fork and the join of a many-call (psfgpv_samp_p_dev_many sizes both lanes first)
+static psf_status ensure_np_batch(psfgpv_handle* g, NpLane& L, size_t B) {
+  if (B <= L.bcap) return PSF_OK;
   HIP_TRY(hipDeviceSynchronize());
-  free_np_batch(g);
+  free_np_batch(L);
   const size_t ld = round_up(B, TR_BN);
-  g->ld = ld;
-  HIP_TRY(hipMalloc(&g->dTm, g->dpad * ld * sizeof(double)));
-  HIP_TRY(hipMalloc(&g->dZf, ld * g->nkb * 16 * sizeof(double)));
-  g->zplane = g->dpad * ld;
-  HIP_TRY(hipMalloc(&g->dZ8, 3 * g->zplane));
-  HIP_TRY(hipMalloc(&g->dZocc, 2 * (ld / 128) * g->nrb));
-  HIP_TRY(hipMalloc(&g->dC0p, ld * g->nkc * 16 * sizeof(double)));
-  HIP_TRY(hipMalloc(&g->dSol, g->n * ld * sizeof(uint64_t)));
+  L.ld = ld;
+  HIP_TRY(hipMalloc(&L.dTm, g->dpad * ld * sizeof(double)));
+  HIP_TRY(hipMalloc(&L.dZf, ld * g->nkb * 16 * sizeof(double)));
+  L.zplane = g->dpad * ld;
+  HIP_TRY(hipMalloc(&L.dZ8, 3 * L.zplane));
+  HIP_TRY(hipMalloc(&L.dZocc, 2 * (ld / 128) * g->nrb));
+  HIP_TRY(hipMalloc(&L.dC0p, ld * g->nkc * 16 * sizeof(double)));
+  HIP_TRY(hipMalloc(&L.dSol, g->n * ld * sizeof(uint64_t)));
   if (g->two_pass) {
-    HIP_TRY(hipMalloc(&g->dC1, ld * g->nkd * 16 * sizeof(double)));
-    HIP_TRY(hipMalloc(&g->dE1, B * g->dim * sizeof(int64_t)));
+    HIP_TRY(hipMalloc(&L.dC1, ld * g->nkd * 16 * sizeof(double)));
+    HIP_TRY(hipMalloc(&L.dE1, B * g->dim * sizeof(int64_t)));
   }
-  g->walk_words = round_up(2 * (ld / NP_GW) * g->nblk + 4, 4);
-  HIP_TRY(hipMalloc(&g->dWalk, g->walk_words * sizeof(unsigned)));
-  HIP_TRY(hipMemset(g->dTm, 0, g->dpad * ld * sizeof(double)));
-  HIP_TRY(hipMemset(g->dZf, 0, ld * g->nkb * 16 * sizeof(double)));      // padding rows / columns of the operands stay zero for good
-  HIP_TRY(hipMemset(g->dZ8, 0, 3 * g->zplane));
+  L.walk_words = round_up(2 * (ld / NP_GW) * g->nblk + 4, 4);
+  HIP_TRY(hipMalloc(&L.dWalk, L.walk_words * sizeof(unsigned)));
+  HIP_TRY(hipMemset(L.dTm, 0, g->dpad * ld * sizeof(double)));
+  HIP_TRY(hipMemset(L.dZf, 0, ld * g->nkb * 16 * sizeof(double)));      // padding rows / columns of the operands stay zero for good
+  HIP_TRY(hipMemset(L.dZ8, 0, 3 * L.zplane));
   HIP_TRY(hipDeviceSynchronize());      // the clears run on the null stream, the walk possibly on a non-blocking one (see ensure_batch, psfp.hip)
-  g->bcap = B;
+  L.bcap = B;
   return PSF_OK;
 }
 
-static psf_status launch_np_recombination(psfgpv_handle* g, hipStream_t st, size_t B, int64_t* d_e, int pass, size_t col0 = 0);
+static psf_status launch_np_recombination(psfgpv_handle* g, NpLane& L, hipStream_t st, size_t B, int64_t* d_e, int pass, size_t col0 = 0);
 
 // One one-launch walk at a time per device and process: the constructor makes `st` wait for the walk launched before (any handle, any stream), the destructor
 // records the event the next one will wait for.  Held across the launch only; costs one hipStreamWaitEvent + one hipEventRecord per call.
@@ -232,10 +243,10 @@ struct WalkTurn {
 struct NpCols {
   double* Tm; double* Zf; int8_t* Z8; unsigned char* Zocc; double* C0p; double* C1; uint64_t* Sol; int64_t* E1;
 };
-static NpCols np_cols(const psfgpv_handle* g, size_t col0) {
+static NpCols np_cols(const psfgpv_handle* g, const NpLane& L, size_t col0) {
   const size_t cb = col0 / TR_BN;
-  return NpCols{g->dTm + col0, g->dZf + cb * g->nkb * TR_CHUNK, g->dZ8 + col0 * 16, g->dZocc + cb * g->nrb, g->dC0p + cb * g->nkc * TR_CHUNK,
-                g->dC1 ? g->dC1 + cb * g->nkd * TR_CHUNK : nullptr, g->dSol + col0, g->dE1 ? g->dE1 + col0 * g->dim : nullptr};
+  return NpCols{L.dTm + col0, L.dZf + cb * g->nkb * TR_CHUNK, L.dZ8 + col0 * 16, L.dZocc + cb * g->nrb, L.dC0p + cb * g->nkc * TR_CHUNK,
+                L.dC1 ? L.dC1 + cb * g->nkd * TR_CHUNK : nullptr, L.dSol + col0, L.dE1 ? L.dE1 + col0 * g->dim : nullptr};
 }
 
 // does a batch of B preimages fit the one-launch walk?  (one sampler workgroup per CU at most beside the updaters that hold d/64 - 2 row blocks per column group)
@@ -262,47 +273,47 @@ static bool np_walk_fits(const psfgpv_handle* g, size_t B, int* Gw_out, unsigned
 // MatZ::sample_d_precomputed_gso for B preimages (gpv.rs:160), the columns col0 ... of the batch buffers: the launch sequence of psf_np_kernels.hpp on one stream
 // pass 0: centre -sol on the pivot columns (K = n), e = sum z b + sol; pass 1 (two-pass mode): centre -e1 on every coordinate (K = d), e = sum z b + e1
 // first_index / d_e: of the range's first preimage
-static psf_status launch_nearest_plane(psfgpv_handle* g, hipStream_t st, uint64_t seed, uint32_t tag, uint64_t first_index, size_t B, int64_t* d_e, int pass = 0, size_t col0 = 0,
+static psf_status launch_nearest_plane(psfgpv_handle* g, NpLane& L, hipStream_t st, uint64_t seed, uint32_t tag, uint64_t first_index, size_t B, int64_t* d_e, int pass = 0, size_t col0 = 0,
                                        bool may_walk = true) {
-  const size_t ld = g->ld, nbj = round_up(B, TR_BN) / TR_BN;
+  const size_t ld = L.ld, nbj = round_up(B, TR_BN) / TR_BN;
   const size_t lds_gemm = 4 * TR_CHUNK * sizeof(double);
-  const NpCols v = np_cols(g, col0);
+  const NpCols v = np_cols(g, L, col0);
   // T = B~[:, pivots] C0[pivots]
-  int* const flags = g->dFlags + 4 * pass;
+  int* const flags = L.dFlags + 4 * pass;
   if (pass == 0) hipLaunchKernelGGL(k_np_project, dim3((unsigned)nbj, (unsigned)g->nrb), dim3(256), lds_gemm, st, g->dBpiv, g->nkc, v.C0p, g->nkc, (int)g->nkc, v.Tm, ld);
   else hipLaunchKernelGGL(k_np_project, dim3((unsigned)nbj, (unsigned)g->nrb), dim3(256), lds_gemm, st, g->dBfull, g->nkd, v.C1, g->nkd, (int)g->nkd, v.Tm, ld);
   int G = g->np_g;
   if (G != 1 && G != 2) G = B <= 2048 ? 1 : 2;      // one wave pair per preimage while the sampler workgroups fit the chip's 512 slots at once (C4 shape: 2.45 / 2.80 ms at 1537 /
                                                     // 2048 preimages against 3.06 / 3.25 with two preimages per pair); two rounds of them lose to two preimages per pair
-  NpSampleArgs a{v.Tm, ld, g->dGin, g->dGnx, g->dRows, g->dSz, v.Zf, g->nkb, v.Z8, g->zplane, ld, flags};
+  NpSampleArgs a{v.Tm, ld, g->dGin, g->dGnx, g->dRows, g->dSz, v.Zf, g->nkb, v.Z8, L.zplane, ld, flags};
   // The whole walk in one launch (k_np_walk) where every workgroup can be resident at once: one sampler workgroup per CU at most (B <= 4 G CUs) beside one
   // updater workgroup per CU, and at most 2 * NP_WALK_SLOTS blocks of T per updater.  Otherwise one launch per block (k_np_step).
   {
     int Gw = 0; unsigned nSw = 0, ngroups = 0, ug = 0;
     if (may_walk && col0 == 0 && np_walk_fits(g, B, &Gw, &nSw, &ngroups, &ug)) {
-      NpWalkSync sy{g->dWalk, g->dWalk + (size_t)ngroups * g->nblk, g->dWalk + (size_t)2 * ngroups * g->nblk, (unsigned)g->nblk, g->walk_spins};
-      NpSampleArgs aw{g->dTm, ld, g->dGin, g->dGnx, g->dRows, g->dSz, g->dZf, g->nkb, g->dZ8, g->zplane, ld, flags};
+      NpWalkSync sy{L.dWalk, L.dWalk + (size_t)ngroups * g->nblk, L.dWalk + (size_t)2 * ngroups * g->nblk, (unsigned)g->nblk, g->walk_spins};
+      NpSampleArgs aw{L.dTm, ld, g->dGin, g->dGnx, g->dRows, g->dSz, L.dZf, g->nkb, L.dZ8, L.zplane, ld, flags};
       const unsigned ntot = nSw + ngroups * ug;
-      unsigned long long* reruns = reinterpret_cast<unsigned long long*>(g->dFlags + 8);
+      unsigned long long* reruns = reinterpret_cast<unsigned long long*>(L.dFlags + 8);
       {
         // two walks at once on one device (two handles, two streams) could each hold half of the slots and wait for the other half for ever: walks of this process take
         // turns per device -- each launch waits for the event behind the previous one.  (Another process is not covered by this; k_np_walk_solo is.)
         WalkTurn turn(g->base->prm.device, st);
-        hipMemsetAsync(g->dWalk, 0, g->walk_words * sizeof(unsigned), st);
-        if (Gw == 1) hipLaunchKernelGGL((k_np_walk<1>), dim3(ntot), dim3(512), 65536, st, aw, g->dim, g->nblk, seed, tag, first_index, B, nSw, ngroups, ug, g->dGp, g->dTm, sy);
+        hipMemsetAsync(L.dWalk, 0, L.walk_words * sizeof(unsigned), st);
+        if (Gw == 1) hipLaunchKernelGGL((k_np_walk<1>), dim3(ntot), dim3(512), 65536, st, aw, g->dim, g->nblk, seed, tag, first_index, B, nSw, ngroups, ug, g->dGp, L.dTm, sy);
 #ifdef PSF_EXPERIMENTS
-        else hipLaunchKernelGGL((k_np_walk<2>), dim3(ntot), dim3(512), 65536, st, aw, g->dim, g->nblk, seed, tag, first_index, B, nSw, ngroups, ug, g->dGp, g->dTm, sy);
+        else hipLaunchKernelGGL((k_np_walk<2>), dim3(ntot), dim3(512), 65536, st, aw, g->dim, g->nblk, seed, tag, first_index, B, nSw, ngroups, ug, g->dGp, L.dTm, sy);
 #endif
       }
       // a walk that gave up (the abort word) is walked again without waits between workgroups, from a fresh projection; both launches return at once otherwise
-      if (pass == 0) hipLaunchKernelGGL(k_np_project, dim3((unsigned)nbj, (unsigned)g->nrb), dim3(256), lds_gemm, st, g->dBpiv, g->nkc, g->dC0p, g->nkc, (int)g->nkc, g->dTm, ld, (const unsigned*)sy.abort);
-      else hipLaunchKernelGGL(k_np_project, dim3((unsigned)nbj, (unsigned)g->nrb), dim3(256), lds_gemm, st, g->dBfull, g->nkd, g->dC1, g->nkd, (int)g->nkd, g->dTm, ld, (const unsigned*)sy.abort);
-      if (Gw == 1) hipLaunchKernelGGL((k_np_walk_solo<1>), dim3(nSw), dim3(512), 65536, st, aw, g->dim, g->nblk, seed, tag, first_index, B, g->dGp, g->dTm, (const unsigned*)sy.abort, reruns);
+      if (pass == 0) hipLaunchKernelGGL(k_np_project, dim3((unsigned)nbj, (unsigned)g->nrb), dim3(256), lds_gemm, st, g->dBpiv, g->nkc, L.dC0p, g->nkc, (int)g->nkc, L.dTm, ld, (const unsigned*)sy.abort);
+      else hipLaunchKernelGGL(k_np_project, dim3((unsigned)nbj, (unsigned)g->nrb), dim3(256), lds_gemm, st, g->dBfull, g->nkd, L.dC1, g->nkd, (int)g->nkd, L.dTm, ld, (const unsigned*)sy.abort);
+      if (Gw == 1) hipLaunchKernelGGL((k_np_walk_solo<1>), dim3(nSw), dim3(512), 65536, st, aw, g->dim, g->nblk, seed, tag, first_index, B, g->dGp, L.dTm, (const unsigned*)sy.abort, reruns);
 #ifdef PSF_EXPERIMENTS
-      else hipLaunchKernelGGL((k_np_walk_solo<2>), dim3(nSw), dim3(512), 65536, st, aw, g->dim, g->nblk, seed, tag, first_index, B, g->dGp, g->dTm, (const unsigned*)sy.abort, reruns);
+      else hipLaunchKernelGGL((k_np_walk_solo<2>), dim3(nSw), dim3(512), 65536, st, aw, g->dim, g->nblk, seed, tag, first_index, B, g->dGp, L.dTm, (const unsigned*)sy.abort, reruns);
 #endif
       g->last_form = 1; g->last_G = Gw;
-      return launch_np_recombination(g, st, B, d_e, pass, col0);
+      return launch_np_recombination(g, L, st, B, d_e, pass, col0);
     }
   }
   const unsigned nS = (unsigned)((B + 4 * (size_t)G - 1) / (4 * (size_t)G));
@@ -312,12 +323,12 @@ static psf_status launch_nearest_plane(psfgpv_handle* g, hipStream_t st, uint64_
 #ifdef PSF_EXPERIMENTS
   if (g->np_walk == 3 && col0 == 0 && g->cus > 0 && g->nblk >= 3 && nS <= 2u * (unsigned)g->cus) {
     const unsigned per = (unsigned)(NP_GW / (4 * G)), ngroups = (nS + per - 1) / per;
-    NpWalkSync sy{g->dWalk, g->dWalk + (size_t)ngroups * g->nblk, g->dWalk + (size_t)2 * ngroups * g->nblk, (unsigned)g->nblk, g->walk_spins};
-    hipMemsetAsync(g->dWalk, 0, g->walk_words * sizeof(unsigned), st);
-    if (G == 1) hipLaunchKernelGGL((k_np_walk2<1>), dim3(nS), dim3(512), 65536, st, a, g->dim, g->nblk, seed, tag, first_index, B, nS, g->dGp, g->dTm, sy);
-    else hipLaunchKernelGGL((k_np_walk2<2>), dim3(nS), dim3(512), 65536, st, a, g->dim, g->nblk, seed, tag, first_index, B, nS, g->dGp, g->dTm, sy);
+    NpWalkSync sy{L.dWalk, L.dWalk + (size_t)ngroups * g->nblk, L.dWalk + (size_t)2 * ngroups * g->nblk, (unsigned)g->nblk, g->walk_spins};
+    hipMemsetAsync(L.dWalk, 0, L.walk_words * sizeof(unsigned), st);
+    if (G == 1) hipLaunchKernelGGL((k_np_walk2<1>), dim3(nS), dim3(512), 65536, st, a, g->dim, g->nblk, seed, tag, first_index, B, nS, g->dGp, L.dTm, sy);
+    else hipLaunchKernelGGL((k_np_walk2<2>), dim3(nS), dim3(512), 65536, st, a, g->dim, g->nblk, seed, tag, first_index, B, nS, g->dGp, L.dTm, sy);
     g->last_form = 3; g->last_G = G;
-    return launch_np_recombination(g, st, B, d_e, pass, col0);
+    return launch_np_recombination(g, L, st, B, d_e, pass, col0);
   }
 #endif
   const size_t W = NP_PANEL;
@@ -354,28 +365,28 @@ static psf_status launch_nearest_plane(psfgpv_handle* g, hipStream_t st, uint64_
     else hipLaunchKernelGGL((k_np_step<2>), dim3(ntot), dim3(512), 65536, st, a, g->dim, J, seed, tag, first_index, B, nS, jobs, (int)nbj, g->dGp, v.Tm);
   }
   g->last_form = 0; g->last_G = G;
-  return launch_np_recombination(g, st, B, d_e, pass, col0);
+  return launch_np_recombination(g, L, st, B, d_e, pass, col0);
 }
 
 // e = sum_i z_i b_i + sol (pass 1 of the two-pass walk: + e1)
-static psf_status launch_np_recombination(psfgpv_handle* g, hipStream_t st, size_t B, int64_t* d_e, int pass, size_t col0) {
-  const size_t ld = g->ld;
-  const NpCols v = np_cols(g, col0);
-  int* const flags = g->dFlags + 4 * pass;
+static psf_status launch_np_recombination(psfgpv_handle* g, NpLane& L, hipStream_t st, size_t B, int64_t* d_e, int pass, size_t col0) {
+  const size_t ld = L.ld;
+  const NpCols v = np_cols(g, L, col0);
+  int* const flags = L.dFlags + 4 * pass;
   const psfp_handle* b = g->base;
   const dim3 cgrid((unsigned)((B + 127) / 128), (unsigned)(g->dpad / 128));
   const int nk128 = (int)(g->dpad / 128);
   if (!g->basis_generic && g->np_combine != 0) {
     // z = z0 + 256 z1 + 65536 z2, b = b0 + 256 b1: every digit pair in one launch, over the tiles of the digit planes that hold anything
-    hipLaunchKernelGGL(k_np_occ_z, dim3((unsigned)(cgrid.x * g->nrb), 2), dim3(256), 0, st, v.Z8, g->zplane, ld, nk128, v.Zocc);
-    hipLaunchKernelGGL(k_np_combine8_fused, cgrid, dim3(256), 65536 + 768, st, g->dB8, g->dpad, g->dim, nk128, g->basis_hi ? 2 : 1, g->dBocc, v.Z8, g->zplane, ld, B, v.Zocc, d_e, g->dim);
+    hipLaunchKernelGGL(k_np_occ_z, dim3((unsigned)(cgrid.x * g->nrb), 2), dim3(256), 0, st, v.Z8, L.zplane, ld, nk128, v.Zocc);
+    hipLaunchKernelGGL(k_np_combine8_fused, cgrid, dim3(256), 65536 + 768, st, g->dB8, g->dpad, g->dim, nk128, g->basis_hi ? 2 : 1, g->dBocc, v.Z8, L.zplane, ld, B, v.Zocc, d_e, g->dim);
     if (pass == 0) hipLaunchKernelGGL(k_np_add_sol, dim3(grid_for(g->n * B)), dim3(256), 0, st, v.Sol, g->dPiv, g->n, B, ld, d_e, g->dim);
   }
 #ifdef PSF_EXPERIMENTS
   else if (!g->basis_generic) {
     // the same sum as one pass per digit pair in use (the z digits beyond the first are gated on the device): PSF_NP_COMBINE=0, kept for the switch matrix
     const size_t plane = g->dpad * g->dpad;
-    const int8_t* zp[3] = {v.Z8, v.Z8 + g->zplane, v.Z8 + 2 * g->zplane};
+    const int8_t* zp[3] = {v.Z8, v.Z8 + L.zplane, v.Z8 + 2 * L.zplane};
     const int* gate[3] = {nullptr, flags + 1, flags + 2};
     bool first = true;
     for (int zi = 0; zi < 3; ++zi)
@@ -457,8 +468,9 @@ static psf_status psfgpv_init(psfgpv_handle* g) {
   HIP_TRY(hipMalloc(&g->dBpiv, g->nrb * g->nkc * TR_CHUNK * sizeof(double)));
   HIP_TRY(hipMalloc(&g->dB8, 2 * g->dpad * g->dpad));
   HIP_TRY(hipMalloc(&g->dBocc, 2 * g->nrb * g->nrb));
-  HIP_TRY(hipMalloc(&g->dFlags, 12 * sizeof(int)));                       // [0..7] per call (two passes), [8..9] a 64-bit count of walks re-run by k_np_walk_solo (never cleared)
-  HIP_TRY(hipMemset(g->dFlags, 0, 12 * sizeof(int)));
+  HIP_TRY(hipMalloc(&g->ln[0].dFlags, 12 * sizeof(int)));                 // [0..7] per call (two passes), [8..9] a 64-bit count of walks re-run by k_np_walk_solo (never cleared)
+  HIP_TRY(hipMemset(g->ln[0].dFlags, 0, 12 * sizeof(int)));
+  g->ln[0].dFail = g->base->dFail;
   // large moduli: q sqrt(n) > 2^13 s (relative centre error of a single pass above 2^-40, see include/psf_mi355x.h "Precision of the centres"); PSF_NP_TWO_PASS=0/1 forces
   g->two_pass = (double)g->base->q * std::sqrt((double)g->n) > g->s * 8192.0;
   { const char* ev = psf_exp_env("PSF_NP_TWO_PASS"); if (ev) g->two_pass = atoi(ev) != 0; }
@@ -507,9 +519,9 @@ static psf_status psfgpv_init(psfgpv_handle* g) {
 void psfgpv_destroy(psfgpv_handle* g) {
   if (!g) return;
   hipSetDevice(g->base->prm.device);
-  free_np_batch(g);
+  for (auto& L : g->ln) { free_np_batch(L); hipFree(L.dFlags); }
   hipFree(g->dSt); hipFree(g->dGt); hipFree(g->dNorm2); hipFree(g->dSz); hipFree(g->dT); hipFree(g->dPiv);
-  hipFree(g->dGp); hipFree(g->dGin); hipFree(g->dGnx); hipFree(g->dRows); hipFree(g->dBpiv); hipFree(g->dB8); hipFree(g->dBocc); hipFree(g->dFlags); hipFree(g->dBfull);
+  hipFree(g->dGp); hipFree(g->dGin); hipFree(g->dGnx); hipFree(g->dRows); hipFree(g->dBpiv); hipFree(g->dB8); hipFree(g->dBocc); hipFree(g->dBfull);
   for (auto& e : g->ev) if (e) hipEventDestroy(e);
   for (auto& sx : g->sh) if (sx) hipStreamDestroy(sx);
   if (g->evFork) hipEventDestroy(g->evFork);
@@ -597,14 +609,33 @@ psf_status psfgpv_samp_p_dev(psfgpv_handle* g, uint64_t seed, uint64_t first_ind
   PSFP_QUIESCE(g->base);                // the walk's buffers are shared with the asynchronous calls in flight (which enqueue through gpv_samp_p_enqueue themselves)
   return gpv_samp_p_enqueue(g, seed, first_index, B, d_u, d_e, stream);
 }
+static psf_status gpv_batch(psfgpv_handle* g, NpLane& L, hipStream_t st, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_e, bool first_of_lane,
+                            bool may_split);
 static psf_status gpv_samp_p_enqueue(psfgpv_handle* g, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_e, void* stream) {
   psfp_handle* b = g->base;
   HIP_TRY(hipSetDevice(b->prm.device));
   hipStream_t st = (hipStream_t)stream;
-  psf_status rcb = ensure_np_batch(g, B);
+  psf_status rcb = ensure_np_batch(g, g->ln[0], B);
   if (rcb != PSF_OK) return rcb;
-  HIP_TRY(hipMemsetAsync(b->dFail, 0, 2 * sizeof(int), st));
-  HIP_TRY(hipMemsetAsync(g->dFlags, 0, 8 * sizeof(int), st));
+  const psf_status rc = gpv_batch(g, g->ln[0], st, seed, first_index, B, d_u, d_e, true, true);
+  if (rc != PSF_OK) return rc;
+  g->last_lanes = 1;
+  g->last_stream = st;
+  b->last_stream = st;
+  return PSF_OK;
+}
+// One batch on lane L, enqueued on `st`: solve, nearest plane, recombination.  first_of_lane: the first batch of the call on this lane clears all of the lane's
+// per-call words; a later one clears only the gates of the recombination ([1..3], [5..7]), so that the failure words ([0], [4]) gather every batch of the call.
+static psf_status gpv_batch(psfgpv_handle* g, NpLane& L, hipStream_t st, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_e, bool first_of_lane,
+                            bool may_split) {
+  psfp_handle* b = g->base;
+  if (first_of_lane) {
+    if (L.dFail) HIP_TRY(hipMemsetAsync(L.dFail, 0, 2 * sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(L.dFlags, 0, 8 * sizeof(int), st));
+  } else {
+    HIP_TRY(hipMemsetAsync(L.dFlags + 1, 0, 3 * sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(L.dFlags + 5, 0, 3 * sizeof(int), st));
+  }
   if (g->timing) hipEventRecord(g->ev[0], st);
   // Two halves side by side (EXPERIMENTS build only: measured and not kept).  A batch that does not fit the one-launch walk runs one launch per 64-row block, and in
   // every such launch the FP64-MFMA update tiles wait for the sampler workgroups to leave their slots (59 us of vector work, then 12 us of matrix work at C4).  Cut into
@@ -615,7 +646,7 @@ static psf_status gpv_samp_p_enqueue(psfgpv_handle* g, uint64_t seed, uint64_t f
   // result the caller's stream waits for.  profiles/r06_notes.md, "C4".  Rows are those of the undivided call bit for bit (tests/test_gpu_np_forms.py).
   size_t half0 = 0;
 #ifdef PSF_EXPERIMENTS
-  if (!g->two_pass && g->np_split > 0 && g->sh[0] && B >= 256) {
+  if (may_split && !g->two_pass && g->np_split > 0 && g->sh[0] && B >= 256) {
     const size_t h0 = round_up((B + 1) / 2, TR_BN);
     const bool shape_ok = h0 < B && !np_walk_fits(g, B, nullptr, nullptr, nullptr, nullptr) && !np_walk_fits(g, h0, nullptr, nullptr, nullptr, nullptr) &&
                           !np_walk_fits(g, B - h0, nullptr, nullptr, nullptr, nullptr);
@@ -624,15 +655,15 @@ static psf_status gpv_samp_p_enqueue(psfgpv_handle* g, uint64_t seed, uint64_t f
 #endif
   // :153-158  sol = A.solve(u), centre = -sol  (the halves solve for their own columns on their own streams)
   auto solve = [&](hipStream_t sx, size_t col0, size_t cnt) {
-    const NpCols v = np_cols(g, col0);
-    const size_t cols = col0 + cnt == B ? g->ld - col0 : round_up(cnt, TR_BN);      // the last range also rewrites the padding columns of the batch buffers
+    const NpCols v = np_cols(g, L, col0);
+    const size_t cols = col0 + cnt == B ? L.ld - col0 : round_up(cnt, TR_BN);      // the last range also rewrites the padding columns of the batch buffers
     const size_t nk16 = g->nkc * 16;
     const dim3 tgrid((unsigned)((cols + 63) / 64), (unsigned)((nk16 + 63) / 64));
     const bool tiled = b->q < (1ull << 24) && g->n <= 65536 && !psf_exp_env("PSF_NP_SOLVE_PLAIN");
     const bool acc32 = tiled && (double)g->n * (double)(b->q - 1) * (double)(b->q - 1) < 4294967296.0;
-    if (acc32) hipLaunchKernelGGL((k_np_solve_tiled<true>), tgrid, dim3(256), 0, sx, g->dT, g->n, nk16, b->q, d_u + col0 * g->n, cnt, g->ld, v.Sol, v.C0p, cols);
-    else if (tiled) hipLaunchKernelGGL((k_np_solve_tiled<false>), tgrid, dim3(256), 0, sx, g->dT, g->n, nk16, b->q, d_u + col0 * g->n, cnt, g->ld, v.Sol, v.C0p, cols);
-    else hipLaunchKernelGGL(k_np_solve, dim3(grid_for(nk16 * cols)), dim3(256), 0, sx, g->dT, g->n, nk16, b->q, b->two64, d_u + col0 * g->n, cnt, g->ld, v.Sol, v.C0p, cols);
+    if (acc32) hipLaunchKernelGGL((k_np_solve_tiled<true>), tgrid, dim3(256), 0, sx, g->dT, g->n, nk16, b->q, d_u + col0 * g->n, cnt, L.ld, v.Sol, v.C0p, cols);
+    else if (tiled) hipLaunchKernelGGL((k_np_solve_tiled<false>), tgrid, dim3(256), 0, sx, g->dT, g->n, nk16, b->q, d_u + col0 * g->n, cnt, L.ld, v.Sol, v.C0p, cols);
+    else hipLaunchKernelGGL(k_np_solve, dim3(grid_for(nk16 * cols)), dim3(256), 0, sx, g->dT, g->n, nk16, b->q, b->two64, d_u + col0 * g->n, cnt, L.ld, v.Sol, v.C0p, cols);
   };
   if (!half0) solve(st, 0, B);
   if (g->timing) hipEventRecord(g->ev[1], st);
@@ -646,22 +677,83 @@ static psf_status gpv_samp_p_enqueue(psfgpv_handle* g, uint64_t seed, uint64_t f
       HIP_TRY(hipStreamWaitEvent(g->sh[i], g->evFork, 0));
       solve(g->sh[i], off[i], cnt[i]);
       if (i == 1 && g->split_delay_us > 0) hipLaunchKernelGGL(k_np_delay, dim3(1), dim3(64), 0, g->sh[i], (unsigned long long)g->split_delay_us * 100ull);
-      rc = launch_nearest_plane(g, g->sh[i], seed, TAG_GPV, first_index + off[i], cnt[i], d_e + off[i] * g->dim, 0, off[i], false);
+      rc = launch_nearest_plane(g, L, g->sh[i], seed, TAG_GPV, first_index + off[i], cnt[i], d_e + off[i] * g->dim, 0, off[i], false);
       HIP_TRY(hipEventRecord(g->evHalf[i], g->sh[i]));
     }
     for (int i = 0; i < 2; ++i) HIP_TRY(hipStreamWaitEvent(st, g->evHalf[i], 0));      // the caller's stream continues behind both halves
     g->last_parts = 2;
   }
-  else if (!g->two_pass) { rc = launch_nearest_plane(g, st, seed, TAG_GPV, first_index, B, d_e); g->last_parts = 1; }
+  else if (!g->two_pass) { rc = launch_nearest_plane(g, L, st, seed, TAG_GPV, first_index, B, d_e); g->last_parts = 1; }
   else {
     g->last_parts = 1;
-    rc = launch_nearest_plane(g, st, seed, TAG_GPV, first_index, B, g->dE1, 0);          // a short representative e1 of the coset (A e1 = u)
-    hipLaunchKernelGGL(k_np_center_from_e, dim3(grid_for(g->nkd * 16 * g->ld, 256, 256 * 64)), dim3(256), 0, st, g->dE1, g->dim, B, g->ld, g->nkd, g->dC1, g->dFlags);
-    if (rc == PSF_OK) rc = launch_nearest_plane(g, st, seed, TAG_GPV2, first_index, B, d_e, 1);   // v ~ D_{Lambda, s, -e1}; e = e1 + v
+    rc = launch_nearest_plane(g, L, st, seed, TAG_GPV, first_index, B, L.dE1, 0);          // a short representative e1 of the coset (A e1 = u)
+    hipLaunchKernelGGL(k_np_center_from_e, dim3(grid_for(g->nkd * 16 * L.ld, 256, 256 * 64)), dim3(256), 0, st, L.dE1, g->dim, B, L.ld, g->nkd, L.dC1, L.dFlags);
+    if (rc == PSF_OK) rc = launch_nearest_plane(g, L, st, seed, TAG_GPV2, first_index, B, d_e, 1);   // v ~ D_{Lambda, s, -e1}; e = e1 + v
   }
   if (g->timing) hipEventRecord(g->ev[2], st);
   if (rc != PSF_OK) return rc;
   HIP_TRY(hipGetLastError());
+  return PSF_OK;
+}
+
+// Lane 1 and the streams the lanes run on (the experiments build creates the streams in psfgpv_init for its two-halves walk)
+static psf_status gpv_ensure_lane1(psfgpv_handle* g) {
+  NpLane& L = g->ln[1];
+  if (!L.dFlags) {
+    HIP_TRY(hipMalloc(&L.dFlags, 12 * sizeof(int)));
+    HIP_TRY(hipMemset(L.dFlags, 0, 12 * sizeof(int)));
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  for (auto& sx : g->sh) if (!sx) HIP_TRY(hipStreamCreateWithFlags(&sx, hipStreamNonBlocking));
+  if (!g->evFork) HIP_TRY(hipEventCreateWithFlags(&g->evFork, hipEventDisableTiming));
+  for (auto& e : g->evHalf) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return PSF_OK;
+}
+
+// `count` independent samp_p_dev calls in one submission (include/psf_mi355x.h).  Batch i runs on lane i % 2, each lane on one of the handle's two non-blocking
+// streams behind a fork event on the caller's stream, and the caller's stream waits for both lanes at the end.  A lane's batches are serialised on its stream, so it
+// reuses its buffers safely; across the lanes one batch's solve, projection and recombination run beside the other batch's walk -- the overlap two independent
+// handles on two streams showed (4.05 against 4.44 ms per 4096 preimages, profiles/r06_notes.md "C4"), here on one key: C4 (launch-per-block walk) 4.27 -> 3.91 ms per
+// batch at 16 batches (tools/np_many_sweep.py, profiles/np_many_sweep.json).  A batch that fits the one-launch walk (C2) does NOT gain: the walk is one latency-bound
+// chain over the whole chip, the other lane's kernels beside it stretch it more than they save (C2 3.13 -> 3.34 ms per batch at 16 batches, 4.68 at 2), so those
+// batches run in order on the caller's stream, lane 0, as the loop of single calls does.  So do all batches with timing on: psfgpv_get_timing keeps its per-stage
+// meaning for the last batch.
+psf_status psfgpv_samp_p_dev_many(psfgpv_handle* g, size_t count, const uint64_t* seeds, const uint64_t* first_indices, size_t B, const uint64_t* d_u, int64_t* d_e,
+                                  void* stream) {
+  if (!g || (count && B && (!seeds || !first_indices || !d_u || !d_e))) return PSF_ERR_PARAM;
+  if (!g->has_key) return PSF_ERR_NO_KEY;
+  if (count == 0 || B == 0) return PSF_OK;
+  if (count == 1) return psfgpv_samp_p_dev(g, seeds[0], first_indices[0], B, d_u, d_e, stream);
+  psfp_handle* b = g->base;
+  HIP_TRY(hipSetDevice(b->prm.device));
+  PSFP_QUIESCE(b);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t un = B * g->n, em = B * g->m;
+  psf_status rc = PSF_OK;
+  // (the experiments build's k_np_walk2, PSF_NP_WALK=3, is a one-launch walk outside WalkTurn: in order as well)
+  if (g->timing || g->np_walk == 3 || np_walk_fits(g, B, nullptr, nullptr, nullptr, nullptr)) {
+    rc = ensure_np_batch(g, g->ln[0], B);
+    for (size_t i = 0; i < count && rc == PSF_OK; ++i) rc = gpv_batch(g, g->ln[0], st, seeds[i], first_indices[i], B, d_u + i * un, d_e + i * em, i == 0, true);
+    if (rc != PSF_OK) return rc;
+    g->last_lanes = 1;
+  } else {
+    rc = gpv_ensure_lane1(g);
+    for (int l = 0; l < 2 && rc == PSF_OK; ++l) rc = ensure_np_batch(g, g->ln[l], B);      // both lanes sized before the fork: it synchronises the device
+    if (rc != PSF_OK) return rc;
+    HIP_TRY(hipEventRecord(g->evFork, st));                                                  // what the caller enqueued before the call (u) is complete
+    for (hipStream_t sx : g->sh) HIP_TRY(hipStreamWaitEvent(sx, g->evFork, 0));
+    for (size_t i = 0; i < count && rc == PSF_OK; ++i) {
+      const int l = (int)(i & 1);
+      rc = gpv_batch(g, g->ln[l], g->sh[l], seeds[i], first_indices[i], B, d_u + i * un, d_e + i * em, i < 2, false);
+    }
+    for (int l = 0; l < 2; ++l) {                                                            // the caller's stream continues behind both lanes (on an error too)
+      HIP_TRY(hipEventRecord(g->evHalf[l], g->sh[l]));
+      HIP_TRY(hipStreamWaitEvent(st, g->evHalf[l], 0));
+    }
+    if (rc != PSF_OK) return rc;
+    g->last_lanes = 2;
+    g->last_parts = 1;
+  }
   g->last_stream = st;
   b->last_stream = st;
   return PSF_OK;
@@ -669,10 +761,14 @@ static psf_status gpv_samp_p_enqueue(psfgpv_handle* g, uint64_t seed, uint64_t f
 
 psf_status psfgpv_last_status(psfgpv_handle* g) {
   if (!g) return PSF_ERR_PARAM;
-  psf_status rc = psfp_last_status(g->base);              // synchronises the stream of the last call
+  psf_status rc = psfp_last_status(g->base);              // synchronises the stream of the last call (behind both lanes after a many-call)
   if (rc != PSF_OK) return rc;
   int fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  HIP_TRY(hipMemcpy(fl, g->dFlags, sizeof(fl), hipMemcpyDeviceToHost));
+  for (int l = 0; l < g->last_lanes; ++l) {
+    int f[8];
+    HIP_TRY(hipMemcpy(f, g->ln[l].dFlags, sizeof(f), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 8; ++i) fl[i] |= f[i];
+  }
   g->last_generic = g->basis_generic || fl[g->two_pass ? 7 : 3] != 0;
   return (fl[0] || fl[4]) ? PSF_ERR_SAMPLER : PSF_OK;
 }
@@ -688,7 +784,7 @@ psf_status psfgpv_samp_p(psfgpv_handle* g, uint64_t seed, uint64_t first_index, 
     if (B * g->n > h->sio_du_cap) { hipFree(h->sio_du); h->sio_du = nullptr; h->sio_du_cap = 0; HIP_TRY(hipMalloc(&h->sio_du, B * g->n * sizeof(uint64_t))); h->sio_du_cap = B * g->n; }
     if (B * g->m > h->sio_de_cap) { hipFree(h->sio_de); h->sio_de = nullptr; h->sio_de_cap = 0; HIP_TRY(hipMalloc(&h->sio_de, B * g->m * sizeof(int64_t))); h->sio_de_cap = B * g->m; }
     int fl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    psf_status rc = sio_call(h, B * g->n, B * g->m, u, e, h->sio_du, h->sio_de, h->sets[0].dFail, h->sets[1].dFail, g->dFlags, 8, fl,
+    psf_status rc = sio_call(h, B * g->n, B * g->m, u, e, h->sio_du, h->sio_de, h->sets[0].dFail, h->sets[1].dFail, g->ln[0].dFlags, 8, fl,
                              [&]() { return psfgpv_samp_p_dev(g, seed, first_index, B, h->sio_du, h->sio_de, nullptr); });
     if (rc != PSF_OK) return rc;
     if (fl[0]) return PSF_ERR_SAMPLER;
@@ -729,7 +825,7 @@ psf_status psfgpv_samp_p(psfgpv_handle* g, uint64_t seed, uint64_t first_index, 
   hipLaunchKernelGGL(k_narrow_rows, dim3(grid_for(ne / 2 + 1, 256, 256 * 16)), dim3(256), 0, nullptr, h->sio_de, h->sio_d32, ne, d_ovf);
   // flags first (with the overflow word of the narrowing), then the rows in NT pieces, an event behind each: thread i widens piece i as soon as it has landed,
   // while the later pieces are still crossing PCIe
-  hipLaunchKernelGGL(k_sio_flags, dim3(1), dim3(64), 0, nullptr, h->sets[0].dFail, h->sets[1].dFail, g->dFlags, 8, hf);
+  hipLaunchKernelGGL(k_sio_flags, dim3(1), dim3(64), 0, nullptr, h->sets[0].dFail, h->sets[1].dFail, g->ln[0].dFlags, 8, hf);
   HIP_TRY(hipMemcpyAsync(hf + 12, d_ovf, sizeof(int), hipMemcpyDeviceToHost, nullptr));
   constexpr int NT = 4;
   if (!h->sio_ev[0]) for (auto& ev : h->sio_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -777,13 +873,13 @@ psf_status psfgpv_samp_p_async(psfgpv_handle* g, uint64_t seed, uint64_t first_i
   if (B == 0) return PSF_OK;
   psfp_handle* h = g->base;
   HIP_TRY(hipSetDevice(h->prm.device));
-  if (B > g->bcap) {                                        // ensure_np_batch reallocates the walk's buffers: nothing may be in flight
+  if (B > g->ln[0].bcap) {                                  // ensure_np_batch reallocates the walk's buffers: nothing may be in flight
     const psf_status rw = psfp_wait(h);
     if (rw != PSF_OK) return rw;
-    const psf_status rb = ensure_np_batch(g, B);
+    const psf_status rb = ensure_np_batch(g, g->ln[0], B);
     if (rb != PSF_OK) return rb;
   }
-  return hp_async(h, B, u, e, false, false, g->dFlags, [&](size_t off, size_t cnt, const uint64_t* d_u, int64_t* d_e, hipStream_t cs) -> psf_status {
+  return hp_async(h, B, u, e, false, false, g->ln[0].dFlags, [&](size_t off, size_t cnt, const uint64_t* d_u, int64_t* d_e, hipStream_t cs) -> psf_status {
     return gpv_samp_p_enqueue(g, seed, first_index + off, cnt, d_u, d_e, cs);
   });
 }
@@ -828,13 +924,15 @@ psf_status psfgpv_get_timing(psfgpv_handle* g, double* solve_ms, double* nearest
   return PSF_OK;
 }
 int psfgpv_two_pass(const psfgpv_handle* g) { return (g && g->two_pass) ? 1 : 0; }
-// debugging / tests: the coefficients z_i the LAST walk of the last call drew for preimage b (d doubles; the second pass's in two-pass mode)
+// debugging / tests: the coefficients z_i the LAST walk of the last call drew for preimage b (d doubles; the second pass's in two-pass mode; lane 0: the last even
+// batch of a many-call)
 extern "C" psf_status psfgpv_debug_last_z(psfgpv_handle* g, size_t b, double* z_out) {
-  if (!g || !z_out || !g->dZf || b >= g->ld) return PSF_ERR_PARAM;
+  const NpLane* L = g ? &g->ln[0] : nullptr;
+  if (!g || !z_out || !L->dZf || b >= L->ld) return PSF_ERR_PARAM;
   HIP_TRY(hipSetDevice(g->base->prm.device));
   HIP_TRY(hipDeviceSynchronize());
-  std::vector<double> zf(g->ld * g->nkb * 16);
-  HIP_TRY(hipMemcpy(zf.data(), g->dZf, zf.size() * sizeof(double), hipMemcpyDeviceToHost));
+  std::vector<double> zf(L->ld * g->nkb * 16);
+  HIP_TRY(hipMemcpy(zf.data(), L->dZf, zf.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (size_t i = 0; i < g->dim; ++i) z_out[i] = zf[((b / TR_BN) * g->nkb + i / 16) * TR_CHUNK + tr_chunk_pos((int)(b % TR_BN), (int)(i % 16))];
   return PSF_OK;
 }
@@ -846,7 +944,12 @@ psf_status psfgpv_get_nearest_plane_form(psfgpv_handle* g, int* form, int* preim
   HIP_TRY(hipSetDevice(g->base->prm.device));
   HIP_TRY(hipStreamSynchronize(g->last_stream));
   unsigned long long r = 0;
-  HIP_TRY(hipMemcpy(&r, g->dFlags + 8, sizeof(r), hipMemcpyDeviceToHost));
+  for (const NpLane& L : g->ln) {                            // both lanes: every batch of a many-call
+    if (!L.dFlags) continue;
+    unsigned long long rl = 0;
+    HIP_TRY(hipMemcpy(&rl, L.dFlags + 8, sizeof(rl), hipMemcpyDeviceToHost));
+    r += rl;
+  }
   if (form) *form = (g->last_form == 0 && g->last_parts == 2) ? 2 : g->last_form;
   if (preimages_per_wave) *preimages_per_wave = g->last_G;
   if (blocks) *blocks = g->nblk;
@@ -875,7 +978,11 @@ psf_status psfgpv_get_nearest_plane_stats(psfgpv_handle* g, size_t* blocks, size
   if (!g) return PSF_ERR_PARAM;
   HIP_TRY(hipStreamSynchronize(g->last_stream));
   int fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  HIP_TRY(hipMemcpy(fl, g->dFlags, sizeof(fl), hipMemcpyDeviceToHost));
+  for (int l = 0; l < g->last_lanes; ++l) {
+    int f[8];
+    HIP_TRY(hipMemcpy(f, g->ln[l].dFlags, sizeof(f), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 8; ++i) fl[i] |= f[i];
+  }
   if (blocks) *blocks = g->nblk;
   if (generic_recombination) *generic_recombination = (g->basis_generic || fl[g->two_pass ? 7 : 3]) ? 1 : 0;
   return PSF_OK;
@@ -1170,6 +1277,10 @@ uint64_t psfring_async_next_ticket(const psfring_handle* h) { return h ? psfgpv_
 psf_status psfring_wait_ticket(psfring_handle* h, uint64_t ticket) { return h ? psfgpv_wait_ticket(h->g, ticket) : PSF_ERR_PARAM; }
 psf_status psfring_samp_p_dev(psfring_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_sigma, void* stream) {
   return h ? psfgpv_samp_p_dev(h->g, seed, first_index, B, d_u, d_sigma, stream) : PSF_ERR_PARAM;
+}
+psf_status psfring_samp_p_dev_many(psfring_handle* h, size_t count, const uint64_t* seeds, const uint64_t* first_indices, size_t B, const uint64_t* d_u, int64_t* d_sigma,
+                                   void* stream) {
+  return h ? psfgpv_samp_p_dev_many(h->g, count, seeds, first_indices, B, d_u, d_sigma, stream) : PSF_ERR_PARAM;
 }
 // gpv_ring.rs:243-247: the domain check, then u = sum_j a_j * sigma_j in R_q.  With the images of a (ring_install) that is k+2 forward
 // transforms, k+2 leaf products and one inverse transform per preimage (k_ring_fa); PSF_RING_FA=matmul keeps the product with rot^-(iota(a)) on

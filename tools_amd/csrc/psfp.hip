@@ -1658,6 +1658,32 @@ psf_status psfp_samp_p_dev(psfp_handle* h, uint64_t seed, uint64_t first_index, 
   return run_samp_p(h, seed, first_index, B, d_u, d_e, (hipStream_t)stream);
 }
 
+// `count` independent psfp_samp_p_dev calls in one submission, in order on the caller's stream (include/psf_mi355x.h).  No second lane: at large batches the FP64
+// product holds every SIMD and nothing issues beside it (profiles/r03_probe_coissue.log).  The failure word of every batch is kept (keep_fail, as the slices of a
+// host-pointer call do); the gates of the later stages ([1..3]) are cleared in front of each batch as a single call clears them.
+psf_status psfp_samp_p_dev_many(psfp_handle* h, size_t count, const uint64_t* seeds, const uint64_t* first_indices, size_t B, const uint64_t* d_u, int64_t* d_e, void* stream) {
+  if (!h || (count && B && (!seeds || !first_indices || !d_u || !d_e))) return PSF_ERR_PARAM;
+  if (!h->has_key || !h->has_pub) return PSF_ERR_NO_KEY;
+  if (count == 0 || B == 0) return PSF_OK;
+  if (count == 1) return psfp_samp_p_dev(h, seeds[0], first_indices[0], B, d_u, d_e, stream);
+  if (h->pipeline) return PSF_ERR_UNSUPPORTED;             // PSF_PIPELINE=1 alternates two sets of failure words per call: single calls only (as psfp_samp_p_async)
+  HIP_TRY(hipSetDevice(h->prm.device));
+  PSFP_QUIESCE(h);
+  psf_status rc = ensure_batch(h, B);
+  if (rc != PSF_OK) return rc;
+  if (h->timing) clear_slots(h);
+  hipStream_t st = (hipStream_t)stream;
+  struct FailGuard { psfp_handle* h; ~FailGuard() { h->keep_fail = false; } } guard{h};
+  for (size_t i = 0; i < count && rc == PSF_OK; ++i) {
+    if (i > 0) {
+      h->keep_fail = true;
+      HIP_TRY(hipMemsetAsync(h->dFail + 1, 0, 3 * sizeof(int), st));
+    }
+    rc = run_samp_p(h, seeds[i], first_indices[i], B, d_u + i * B * h->n, d_e + i * B * h->m, st);
+  }
+  return rc;
+}
+
 // ---- host-pointer entry points ---------------------------------------------------------------------------------------------------------------
 constexpr size_t SIO_MAX_BYTES = (size_t)1 << 20;           // calls whose u + e fit this take the one-buffer form (at 4 MB the runtime's copies are faster again: 1.27 vs 1.17 ms at C3, 16 preimages)
 // flags of a small call into the pinned buffer: [0] = a[0] | b[0] (the two failure words psfp_last_status reads), [1 ..] = c[0 .. nc)

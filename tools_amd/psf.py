@@ -15,6 +15,16 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _many(fn, h, d_u_ptr, d_e_ptr, B, seeds, first_indices, stream):
+    """X_samp_p_dev_many: len(seeds) batches of B rows, batch i with seeds[i] / first_indices[i] (include/psf_mi355x.h)."""
+    s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+    f = np.ascontiguousarray(np.asarray(first_indices, dtype=np.uint64).reshape(-1))
+    if s.shape != f.shape:
+        raise PsfError(_ffi.ERR_PARAM, "samp_p_dev_many")
+    check(fn(h, C.c_size_t(s.size), _p(s, C.c_uint64), _p(f, C.c_uint64), C.c_size_t(B), C.c_void_p(d_u_ptr), C.c_void_p(d_e_ptr),
+             C.c_void_p(stream or 0)), "samp_p_dev_many")
+
+
 class GadgetParameters:
     """gadget_parameters.rs:44-52.  distribution = PlusMinusOneZero (trapdoor_distribution.rs:52-53)."""
 
@@ -239,6 +249,10 @@ class PSFPerturbation:
         check(lib().psfp_samp_p_dev(self._h, C.c_uint64(seed), C.c_uint64(first_index), C.c_size_t(B), C.c_void_p(d_u_ptr),
                                     C.c_void_p(d_e_ptr), C.c_void_p(stream or 0)), "samp_p_dev")
 
+    def samp_p_dev_many(self, d_u_ptr, d_e_ptr, B, seeds, first_indices, stream=None):
+        """len(seeds) samp_p_dev calls in one submission: batch i reads d_u + i*B*n, writes d_e + i*B*m (the bytes of the loop of samp_p_dev calls)."""
+        _many(lib().psfp_samp_p_dev_many, self._h, d_u_ptr, d_e_ptr, B, seeds, first_indices, stream)
+
     def f_a_dev(self, d_e_ptr, d_u_ptr, d_ok_ptr, B, stream=None):
         check(lib().psfp_f_a_dev(self._h, C.c_size_t(B), C.c_void_p(d_e_ptr), C.c_void_p(d_u_ptr), C.c_void_p(d_ok_ptr),
                                  C.c_void_p(stream or 0)), "f_a_dev")
@@ -402,6 +416,11 @@ class PSFGPV:
     def samp_p_dev(self, d_u_ptr, d_e_ptr, B, seed=0, first_index=0, stream=None):
         check(lib().psfgpv_samp_p_dev(self._h, C.c_uint64(seed), C.c_uint64(first_index), C.c_size_t(B), C.c_void_p(d_u_ptr),
                                       C.c_void_p(d_e_ptr), C.c_void_p(stream or 0)), "samp_p_dev")
+
+    def samp_p_dev_many(self, d_u_ptr, d_e_ptr, B, seeds, first_indices, stream=None):
+        """len(seeds) samp_p_dev calls in one submission, on two lanes that overlap one batch's solve and recombination with the other's walk: batch i reads
+        d_u + i*B*n, writes d_e + i*B*m (the bytes of the loop of samp_p_dev calls)."""
+        _many(lib().psfgpv_samp_p_dev_many, self._h, d_u_ptr, d_e_ptr, B, seeds, first_indices, stream)
 
     def f_a_dev(self, d_e_ptr, d_u_ptr, d_ok_ptr, B, stream=None):
         check(lib().psfgpv_f_a_dev(self._h, C.c_size_t(B), C.c_void_p(d_e_ptr), C.c_void_p(d_u_ptr), C.c_void_p(d_ok_ptr),
@@ -575,6 +594,10 @@ class PSFGPVRing:
     def samp_p_dev(self, d_u_ptr, d_sigma_ptr, B, seed=0, first_index=0, stream=None):
         check(lib().psfring_samp_p_dev(self._h, C.c_uint64(seed), C.c_uint64(first_index), C.c_size_t(B), C.c_void_p(d_u_ptr),
                                        C.c_void_p(d_sigma_ptr), C.c_void_p(stream or 0)), "samp_p_dev")
+
+    def samp_p_dev_many(self, d_u_ptr, d_sigma_ptr, B, seeds, first_indices, stream=None):
+        """as PSFGPV.samp_p_dev_many: batch i reads d_u + i*B*n, writes d_sigma + i*B*n(k+2)"""
+        _many(lib().psfring_samp_p_dev_many, self._h, d_u_ptr, d_sigma_ptr, B, seeds, first_indices, stream)
 
     def f_a_dev(self, d_sigma_ptr, d_u_ptr, d_ok_ptr, B, stream=None):
         check(lib().psfring_f_a_dev(self._h, C.c_size_t(B), C.c_void_p(d_sigma_ptr), C.c_void_p(d_u_ptr), C.c_void_p(d_ok_ptr),
