@@ -267,7 +267,7 @@ psf_status psfp_samp_p_dev(psfp_handle*, uint64_t seed, uint64_t first_index, si
  * of per-batch buffers, allocated by the first such call with count >= 2, and two streams of the handle): one batch's solve, projection and
  * recombination overlap the other lane's walk.  Batches that fit the one-launch walk (C2) gain nothing from that and run in order on `stream`, as do
  * all batches with timing enabled (psfgpv_enable_timing; get_timing then describes the last batch).  psfp_samp_p_dev_many runs the batches in order
- * on `stream` (PSF_ERR_UNSUPPORTED under the experiments build's PSF_PIPELINE=1). */
+ * on `stream`. */
 psf_status psfp_samp_p_dev_many(psfp_handle*, size_t count, const uint64_t* seeds, const uint64_t* first_indices, size_t B,
                                 const uint64_t* d_u, int64_t* d_e, void* stream);
 psf_status psfp_samp_d_dev(psfp_handle*, uint64_t seed, uint64_t first_index, size_t B, int64_t* d_e, void* stream);

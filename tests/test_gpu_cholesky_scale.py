@@ -140,14 +140,15 @@ def test_full_size_preimages_have_the_right_variance_in_every_panel(c3):
 
 @pytest.mark.parametrize("n,q", [(8, 64), (20, 257), (40, 2**20)])
 def test_the_three_cholesky_forms_agree(monkeypatch, exp_lib, oracle, n, q):
-    """PSF_CHOL selects the factorisation: on the key's chunk stream (the default for large keys: no dense matrix), left-looking on a dense matrix with
-    the LDS-staged GEMM (the default below 16 GB), right-looking (rounds 1-2).  Same key seed: A and R are bitwise equal, the factors agree with each
-    other and with the oracle's unblocked recurrence within rounding, and each reproduces Sigma_2; m runs from one partial panel to several panels."""
+    """Three factorisations of the same Sigma_2: on the key's chunk stream with Sigma_2 assembled panel by panel (PSF_CHOL=stream, the default for large
+    keys: no dense matrix), the hybrid (no switch, the default below 16 GB: Sigma_2 dense at once, factorisation on the chunk stream) and the oracle's
+    unblocked recurrence.  Same key seed: A and R are bitwise equal, the two device factors agree bit for bit and with the oracle within rounding;
+    m runs from one partial panel to several panels."""
     import tools_amd as T
     r, s = 4.0, 120.0
     gp = T.GadgetParameters.init_default(n, q)
     got = {}
-    for form in ("stream", "gemm", "right", "hybrid"):                 # "hybrid" = no switch: the default below 16 GB (Sigma_2 dense at once, factorisation on the chunk stream)
+    for form in ("stream", "hybrid"):                                 # "hybrid" = no switch: the default below 16 GB (Sigma_2 dense at once, factorisation on the chunk stream)
         if form == "hybrid":
             monkeypatch.delenv("PSF_CHOL", raising=False)
         else:
@@ -157,9 +158,8 @@ def test_the_three_cholesky_forms_agree(monkeypatch, exp_lib, oracle, n, q):
         got[form] = (A, R, Lp)
         psf.close()
     A, R, L0 = got["stream"]
-    for form in ("gemm", "right", "hybrid"):
-        assert (got[form][0] == A).all() and (got[form][1] == R).all()
-        np.testing.assert_allclose(got[form][2], L0, rtol=0, atol=1e-10 * np.abs(L0).max())
+    assert (got["hybrid"][0] == A).all() and (got["hybrid"][1] == R).all()
+    np.testing.assert_allclose(got["hybrid"][2], L0, rtol=0, atol=1e-10 * np.abs(L0).max())
     assert (got["hybrid"][2] == L0).all()                             # the hybrid copies its panels out of the same integers: the stream form's factor bit for bit
     orc = oracle.PSFPerturbation(oracle.gadget_params_default(n, q), r, s)
     rc, Lref = orc.compute_sqrt_sigma_2(R, s)

@@ -1,5 +1,5 @@
-"""PSF_PIPELINE=1 (two buffer sets, normals + FP64 product of call i+1 overlapped with the sampling stages of call i)
-must give the same bits as the default sequential mode; run in a subprocess because the switch is read at handle creation."""
+"""Forms of samp_p that must give the same bits (the FP64 product kernels, the lock-step gadget kernel; the latter in a subprocess because its switch
+is read at handle creation), and the host-pointer and multi-rank paths around samp_p."""
 import os
 import subprocess
 import sys
@@ -32,23 +32,19 @@ print(h.hexdigest())
 ''' % ROOT
 
 
-def run(mode, **extra):
+def run(**switches):
     from tests.conftest import exp_env
-    env = exp_env(PSF_PIPELINE=mode, **extra) if (mode != "0" or extra) else exp_env()      # the plain run is the release library, a switch the experiments build
+    env = exp_env(**switches)      # without switches the release library, with them the experiments build
     r = subprocess.run([sys.executable, "-c", SCRIPT], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     return r.stdout.strip().splitlines()[-1]
 
 
-def test_pipelined_mode_is_bit_identical():
-    assert run("0") == run("1")
-
-
 def test_the_fp64_product_kernels_give_the_same_bits(monkeypatch, exp_lib):
-    """k_trmm_f64_big (one workgroup per CU, accumulators in AccVGPRs: the default), k_trmm_f64_reg (PSF_TRMM_VARIANT=1) and k_trmm_f64 (LDS-staged,
-    PSF_TRMM_VARIANT=0) run the same ascending fma chains: x and everything downstream must agree bit for bit, here on keys of several row-blocks
-    (m = 932: 8 blocks of 128 with a ragged top; structured: 484 rows = 4 blocks, and with n = 40 an ODD number of row-blocks, so the last 256-row
-    tile has an empty lower half) and a batch that leaves part of the last column block empty."""
+    """k_trmm_f64_big (one workgroup per CU, accumulators in AccVGPRs: forced with PSF_TRMM_STREAM_MAX=0) and the streaming product that serves this batch
+    size by default run the same ascending fma chains: x and everything downstream must agree bit for bit, here on keys of several row-blocks (m = 932:
+    8 blocks of 128 with a ragged top; structured: 484 rows = 4 blocks, and with n = 40 an ODD number of row-blocks, so the last 256-row tile of
+    k_trmm_f64_big has an empty lower half) and a batch that leaves part of the last column block empty."""
     import numpy as np
     import tools_amd as T
     for n, structured in ((64, False), (64, True), (40, False)):
@@ -56,20 +52,19 @@ def test_the_fp64_product_kernels_give_the_same_bits(monkeypatch, exp_lib):
         psf = T.PSFPerturbation(gp, 3.0, 300.0, structured=structured)
         psf.trap_gen(4, export=False)
         u = np.random.default_rng(5).integers(0, 128, size=(300, n), dtype=np.int64)
-        res = {}
-        for v in ("0", "1", "2"):
-            monkeypatch.setenv("PSF_TRMM_VARIANT", v)
-            res[v] = psf.samp_p_stages(u, seed=9)
-        for v in ("0", "1"):
-            for key in ("x", "p", "e"):
-                assert (res[v][key] == res["2"][key]).all(), (n, structured, v, key)
-        assert (psf.f_a(res["2"]["e"]) == u).all()
+        monkeypatch.delenv("PSF_TRMM_STREAM_MAX", raising=False)
+        stream = psf.samp_p_stages(u, seed=9)
+        monkeypatch.setenv("PSF_TRMM_STREAM_MAX", "0")
+        big = psf.samp_p_stages(u, seed=9)
+        for key in ("x", "p", "e"):
+            assert (stream[key] == big[key]).all(), (n, structured, key)
+        assert (psf.f_a(big["e"]) == u).all()
 
 
 def test_lock_step_gadget_kernel_is_bit_identical():
     """PSF_GADGET_QUEUE=0 selects the lock-step gadget sampler (one lane per problem, sample_z loop) instead of the
     READY/PENDING queue kernel; same Philox streams, same bits."""
-    assert run("0") == run("0", PSF_GADGET_QUEUE="0")
+    assert run() == run(PSF_GADGET_QUEUE="0")
 
 
 @pytest.mark.gpu
@@ -247,10 +242,10 @@ def test_overlapped_async_calls_return_the_rows_of_synchronous_ones(oracle):
     psf.close()
 
 
-@pytest.mark.parametrize("mode", ["sdma", "runtime", "kernel:8"])
+@pytest.mark.parametrize("mode", ["sdma", "runtime"])
 def test_every_chunk_transport_of_the_host_path_returns_the_same_rows(oracle, monkeypatch, exp_lib, mode):
-    """PSF_HOST_COPY picks how a chunk of narrowed rows crosses PCIe: the DMA engine through the HSA runtime (default, psf_sdma.hpp), the HIP runtime's copies,
-    or a copy kernel storing into pinned memory.  Each must hand back the rows of the device-pointer path, with chunks smaller than a call (PSF_HOST_CHUNK_MB=1:
+    """PSF_HOST_COPY picks how a chunk of narrowed rows crosses PCIe: the DMA engine through the HSA runtime (default, psf_sdma.hpp) or the HIP runtime's
+    copies (the fallback when the DMA path cannot open).  Each must hand back the rows of the device-pointer path, with chunks smaller than a call (PSF_HOST_CHUNK_MB=1:
     several chunks per worker, both pinned buffers of a worker in use) and asynchronous calls cut into slices or not."""
     import numpy as np
     import torch

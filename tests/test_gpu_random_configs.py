@@ -133,7 +133,7 @@ def test_ring_random_configuration(oracle, case):
     psf.close()
 
 
-LEGACY = {"PSF_TRMM_STREAM_MAX": "0", "PSF_FUSED_MAX": "0", "PSF_GADGET_WAVE": "0", "PSF_GADGET_WAVE16": "0", "PSF_COMPACT_D": "0", "PSF_ZQ_FOLD128": "0"}
+LEGACY = {"PSF_TRMM_STREAM_MAX": "0", "PSF_FUSED_MAX": "0", "PSF_GADGET_WAVE": "0", "PSF_COMPACT_D": "0", "PSF_ZQ_FOLD128": "0"}
 
 
 @pytest.mark.parametrize("case", range(0, 64, 3))

@@ -278,14 +278,14 @@ def _with_env(env, fn):
 
 @pytest.mark.parametrize("B", [17, 24, 32, 33, 48, 64, 65, 80, 96, 97, 100, 128, 129, 160, 192, 300, 449, 1000, 1100, 1300, 1472, 1600, 1728])
 def test_shared_operand_tiles_give_the_batch_kernels_bits(exp_pair, exp_lib, oracle, B):
-    """k_trmm_stream_wg (64 x 64 tiles, operands shared through LDS; the default at 33 ... 64 preimages; beyond 64 the experiments build's column groups of 128 on
-    halves of eight waves) at every batch size the experiments build lets it serve (PSF_STREAM_WG = smallest batch, PSF_STREAM_WG_MAX = largest), the default form of
+    """k_trmm_stream_wg (64 x 64 tiles, operands shared through LDS; the default at 33 ... 64 preimages) forced at every batch size here (PSF_STREAM_WG = smallest
+    batch up to 64, PSF_STREAM_WG192 = the range beyond 64 where the tiles serve column groups of 64 of a tile group side by side), the default form of
     the batch size (17 ... 32: k_trmm_stream_wg32, 64 x 32 tiles; 65 ... 96: one launch of each over a stream of six fragments; beyond 128 with an odd number of column groups of 64: the 64 x 64 tiles again) and the one-wave tasks: the bits of k_trmm_f64_big (PSF_TRMM_STREAM_MAX = 0).  The shapes have 31 / 59 / 83 sixteen-row
     tiles: the last tile group is ragged, the task count odd or even, and the ring runs 16 k-steps past the diagonal."""
     psf, orc, n, q = exp_pair
     u = oracle.uniform_targets(6, B, n, q)
     ref = _with_env({"PSF_TRMM_STREAM_MAX": "0", "PSF_STREAM_WG": None, "PSF_STREAM_WG_MAX": None}, lambda: psf.samp_p_stages(u, seed=19, first_index=7))
-    got = _with_env({"PSF_TRMM_STREAM_MAX": "4096", "PSF_STREAM_WG": "17", "PSF_STREAM_WG_MAX": "1024"}, lambda: psf.samp_p_stages(u, seed=19, first_index=7))
+    got = _with_env({"PSF_TRMM_STREAM_MAX": "4096", "PSF_STREAM_WG": "17", "PSF_STREAM_WG_MAX": None, "PSF_STREAM_WG192": "65:2048"}, lambda: psf.samp_p_stages(u, seed=19, first_index=7))
     one = _with_env({"PSF_TRMM_STREAM_MAX": "4096", "PSF_STREAM_WG": "0", "PSF_STREAM_WG32": "0", "PSF_STREAM_WG96": "0", "PSF_STREAM_WG192": "0"}, lambda: psf.samp_p_stages(u, seed=19, first_index=7))
     dflt = _with_env({"PSF_TRMM_STREAM_MAX": None, "PSF_STREAM_WG": None, "PSF_STREAM_WG_MAX": None, "PSF_STREAM_WG32": None, "PSF_STREAM_WG96": None, "PSF_STREAM_WG192": None}, lambda: psf.samp_p_stages(u, seed=19, first_index=7))
     assert (dflt["x"].view(np.uint64) == ref["x"].view(np.uint64)).all(), "the default form of this batch size differs from k_trmm_f64_big"
@@ -322,7 +322,7 @@ def test_gadget_walk_with_a_quad_per_problem_equals_the_other_forms(exp_pair, ex
     u = oracle.uniform_targets(12, B, n, q)
     ref = _with_env({"PSF_GADGET_QUAD": "0", "PSF_GADGET_ROW": "0"}, lambda: psf.samp_p_stages(u, seed=23, first_index=99))
     quad = _with_env({"PSF_GADGET_QUAD": "100000000", "PSF_GADGET_ROW": "0", "PSF_GADGET_WAVE": "0"}, lambda: psf.samp_p_stages(u, seed=23, first_index=99))
-    queue = _with_env({"PSF_GADGET_QUAD": "0", "PSF_GADGET_ROW": "0", "PSF_GADGET_WAVE": "0", "PSF_GADGET_WAVE16": "0"}, lambda: psf.samp_p_stages(u, seed=23, first_index=99))
+    queue = _with_env({"PSF_GADGET_QUAD": "0", "PSF_GADGET_ROW": "0", "PSF_GADGET_WAVE": "0"}, lambda: psf.samp_p_stages(u, seed=23, first_index=99))
     row = _with_env({"PSF_GADGET_ROW": "100000000", "PSF_GADGET_WAVE": "0"}, lambda: psf.samp_p_stages(u, seed=23, first_index=99))      # sixteen lanes per problem
     wave = _with_env({"PSF_GADGET_WAVE": "100000000"}, lambda: psf.samp_p_stages(u, seed=23, first_index=99))                             # one wave per problem
     assert (quad["z"] == ref["z"]).all() and (queue["z"] == ref["z"]).all() and (row["z"] == ref["z"]).all() and (wave["z"] == ref["z"]).all()

@@ -1,7 +1,7 @@
 """Every experiment switch of the PSFPerturbation path (alive in the experiments build only: tools_amd/csrc `make exp`; the release library reads none) selects another kernel, stream arrangement or slicing for the SAME arithmetic: on seeded random shapes
 (ragged batches on both sides of the 128 / 256 tile boundaries, key dimensions with partial row blocks, moduli of one to three limbs) each setting must
 reproduce the default's bytes.  One subprocess per setting (the switches are read at handle creation / first use); the key comes from the same seed every time,
-so key generation under PSF_CHOL's three forms is part of what is compared (A, R bitwise; the factors agree within rounding, checked elsewhere), and the
+so key generation under both Cholesky forms (the default hybrid and PSF_CHOL=stream) is part of what is compared (A, R bitwise; the factors agree within rounding, checked elsewhere), and the
 preimages are compared through the factor of the default form, loaded explicitly."""
 import json
 import os
@@ -58,8 +58,7 @@ A, (R, L, _) = psf.trap_gen(900 + case)
 np.savez(sys.argv[2], A=A, R=R, L=L)
 ''' % ROOT
 
-SETTINGS = [{}, {"PSF_PIPELINE": "1"}, {"PSF_HALVES": "1"}, {"PSF_HOST_SLICE": "64"}, {"PSF_HOST_SLICE": "200"}, {"PSF_GADGET_QUEUE": "0"}, {"PSF_ROUND": "wave"},
-            {"PSF_TRMM_VARIANT": "0"}, {"PSF_TRMM_VARIANT": "1"}, {"PSF_TRMM_GR": "4", "PSF_TRMM_GC": "8"}]
+SETTINGS = [{}, {"PSF_HOST_SLICE": "64"}, {"PSF_HOST_SLICE": "200"}, {"PSF_GADGET_QUEUE": "0"}, {"PSF_ROUND": "wave"}, {"PSF_TRMM_GR": "4", "PSF_TRMM_GC": "8"}]
 
 
 def run(script, case, path, **extra):
@@ -82,13 +81,16 @@ def test_every_switch_reproduces_the_default_bytes(tmp_path, case):
 
 @pytest.mark.parametrize("case", range(2))
 def test_key_generation_forms_produce_the_same_key_material(tmp_path, case):
-    """A and R are bitwise the same under the three Cholesky forms (they do not depend on the factorisation); the factors agree to rounding."""
+    """A and R are bitwise the same under both Cholesky forms, the default hybrid (release library) and PSF_CHOL=stream (they do not depend on the
+    factorisation); the factors agree to rounding."""
     import numpy as np
     keys = {}
-    for form in ("gemm", "stream", "right"):
+    for form in ("hybrid", "stream"):
         path = str(tmp_path / f"key_{form}.npz")
-        run(KEYGEN, case, path, PSF_CHOL=form)
+        if form == "hybrid":
+            run(KEYGEN, case, path)
+        else:
+            run(KEYGEN, case, path, PSF_CHOL=form)
         keys[form] = np.load(path)
-    for form in ("stream", "right"):
-        assert (keys[form]["A"] == keys["gemm"]["A"]).all() and (keys[form]["R"] == keys["gemm"]["R"]).all()
-        np.testing.assert_allclose(keys[form]["L"], keys["gemm"]["L"], rtol=0, atol=1e-9 * np.abs(keys["gemm"]["L"]).max())
+    assert (keys["stream"]["A"] == keys["hybrid"]["A"]).all() and (keys["stream"]["R"] == keys["hybrid"]["R"]).all()
+    np.testing.assert_allclose(keys["stream"]["L"], keys["hybrid"]["L"], rtol=0, atol=1e-9 * np.abs(keys["hybrid"]["L"]).max())

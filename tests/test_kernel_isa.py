@@ -1,7 +1,7 @@
 """The default FP64 product k_trmm_f64_big -- and k_chol_update_big, the same K loop run on two row blocks of the key's chunk stream -- rely on orderings the compiler cannot see (asm-statement MFMAs, loads whose results are
 in flight, a hand-written drain before the accumulators are read).  This test compiles the device code for gfx950 (no GPU needed) and
 checks the EMITTED instruction stream, so that a toolchain bump which breaks one of the assumptions fails here and not as a silent
-wrong bit on the GPU (psf_kernels.hpp).  If it fails: PSF_TRMM_VARIANT=1 (k_trmm_f64_reg, builtin MFMAs) is the fallback."""
+wrong bit on the GPU (psf_kernels.hpp)."""
 import os
 import re
 import shutil

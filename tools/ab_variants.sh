@@ -12,7 +12,3 @@ for cfg in c2 c4; do
   timeout 300 python3 bench.py --config $cfg --no-cpu-baseline --steps 10 --warmup 2 > $O/${cfg}_base.log 2>&1; line $O/${cfg}_base.log ${cfg}_base
   PSF_NP_IMMEDIATE=1 timeout 300 python3 bench.py --config $cfg --no-cpu-baseline --steps 10 --warmup 2 > $O/${cfg}_imm.log 2>&1; line $O/${cfg}_imm.log ${cfg}_imm
 done
-# FP64 product
-PSF_TRMM_VARIANT=1 timeout 300 python3 -m pytest tests/test_gpu_psfp_parity.py tests/test_gpu_structured.py -q -m gpu -x 2>&1 | tail -2
-timeout 300 python3 bench.py --config c3 --no-cpu-baseline --steps 5 --warmup 1 > $O/c3_v0.log 2>&1; line $O/c3_v0.log c3_v0
-PSF_TRMM_VARIANT=1 timeout 300 python3 bench.py --config c3 --no-cpu-baseline --steps 5 --warmup 1 > $O/c3_v1.log 2>&1; line $O/c3_v1.log c3_v1

@@ -374,7 +374,6 @@ int main(int argc, char** argv) {
   for (int bi = 0; bi < nbi; ++bi) flops += 2.0 * 128 * 128 * 128 * (bi + 1) * nbj;
   const int GR = argc > 5 ? atoi(argv[5]) : 8, GC = argc > 6 ? atoi(argv[6]) : 8;      // super-tile shape, GR * GC = 64
   const unsigned grid = tr_grid_size(nbi, nbj, GR, GC);
-  hipFuncSetAttribute(reinterpret_cast<const void*>(k_trmm_f64), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TR_CHUNK * sizeof(double));
   hipFuncSetAttribute(reinterpret_cast<const void*>(k_ring_variant<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 2048 * 8);
   hipFuncSetAttribute(reinterpret_cast<const void*>(k_ring_variant<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 2048 * 8);
   unsigned* meet; hipMalloc(&meet, (size_t)tr_group_count(nbi, nbj, GR, GC) * TR_SYNC_SLOTS * 4);
@@ -388,7 +387,7 @@ int main(int argc, char** argv) {
     for (int r = 0; r < reps; ++r) {
       hipEventRecord(e0, 0);
       switch (which) {
-        case 0: hipLaunchKernelGGL(k_trmm_f64, dim3(grid), dim3(256), 4 * TR_CHUNK * sizeof(double), 0, L, D, X, nbi, nbj, nkb, ldx, GR, GC, (size_t)nbi * 128); break;
+        case 0: hipLaunchKernelGGL(k_trmm_f64_big, dim3(tr_grid_size((nbi + 1) / 2, nbj, 8, 4)), dim3(256), 0, 0, L, D, X, nbi, nbj, nkb, ldx, 8, 4, (size_t)nbi * 128); break;
         case 19: hipLaunchKernelGGL((k_big_variant<4, 0>), dim3(tr_grid_size(nbi / 2, nbj, 4, 8)), dim3(256), 0, 0, L, D, X, nbi, nbj, nkb, ldx, 4, 8); break;
         case 20: hipLaunchKernelGGL((k_big_variant<5, 0>), dim3(tr_grid_size(nbi / 2, nbj, 4, 8)), dim3(256), 0, 0, L, D, X, nbi, nbj, nkb, ldx, 4, 8); break;
         case 21: hipLaunchKernelGGL((k_big_variant<4, 1>), dim3(tr_grid_size(nbi / 2, nbj, 4, 8)), dim3(256), 0, 0, L, D, X, nbi, nbj, nkb, ldx, 4, 8); break;
@@ -402,7 +401,6 @@ int main(int argc, char** argv) {
         case 29: hipLaunchKernelGGL((k_big_variant<4, 2>), dim3(tr_grid_size(nbi / 2, nbj, 8, 4)), dim3(256), 0, 0, L, D, X, nbi, nbj, nkb, ldx, 8, 4); break;
         case 30: hipLaunchKernelGGL((k_big_variant<4, 3>), dim3(tr_grid_size(nbi / 2, nbj, 8, 4)), dim3(256), 0, 0, L, D, X, nbi, nbj, nkb, ldx, 8, 4); break;
         case 31: hipLaunchKernelGGL((k_big_variant<4, 4>), dim3(tr_grid_size(nbi / 2, nbj, 8, 4)), dim3(256), 0, 0, L, D, X, nbi, nbj, nkb, ldx, 8, 4); break;
-        case 12: hipLaunchKernelGGL(k_trmm_f64_reg, dim3(grid), dim3(256), 0, 0, L, D, X, nbi, nbj, nkb, ldx, GR, GC, (size_t)nbi * 128); break;
         case 13: for (int ph = 1; ph <= 2; ++ph) hipLaunchKernelGGL(k_reg_phase_meet, dim3(grid), dim3(256), 0, 0, L, D, X, nbi, nbj, nkb, ldx, GR, GC, (size_t)nbi * 128, ph, (unsigned*)nullptr); break;
         case 15: hipMemsetAsync(meet, 0, (size_t)tr_group_count(nbi, nbj, GR, GC) * TR_SYNC_SLOTS * 4, 0);
                  for (int ph = 1; ph <= 2; ++ph) hipLaunchKernelGGL(k_reg_phase_meet, dim3(grid), dim3(256), 0, 0, L, D, X, nbi, nbj, nkb, ldx, GR, GC, (size_t)nbi * 128, ph, meet); break;
@@ -441,7 +439,7 @@ int main(int argc, char** argv) {
     printf("%-62s best %8.3f ms  avg %8.3f ms  %6.2f TFLOP/s (best)  mismatches vs shipped: %ld  clock %.0f MHz (peak there %.2f)  %s\n", name, best, sum / reps, flops / best * 1e-9, bad, mhz, 256 * 4 * 32 * mhz * 1e-6, err == hipSuccess ? "" : hipGetErrorString(err));
     fflush(stdout);
   };
-  run("k_trmm_f64 (shipped: LDS-DMA, 2 stages of 16 coordinates)", 0, false);
+  run("k_trmm_f64_big (shipped: the reference of the bit checks)", 0, false);
   run("registers, 4 k-steps in flight", 1, true);
   run("registers, 4 in flight, loads re-read 8 steps (cache hits)", 2, false);
   run("registers, no loads in the loop (issue pattern only)", 3, false);
@@ -451,26 +449,7 @@ int main(int argc, char** argv) {
   run("same ring, loads re-read 8 half chunks (cache hits)", 7, false);
   run("registers, no loads in the loop, accumulators in AccVGPRs", 8, false);
   run("registers, 6 in flight, accumulators in AccVGPRs", 9, true);
-  run("k_trmm_f64 (shipped) again", 0, false);
-#ifdef TRMM_CLOCK_PROBE
-  if ((mask >> 14) & 1u) {      // timeline of the shipped LDS kernel: when do the 64 workgroups of a super-tile start and end?
-    unsigned long long* dlog; hipMalloc(&dlog, (size_t)grid * 16); hipMemset(dlog, 0, (size_t)grid * 16);
-    hipMemcpyToSymbol(HIP_SYMBOL(g_trmm_log), &dlog, sizeof(dlog));
-    hipLaunchKernelGGL(k_trmm_f64, dim3(grid), dim3(256), 4 * TR_CHUNK * sizeof(double), 0, L, D, X, nbi, nbj, nkb, ldx, GR, GC, (size_t)nbi * 128);
-    hipDeviceSynchronize();
-    std::vector<unsigned long long> hl((size_t)grid * 2); hipMemcpy(hl.data(), dlog, (size_t)grid * 16, hipMemcpyDeviceToHost);
-    unsigned long long* nul = nullptr; hipMemcpyToSymbol(HIP_SYMBOL(g_trmm_log), &nul, sizeof(nul));
-    unsigned long long base = ~0ull; for (unsigned i = 0; i < grid; ++i) if (hl[2 * i] && hl[2 * i] < base) base = hl[2 * i];
-    for (int gen = 0; gen < 3; ++gen) {       // XCD 0: super-tiles 0, 8, 16 (slots 64 gen .. 64 gen + 63)
-      printf("XCD 0, super-tile generation %d: start / end in us relative to the first workgroup of the launch, by position t = 8 r + c inside the super-tile\n", gen);
-      for (int t = 0; t < 64; ++t) {
-        const unsigned id = (unsigned)((gen * 64 + t) * 8);
-        printf("  t=%2d %9.1f %9.1f%s", t, (hl[2 * id] - base) * 0.01, (hl[2 * id + 1] - base) * 0.01, t % 4 == 3 ? "\n" : "");
-      }
-    }
-  }
-#endif
-  run("k_trmm_f64_reg (library, 6 in flight)", 12, true);
+  run("k_trmm_f64_big (shipped) again", 0, false);
   run("k_trmm_f64_big (library default: one workgroup / CU, 8 x 4 super-tiles)", 28, true);
   run("one workgroup / CU, wave tile 128 x 64 in AccVGPRs, 4 in flight, 4 x 8 super-tiles", 19, true);
   run("same, 5 in flight", 20, true);
@@ -484,8 +463,8 @@ int main(int argc, char** argv) {
   run("same, 4 in flight, 8 x 4, A loads non-temporal", 29, true);
   run("same, 4 in flight, 8 x 4, B loads non-temporal", 30, true);
   run("same, 4 in flight, 8 x 4, all loads non-temporal", 31, true);
-  run("k_trmm_f64_reg in two phases", 13, true);
-  run("k_trmm_f64_reg in two phases, meeting points in phase 1", 15, true);
+  run("registers, 6 in flight, in two phases", 13, true);
+  run("registers, 6 in flight, in two phases, meeting points in phase 1", 15, true);
 #ifdef TRMM_CLOCK_PROBE
   if ((mask >> 16) & 1u) {      // phase 1 with meeting points: did any workgroup give up, and how far apart do the workgroups of a super-tile start and end?
     unsigned long long* dlog; hipMalloc(&dlog, (size_t)grid * 16); hipMemset(dlog, 0, (size_t)grid * 16);

@@ -1,4 +1,5 @@
-"""A/B of the small-batch product at C3: one-wave tasks (k_trmm_stream, PSF_STREAM_WG=0) against 64 x 64 tiles with LDS-shared operands (k_trmm_stream_wg).
+"""A/B of the small-batch product at C3: one-wave tasks (k_trmm_stream, PSF_STREAM_WG=0) against 64 x 64 tiles with LDS-shared operands (k_trmm_stream_wg; beyond
+64 preimages forced with PSF_STREAM_WG192).
 Experiments build; one key, the switch is read per call.  For every batch size: the rows of the two forms compared bit for bit, the median call and the product's
 own HIP-event time.    python tools/stream_wg_ab.py [config=c3] [reps=15] [sizes ...]"""
 import json
@@ -32,9 +33,9 @@ def main():
         res = {}
         for form in ("wave", "wg"):
             if form == "wave":
-                os.environ["PSF_STREAM_WG"] = "0"; os.environ["PSF_STREAM_WG32"] = "0"
+                os.environ["PSF_STREAM_WG"] = "0"; os.environ["PSF_STREAM_WG32"] = "0"; os.environ["PSF_STREAM_WG192"] = "0"
             else:
-                os.environ.pop("PSF_STREAM_WG32", None); os.environ["PSF_STREAM_WG"] = "33"; os.environ["PSF_STREAM_WG_MAX"] = "1024"
+                os.environ.pop("PSF_STREAM_WG32", None); os.environ["PSF_STREAM_WG"] = "33"; os.environ["PSF_STREAM_WG192"] = "65:2048"
             e = torch.zeros((B, m), dtype=torch.int64, device=dev)
             call = lambda: psf.samp_p_dev(u.data_ptr(), e.data_ptr(), B, seed=9, first_index=1000, stream=stream)
             call(); call()
@@ -56,7 +57,7 @@ def main():
                "wave_product_ms": round(res["wave"][2], 4), "wg_product_ms": round(res["wg"][2], 4)}
         rows.append(row)
         print(json.dumps(row), flush=True)
-    os.environ.pop("PSF_STREAM_WG", None)
+    os.environ.pop("PSF_STREAM_WG", None); os.environ.pop("PSF_STREAM_WG192", None)
     assert all(r["same_bits"] for r in rows), "the two forms differ"
 
 

@@ -285,164 +285,14 @@ __device__ unsigned long long* g_trmm_log;      /* optional: per workgroup {star
 #define TR_CLK_BEGIN
 #define TR_CLK_END
 #endif
-#ifdef PSF_EXPERIMENTS   /* round 1's LDS-staged product: lost to k_trmm_f64_big (-5 %), comparison arm of the experiments build */
-__global__ __launch_bounds__(256, PSF_TR_BK == 16 ? 2 : 3) void k_trmm_f64(const double* __restrict__ Lt, const double* __restrict__ Dt,
-                                                     double* __restrict__ X, int nbi, int nbj, size_t nkb, size_t ldx, int GR, int GC, size_t row_hi) {
-  // LDS: 2 stages x (A chunk 2048 doubles | B chunk 2048 doubles); filled by LDS-DMA (global_load_lds_dwordx4), no
-  // staging registers: the accumulators (128 VGPRs) leave no room to hold a chunk in flight (hipcc serialised
-  // register-staged prefetch loads behind vmcnt(0) waits).
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  int bi, bj;
-  tr_map_block(blockIdx.x, nbi, nbj, GR, GC, &bi, &bj);
-  if (bi < 0 || bi >= nbi || bj >= nbj) return;
-  TR_CLK_BEGIN
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 1, wc = wave & 1;
-  const int nk = TR_KB_PER_BLOCK * (bi + 1);
-  const double* gA = Lt + tr_rowblock_base((size_t)bi) * TR_CHUNK + lane * 2;
-  const double* gB = Dt + (size_t)bj * nkb * TR_CHUNK + lane * 2;
 
-  d4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-
-  // each wave moves pieces 4*wave .. 4*wave+3 (1 KiB each) of both chunks: LDS address = wave-uniform base + lane*16
-  auto stage_load = [&](int kb, int buf) {
-#ifdef TRMM_FAKE_L2   /* timing experiment only: every load hits the same few chunks (results are garbage) */
-    const double* ga = Lt + lane * 2 + (size_t)(kb & 7) * TR_CHUNK;
-    const double* gb = Dt + lane * 2 + (size_t)(kb & 7) * TR_CHUNK;
-#else
-    const double* ga = gA + (size_t)kb * TR_CHUNK;
-    const double* gb = gB + (size_t)kb * TR_CHUNK;
-#endif
-    double* la = smem + buf * (2 * TR_CHUNK);
-#pragma unroll
-    for (int i = 0; i < TR_CHUNK / 512; ++i) {
-      const int piece = wave * (TR_CHUNK / 512) + i;
-      __builtin_amdgcn_global_load_lds(ga + piece * 128, (lds_void_ptr)(la + piece * 128), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(gb + piece * 128, (lds_void_ptr)(la + TR_CHUNK + piece * 128), 16, 0, 0);
-    }
-  };
-
-  stage_load(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kb = 0; kb < nk; ++kb) {
-    const int cur = kb & 1;
-    if (kb + 1 < nk) stage_load(kb + 1, cur ^ 1);
-    const double* sA = smem + cur * (2 * TR_CHUNK);
-    const double* sB = sA + TR_CHUNK;
-#pragma unroll
-    for (int ks = 0; ks < TR_BK / 4; ++ks) {
-      double a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        a[i] = sA[(ks * 8 + wr * 4 + i) * 64 + lane];
-        b[i] = sB[(ks * 8 + wc * 4 + i) * 64 + lane];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  // C/D map of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 * reg
-  const size_t row0 = (size_t)bi * TR_BM + wr * 64, col0 = (size_t)bj * TR_BN + wc * 64;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-      {
-        const size_t row = row0 + i * 16 + (lane >> 4) + 4 * r;      // rows from row_hi on are padding of the factor (structured mode: they belong to x_bot)
-        if (row < row_hi) X[row * ldx + col0 + j * 16 + (lane & 15)] = acc[i][j][r];
-      }
-  TR_CLK_END
-}
-#endif
-
-// Same product, operands streamed from global memory straight into MFMA operand registers: the chunk streams are already in fragment order, so
-// k-step s of a wave is eight 512-byte loads (4 A fragments, 4 B fragments) at stream offset 512 s.  No LDS, no barrier: the four waves of a
-// workgroup only share cache lines.  TR_PD k-steps are in flight per wave.  Bit-identical to k_trmm_f64 (same ascending chains); PSF_TRMM_VARIANT=1
-// (the default is k_trmm_f64_big below); measured on
-// MI355X at C3: 54.0 vs 55.0 ms inside the library, 0.967 of the FP64 MFMA peak AT THE CLOCK THE KERNEL RUNS AT (2.25-2.35 GHz under this load;
-// a loop with the same MFMAs and no loads at all reaches 0.963, profiles/r02_notes.md).
-constexpr int TR_PD = 6;
+// Operands streamed from global memory straight into MFMA operand registers: the chunk streams are already in fragment order, so k-step s of a
+// wave is 512-byte loads of its fragments at stream offset 512 s.  No LDS, no barrier: the waves of a workgroup only share cache lines.
+constexpr int TR_PD = 6;      // k-steps in flight of round 2's two-workgroups-per-CU form (tools/probe_trmm.hip)
 // hipcc hoists plain loads of an unrolled prefetch ring to the top of the loop body and drains them with vmcnt(0) at its end, so the loads and
 // their waits are written out: loads return in order, hence "all but the newest 8 (TR_PD - 1) have landed".
 #define TR_LOAD8(dst, voff, base, imm) asm volatile("global_load_dwordx2 %0, %1, %2 offset:" #imm : "=v"(dst) : "v"(voff), "s"(base) : "memory")
 #define TR_WAIT(n, A, Bv) asm volatile("s_waitcnt vmcnt(" #n ")" : "+v"(A[0]), "+v"(A[1]), "+v"(A[2]), "+v"(A[3]), "+v"(Bv[0]), "+v"(Bv[1]), "+v"(Bv[2]), "+v"(Bv[3]))
-#ifdef PSF_EXPERIMENTS   /* round 2's register-streamed product: lost to k_trmm_f64_big, comparison arm of the experiments build */
-__global__ __launch_bounds__(256, 2) void k_trmm_f64_reg(const double* __restrict__ Lt, const double* __restrict__ Dt,
-                                                         double* __restrict__ X, int nbi, int nbj, size_t nkb, size_t ldx, int GR, int GC, size_t row_hi) {
-  int bi, bj;
-  tr_map_block(blockIdx.x, nbi, nbj, GR, GC, &bi, &bj);
-  if (bi < 0 || bi >= nbi || bj >= nbj) return;
-  TR_CLK_BEGIN
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 1, wc = wave & 1;
-  const int nsteps = TR_KB_PER_BLOCK * (bi + 1) * (TR_BK / 4);
-  const double* gA = Lt + tr_rowblock_base((size_t)bi) * TR_CHUNK + (size_t)(wr * 4) * 64;      // wave-uniform
-  const double* gB = Dt + (size_t)bj * nkb * TR_CHUNK + (size_t)(wc * 4) * 64;
-  const uint32_t voff = (uint32_t)lane * 8u;
-
-  d4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-  double a[TR_PD][4], b[TR_PD][4];
-  auto issue = [&](double (&av)[4], double (&bv)[4], int s) {
-    const double* pa = gA + (size_t)s * 512;
-    const double* pb = gB + (size_t)s * 512;
-    TR_LOAD8(av[0], voff, pa, 0); TR_LOAD8(bv[0], voff, pb, 0);
-    TR_LOAD8(av[1], voff, pa, 512); TR_LOAD8(bv[1], voff, pb, 512);
-    TR_LOAD8(av[2], voff, pa, 1024); TR_LOAD8(bv[2], voff, pb, 1024);
-    TR_LOAD8(av[3], voff, pa, 1536); TR_LOAD8(bv[3], voff, pb, 1536);
-  };
-#pragma unroll
-  for (int u = 0; u < TR_PD; ++u) issue(a[u], b[u], u);                    // at least 32 steps per row-block
-  for (int s0 = 0; s0 < nsteps; s0 += TR_PD) {
-#pragma unroll
-    for (int u = 0; u < TR_PD; ++u) {
-      if (s0 + u < nsteps) {                                           // the number of k-steps is a multiple of 32, not of TR_PD
-        TR_WAIT(40, a[u], b[u]);                                       // 8 (TR_PD - 1)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u][i], b[u][j], acc[i][j], 0, 0, 0);
-      }
-      int sn = s0 + u + TR_PD;
-      sn = sn < nsteps ? sn : nsteps - 1;                              // past the end: re-read the last step (never consumed)
-      issue(a[u], b[u], sn);
-    }
-  }
-  // the re-reads behind the last step are never consumed: their destination registers must stay allocated until they have landed (a load that
-  // lands in a register the compiler has reused since corrupts it -- seen as a memory fault through a clobbered store address)
-#pragma unroll
-  for (int u = 0; u < TR_PD; ++u) TR_WAIT(0, a[u], b[u]);
-  const size_t row0 = (size_t)bi * TR_BM + wr * 64, col0 = (size_t)bj * TR_BN + wc * 64;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-      {
-        const size_t row = row0 + i * 16 + (lane >> 4) + 4 * r;
-        if (row < row_hi) X[row * ldx + col0 + j * 16 + (lane & 15)] = acc[i][j][r];
-      }
-  TR_CLK_END
-}
-#endif
 
 // The default since the end of round 2: ONE workgroup per CU, four waves, each alone on its SIMD with a 128 x 64 tile of X -- 256 AccVGPRs of
 // accumulators (the MFMAs are asm statements: hipcc keeps builtin accumulators in architectural VGPRs) and the operand ring in the 256
@@ -450,8 +300,8 @@ __global__ __launch_bounds__(256, 2) void k_trmm_f64_reg(const double* __restric
 // 2 bt + wr and the 4 B fragments of its half of the column block: 12 loads for 32 MFMAs per k-step, a quarter fewer operand bytes per flop than
 // two 128 x 128 workgroups per CU, TR_BIG_PD k-steps in flight.  No co-resident workgroup: nothing competes for the matrix cores, so the 32
 // workgroups of an XCD (a super-tile of 8 row tiles x 4 column blocks) run at one pace and share their fetches in L2.  Same ascending chains,
-// same bits.  Measured at C3 (tools/probe_trmm.hip, profiles/r02_notes.md): 52.2 ms against 53.1-54.3 (k_trmm_f64_reg) and 54.9 (k_trmm_f64) in the
-// same runs, 0.946 of the FP64 peak at 2.4 GHz, FETCH_SIZE 63 GB against 138 / 121.
+// same bits.  Measured at C3 (tools/probe_trmm.hip, profiles/r02_notes.md): 52.2 ms against 53.1-54.3 (two register-streamed 128 x 128 workgroups per CU)
+// and 54.9 (LDS-staged, round 1) in the same runs, 0.946 of the FP64 peak at 2.4 GHz, FETCH_SIZE 63 GB against 138 / 121.
 constexpr int TR_BIG_PD = 4;
 #ifndef TR_BIG_UNROLL
 #define TR_BIG_UNROLL 2      /* rounds of the operand ring per loop iteration (must divide 8); measured 1 -> 2: +0.4 %, 4: no more */
@@ -522,7 +372,8 @@ __global__ __launch_bounds__(256, 1) void k_trmm_f64_big(const double* __restric
       }
     }
 #undef TR_MFMA
-    // the unconsumed re-reads keep their registers until they have landed (see k_trmm_f64_reg)
+    // the unconsumed re-reads keep their registers until they have landed (a load that lands in a register the compiler has reused since corrupts it --
+    // seen as a memory fault through a clobbered store address)
 #pragma unroll
     for (int u = 0; u < TR_BIG_PD; ++u) TR_WAIT12(0, a[u], b[u]);
     // The hazard recogniser does not see MFMAs inside asm statements: nothing may read an accumulator until the last MFMA has retired (16 passes = 64
@@ -1018,7 +869,7 @@ __global__ void k_split_A(const uint64_t* __restrict__ A, size_t lda, size_t n, 
 }
 
 // P (K x ld int32) -> three digit planes [K_pad/16][ld][16]; thread = (16-coordinate group, preimage).  Only the columns [col0, col0 + cw) are
-// converted (the two halves of a batch run their stages on two streams: a half must not touch the other half's columns).
+// converted.
 __global__ void k_split_P(const int32_t* __restrict__ P, size_t K, size_t ld, size_t ngroups, int8_t* __restrict__ P8, int* __restrict__ fail, size_t col0, size_t cw) {
   const size_t total = ngroups * cw;
   const size_t plane = ngroups * ld * 16;

@@ -784,7 +784,7 @@ psf_status psfgpv_samp_p(psfgpv_handle* g, uint64_t seed, uint64_t first_index, 
     if (B * g->n > h->sio_du_cap) { hipFree(h->sio_du); h->sio_du = nullptr; h->sio_du_cap = 0; HIP_TRY(hipMalloc(&h->sio_du, B * g->n * sizeof(uint64_t))); h->sio_du_cap = B * g->n; }
     if (B * g->m > h->sio_de_cap) { hipFree(h->sio_de); h->sio_de = nullptr; h->sio_de_cap = 0; HIP_TRY(hipMalloc(&h->sio_de, B * g->m * sizeof(int64_t))); h->sio_de_cap = B * g->m; }
     int fl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    psf_status rc = sio_call(h, B * g->n, B * g->m, u, e, h->sio_du, h->sio_de, h->sets[0].dFail, h->sets[1].dFail, g->ln[0].dFlags, 8, fl,
+    psf_status rc = sio_call(h, B * g->n, B * g->m, u, e, h->sio_du, h->sio_de, h->dFail, g->ln[0].dFlags, 8, fl,
                              [&]() { return psfgpv_samp_p_dev(g, seed, first_index, B, h->sio_du, h->sio_de, nullptr); });
     if (rc != PSF_OK) return rc;
     if (fl[0]) return PSF_ERR_SAMPLER;
@@ -825,7 +825,7 @@ psf_status psfgpv_samp_p(psfgpv_handle* g, uint64_t seed, uint64_t first_index, 
   hipLaunchKernelGGL(k_narrow_rows, dim3(grid_for(ne / 2 + 1, 256, 256 * 16)), dim3(256), 0, nullptr, h->sio_de, h->sio_d32, ne, d_ovf);
   // flags first (with the overflow word of the narrowing), then the rows in NT pieces, an event behind each: thread i widens piece i as soon as it has landed,
   // while the later pieces are still crossing PCIe
-  hipLaunchKernelGGL(k_sio_flags, dim3(1), dim3(64), 0, nullptr, h->sets[0].dFail, h->sets[1].dFail, g->ln[0].dFlags, 8, hf);
+  hipLaunchKernelGGL(k_sio_flags, dim3(1), dim3(64), 0, nullptr, h->dFail, g->ln[0].dFlags, 8, hf);
   HIP_TRY(hipMemcpyAsync(hf + 12, d_ovf, sizeof(int), hipMemcpyDeviceToHost, nullptr));
   constexpr int NT = 4;
   if (!h->sio_ev[0]) for (auto& ev : h->sio_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));

@@ -105,13 +105,9 @@ struct psfp_handle {
   int8_t* dZlo = nullptr; int8_t* dZhi = nullptr; size_t mb_pad = 0;
   int8_t* dP8 = nullptr;                      // three digit planes of P, [K_pad/16][ld][16] each
   uint64_t* dU = nullptr; int64_t* dE = nullptr; uint8_t* dOk = nullptr;
-  int* dFail = nullptr;
-  // Two sets of the per-batch intermediates: consecutive samp_p calls alternate between them so that the sampling
-  // stages of call i (stream aux) overlap the normals + FP64 product of call i+1 (stream s1).
-  struct BatchSet { double* dDt = nullptr; double* dX = nullptr; int32_t* dP = nullptr; int8_t* dP8 = nullptr; uint64_t* dV = nullptr;
-                    int8_t* dZlo = nullptr; int8_t* dZhi = nullptr; int* dFail = nullptr; int8_t* dD8 = nullptr; } sets[2];
+  int* dFail = nullptr;                       // four words: [0] sampler failure, [1] some |z| > 127, [2] some |p| >= 2^15 (run_samp_p)
   int8_t* dD8 = nullptr;                      // five digit planes of d_2 2^32 (structured mode), [ldr/16][ld][16] each
-  int32_t* dPf = nullptr; int8_t* dP8f = nullptr;   // scratch of f_a (kept apart from the pipelined sets)
+  int32_t* dPf = nullptr; int8_t* dP8f = nullptr;   // scratch of f_a (kept apart from the samp_p intermediates)
   uint64_t* dPart = nullptr; int zq_split_cap = 1;   // per-split residues of the int8-MFMA Z_q product
   bool gadget_queue = true;   // task-queue gadget sampler (PSF_GADGET_QUEUE=0: lock-step kernel)
   bool keep_fail = false;     // sliced host path: the failure flags accumulate over the slices of one call
@@ -144,8 +140,7 @@ struct psfp_handle {
     uint64_t slot_seq[2] = {0, 0};              // ticket of the call in each slot
     struct Done { uint64_t seq; int status; bool used; } done[8] = {};      // the last joined calls and their statuses (psfp_wait_ticket)
     bool slice_tail = false;                    // set by psfp_samp_p around its own asynchronous call: cut a short last slice (single-call latency)
-    int copy_mode = 1;                          // how a chunk crosses PCIe: 1 = SDMA engine through the HSA runtime (psf_sdma.hpp), 0 = hipMemcpyAsync, 2 = a copy kernel (PSF_HOST_COPY)
-    int copy_grid = 32;                         // workgroups of the copy kernel (mode 2)
+    int copy_mode = 1;                          // how a chunk crosses PCIe: 1 = SDMA engine through the HSA runtime (psf_sdma.hpp), 0 = hipMemcpyAsync (PSF_HOST_COPY)
     psf::SdmaCopy sdma;
     hsa_signal_t sigC[2][NW][2] = {};           // mode 1: chunk landed in its pinned buffer
     hsa_signal_t sigU = {};                     // mode 1: the call's targets have reached the device
@@ -160,13 +155,9 @@ struct psfp_handle {
   int32_t* sio_d32 = nullptr; size_t sio_d32_cap = 0;         // narrowed rows of a PSFGPV / ring batch on their way to the host
   hipEvent_t sio_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // pieces 0..3 of such a batch have landed; [4]: its flags have
   bool no_slice = false;      // stage export wants the intermediates of the whole batch
-  bool pipeline = false;   // PSF_PIPELINE=1 enables it; measured zero-sum on MI355X (profiles/r01_notes.md)
-  size_t ncall = 0;
   uint32_t normals_ncf = 0;   // layout of dDt after the last samp_p: 0 = chunk stream, else the compact stream with this many column fragments
-  hipStream_t s1 = nullptr;
-  hipEvent_t evT[2] = {nullptr, nullptr}, evP[2] = {nullptr, nullptr}, evIn = nullptr;
   hipStream_t last_stream = nullptr;
-  hipStream_t aux = nullptr;                 // low-priority stream of the sampling stages in pipelined mode
+  hipStream_t side = nullptr; hipEvent_t evSide = nullptr;      // psfp_trap_gen: A is computed on this low-priority stream beside the factorisation of Sigma_2
   // timing
   bool timing = false;
   std::vector<TimingSlot> slots;
@@ -207,7 +198,7 @@ static bool rcb_packed() {
 }
 // the tile-packed copy of R, rebuilt on `st` when R has changed since
 // (as the compact copies above: the stream that packs is ordered behind the pack by itself; every OTHER stream that reads dR8 before the pack is known to have
-// completed waits for its event -- the halves of PSF_HALVES on s1 / aux, back-to-back device-pointer calls on different non-blocking streams)
+// completed waits for its event -- back-to-back device-pointer calls on different non-blocking streams)
 static void ensure_R8(psfp_handle* h, hipStream_t st) {
   if (!h->dR8) return;
   if (!h->r8_valid) {
@@ -226,19 +217,11 @@ static void ensure_R8(psfp_handle* h, hipStream_t st) {
 
 static size_t gadget_lds_bytes(size_t k) { return k * k * 8 + k * 8 + k * sizeof(SampleZParams) + k * k * 4 + k * 256 * 4; }
 
-static void select_set(psfp_handle* h, int i) {
-  const auto& t = h->sets[i];
-  h->dDt = t.dDt; h->dX = t.dX; h->dP = t.dP; h->dP8 = t.dP8; h->dV = t.dV; h->dZlo = t.dZlo; h->dZhi = t.dZhi; h->dFail = t.dFail; h->dD8 = t.dD8;
-}
-
 static void free_batch(psfp_handle* h) {
-  for (auto& t : h->sets) {
-    hipFree(t.dDt); hipFree(t.dX); hipFree(t.dP); hipFree(t.dP8); hipFree(t.dV); hipFree(t.dZlo); hipFree(t.dZhi); hipFree(t.dD8);
-    t.dDt = t.dX = nullptr; t.dP = nullptr; t.dP8 = nullptr; t.dV = nullptr; t.dZlo = t.dZhi = nullptr; t.dD8 = nullptr;
-  }
+  hipFree(h->dDt); hipFree(h->dX); hipFree(h->dP); hipFree(h->dP8); hipFree(h->dV); hipFree(h->dZlo); hipFree(h->dZhi); hipFree(h->dD8);
+  h->dDt = h->dX = nullptr; h->dP = nullptr; h->dP8 = nullptr; h->dV = nullptr; h->dZlo = h->dZhi = nullptr; h->dD8 = nullptr;
   hipFree(h->dPf); hipFree(h->dP8f); hipFree(h->dPart); hipFree(h->dU); hipFree(h->dE); hipFree(h->dOk);
   h->dPf = nullptr; h->dP8f = nullptr; h->dPart = nullptr; h->dU = nullptr; h->dE = nullptr; h->dOk = nullptr;
-  select_set(h, 0);
   h->Bcap = 0;
 }
 
@@ -264,25 +247,20 @@ static psf_status ensure_batch(psfp_handle* h, size_t B) {
   const size_t ld = round_up(B, TR_BN);
   h->ld = ld;
   h->nbj = ld / TR_BN;
-  const bool perturb = !(h->prm.flags & PSFP_FLAG_NO_PERTURB);
-  const int nsets = (perturb && h->pipeline) ? 2 : 1;
-  for (int i = 0; i < nsets; ++i) {
-    auto& t = h->sets[i];
-    if (perturb) {
-      HIP_TRY(hipMalloc(&t.dDt, (ld / TR_BN * h->nkb * TR_CHUNK + TS_SLACK_DOUBLES) * sizeof(double)));   // slack: k_trmm_stream reads past the diagonal
-      HIP_TRY(hipMalloc(&t.dX, h->M_pad * ld * sizeof(double)));
-      HIP_TRY(hipMalloc(&t.dP, h->M_pad * ld * sizeof(int32_t)));
-      HIP_TRY(hipMalloc(&t.dP8, 3 * h->K_pad * ld));
-      HIP_TRY(hipMalloc(&t.dV, h->n * ld * sizeof(uint64_t)));
-      HIP_TRY(hipMalloc(&t.dZlo, h->ldr * ld + RS_SLACK_SLOTS * 128 * ld));      // [ldr/16][ld][16] (+ the slots k_recombine_wg's ring reads past the last K group)
-      HIP_TRY(hipMalloc(&t.dZhi, h->ldr * ld + RS_SLACK_SLOTS * 128 * ld));
-      HIP_TRY(hipMemset(t.dZlo, 0, h->ldr * ld));
-      HIP_TRY(hipMemset(t.dZhi, 0, h->ldr * ld));
-      HIP_TRY(hipMemset(t.dP, 0, h->M_pad * ld * sizeof(int32_t)));
-      if (h->structured) {
-        HIP_TRY(hipMalloc(&t.dD8, kFixPlanes * h->ldr * ld));
-        HIP_TRY(hipMemset(t.dD8, 0, kFixPlanes * h->ldr * ld));
-      }
+  if (!(h->prm.flags & PSFP_FLAG_NO_PERTURB)) {
+    HIP_TRY(hipMalloc(&h->dDt, (ld / TR_BN * h->nkb * TR_CHUNK + TS_SLACK_DOUBLES) * sizeof(double)));   // slack: k_trmm_stream reads past the diagonal
+    HIP_TRY(hipMalloc(&h->dX, h->M_pad * ld * sizeof(double)));
+    HIP_TRY(hipMalloc(&h->dP, h->M_pad * ld * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(&h->dP8, 3 * h->K_pad * ld));
+    HIP_TRY(hipMalloc(&h->dV, h->n * ld * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc(&h->dZlo, h->ldr * ld + RS_SLACK_SLOTS * 128 * ld));      // [ldr/16][ld][16] (+ the slots k_recombine_wg's ring reads past the last K group)
+    HIP_TRY(hipMalloc(&h->dZhi, h->ldr * ld + RS_SLACK_SLOTS * 128 * ld));
+    HIP_TRY(hipMemset(h->dZlo, 0, h->ldr * ld));
+    HIP_TRY(hipMemset(h->dZhi, 0, h->ldr * ld));
+    HIP_TRY(hipMemset(h->dP, 0, h->M_pad * ld * sizeof(int32_t)));
+    if (h->structured) {
+      HIP_TRY(hipMalloc(&h->dD8, kFixPlanes * h->ldr * ld));
+      HIP_TRY(hipMemset(h->dD8, 0, kFixPlanes * h->ldr * ld));
     }
   }
   HIP_TRY(hipMalloc(&h->dPf, h->M_pad * ld * sizeof(int32_t)));
@@ -304,7 +282,6 @@ static psf_status ensure_batch(psfp_handle* h, size_t B) {
   // not wait for it -- without this barrier a clear could land AFTER the first kernels had written the same buffer (found in round 5 by tools/host_vs_device_fuzz.py: one
   // whole-batch mismatch in 240 000 first calls, small keys whose product finishes within the clear of dP)
   HIP_TRY(hipDeviceSynchronize());
-  select_set(h, 0);
   h->Bcap = B;
   return PSF_OK;
 }
@@ -513,23 +490,14 @@ static psf_status psfp_init(psfp_handle* h, const psfp_params* prm) {
   HIP_TRY(hipMemset(h->dR, 0, h->mb_pad * h->ldr));
   if (!(prm->flags & PSFP_FLAG_NO_PERTURB)) HIP_TRY(hipMalloc(&h->dLt, (tr_total_chunks(h->nbiL) * TR_CHUNK + TS_SLACK_DOUBLES) * sizeof(double)));
   if (!(prm->flags & PSFP_FLAG_NO_PERTURB)) HIP_TRY(hipMalloc(&h->dR8, h->mb_pad * h->ldr));      // tile-packed copy of R: k_recombine_mfma_big, k_rd2_mfma
-  for (auto& t : h->sets) {                             // [0] sampler failure, [1] some |z| > 127
-    HIP_TRY(hipMalloc(&t.dFail, 4 * sizeof(int)));
-    HIP_TRY(hipMemset(t.dFail, 0, 4 * sizeof(int)));
-  }
-  h->dFail = h->sets[0].dFail;
-  {  // the FP64 product gets the high-priority queue, the sampling stages the low one
+  HIP_TRY(hipMalloc(&h->dFail, 4 * sizeof(int)));
+  HIP_TRY(hipMemset(h->dFail, 0, 4 * sizeof(int)));
+  {
     int lo_prio = 0, hi_prio = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
-    HIP_TRY(hipStreamCreateWithPriority(&h->s1, hipStreamNonBlocking, hi_prio));
-    HIP_TRY(hipStreamCreateWithPriority(&h->aux, hipStreamNonBlocking, lo_prio));
+    HIP_TRY(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, lo_prio));
   }
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(hipEventCreateWithFlags(&h->evT[i], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&h->evP[i], hipEventDisableTiming));
-  }
-  HIP_TRY(hipEventCreateWithFlags(&h->evIn, hipEventDisableTiming));
-  if (const char* env = psf_exp_env("PSF_PIPELINE")) h->pipeline = std::atoi(env) != 0;
+  HIP_TRY(hipEventCreateWithFlags(&h->evSide, hipEventDisableTiming));
   // gadget part of the trapdoor: (S, S~) of mp_perturbation.rs:233-234, block form
   h->hSk = short_basis_gadget_block(gp);
   std::vector<double> norm2;
@@ -560,11 +528,6 @@ static psf_status psfp_init(psfp_handle* h, const psfp_params* prm) {
   HIP_TRY(hipMemcpy(h->dNorm2, norm2.data(), h->k * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->dSz, sz.data(), h->k * sizeof(SampleZParams), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->dGvec, gvec.data(), h->k * sizeof(uint64_t), hipMemcpyHostToDevice));
-#ifdef PSF_EXPERIMENTS
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_diag), hipFuncAttributeMaxDynamicSharedMemorySize, CH_NB * (CH_NB + 1) * 8));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_trsm), hipFuncAttributeMaxDynamicSharedMemorySize, (CH_NB * (CH_NB + 1) / 2 + CH_NB * 64) * 8));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_trmm_f64), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TR_CHUNK * sizeof(double)));
-#endif
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_recombine_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_recombine_mfma_big), hipFuncAttributeMaxDynamicSharedMemorySize, RCB_LDS));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_recombine_small<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -581,10 +544,6 @@ static psf_status psfp_init(psfp_handle* h, const psfp_params* prm) {
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_recombine_wg<4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RW_LDS));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_trmm_stream_wg32<TSW_H, TSW_NBUF, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TSW32_LDS));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_trmm_stream_wg32<TSW_H, TSW_NBUF, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TSW32_LDS));
-#ifdef PSF_EXPERIMENTS
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_trmm_stream_wg<2, TSW_NBUF, 0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TSW128_LDS));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_trmm_stream_wg<2, TSW_NBUF, 1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TSW128_LDS));
-#endif
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TSW_LDS));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TSW_LDS));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gadget_queue<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gadget_queue_lds_bytes(h->k)));
@@ -616,15 +575,13 @@ void psfp_destroy(psfp_handle* h) {
   for (auto& ev : h->sio_ev) if (ev) hipEventDestroy(ev);
   free_batch(h);
   clear_slots(h);
-  if (h->aux) hipStreamDestroy(h->aux);
+  if (h->side) hipStreamDestroy(h->side);
+  if (h->evSide) hipEventDestroy(h->evSide);
   hipFree(h->dA); hipFree(h->dR); hipFree(h->dLt); hipFree(h->dR8); hipFree(h->dR2); hipFree(h->dA32); hipFree(h->dR2bad); hipFree(h->dA32T); hipFree(h->dPartF);
   if (h->hR2bad) hipHostFree(h->hR2bad);
   if (h->evSmall) hipEventDestroy(h->evSmall);
   if (h->evR8) hipEventDestroy(h->evR8);
-  for (auto& t : h->sets) hipFree(t.dFail);
-  if (h->s1) hipStreamDestroy(h->s1);
-  for (int i = 0; i < 2; ++i) { if (h->evT[i]) hipEventDestroy(h->evT[i]); if (h->evP[i]) hipEventDestroy(h->evP[i]); }
-  if (h->evIn) hipEventDestroy(h->evIn);
+  hipFree(h->dFail);
   hipFree(h->dA8); hipFree(h->dSzTab);
   hipFree(h->dRng);
   hipFree(h->dSk); hipFree(h->dGso); hipFree(h->dNorm2); hipFree(h->dSz); hipFree(h->dGvec);
@@ -638,23 +595,12 @@ size_t psfp_m(const psfp_handle* h) { return h ? h->m : 0; }
 // beta = alpha - kappa) as B B^t with B = [[L_1 / sqrt c, -kappa R / sqrt beta], [0, sqrt beta I]] sqrt c, where L_1 is the Cholesky factor of
 // c (alpha I - kappa (alpha / beta) R R^t): only that m_bar x m_bar block is assembled, factored and stored.
 // Cholesky of Sigma_2 directly on the key's chunk stream (psf_chol_kernels.hpp, "Cholesky directly on the key's chunk stream"): no dense m x m matrix.
-// factor + invert one 128 x 128 diagonal block: the blocked kernel (round 6); PSF_CHOL_DIAG=steps (experiments build): the step-by-step kernel of rounds 3-5
+// factor + invert one 128 x 128 diagonal block (k_chol_diag_inv)
 static void launch_chol_diag(hipStream_t st, double* P, size_t ld, size_t off, int nb, double* dLi, int* dinfo, size_t report_base) {
-#ifdef PSF_EXPERIMENTS
-  static const bool steps = [] { const char* e = psf_exp_env("PSF_CHOL_DIAG"); return e && !std::strcmp(e, "steps"); }();
-  if (steps) {
-    hipLaunchKernelGGL(k_chol_diag_inv_steps, dim3(1), dim3(256), ((size_t)CH_NB * (CH_NB + 1) + 2 * CH_NB) * sizeof(double), st, P, ld, off, nb, dLi, dinfo, report_base);
-    return;
-  }
-#endif
   hipLaunchKernelGGL(k_chol_diag_inv, dim3(1), dim3(256), CH_DIAG_LDS, st, P, ld, off, nb, dLi, dinfo, report_base);
 }
 static bool prepare_chol_diag() {
-  bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_diag_inv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_DIAG_LDS) == hipSuccess;
-#ifdef PSF_EXPERIMENTS
-  ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_diag_inv_steps), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)CH_NB * (CH_NB + 1) + 2 * CH_NB) * sizeof(double))) == hipSuccess;
-#endif
-  return ok;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_diag_inv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_DIAG_LDS) == hipSuccess;
 }
 
 // dS_dense: nullptr, or Sigma_2 already assembled as a dense m x m matrix (lower triangle; the hybrid of build_sqrt_sigma2): the panels are then copied out of it
@@ -811,17 +757,14 @@ static psf_status build_sqrt_sigma2(psfp_handle* h, double s_cov, const double* 
     h->h_const = std::sqrt(nf_r2 * beta);
     ensure_R8(h, nullptr);
   }
-  {
-    // "stream": left-looking on the key's chunk stream, no dense matrix (C5: 10.1 s against 21.1 s, and 121 GB less memory; C3: 0.28 s either way); "gemm": left-looking on a
-    // dense m x m matrix with the LDS-staged GEMM; "right": the right-looking kernels of rounds 1-2.  Default by size: the
-    // dense form while the matrix stays below 16 GB (m < 46 341), the stream form above.  (The dense form factors the diagonal blocks beside the updates on a
-    // second stream; beside k_chol_update_big that overlap returns nothing -- FP64 MFMAs and the vector work of the triangular kernel share
-    // one pipe, profiles/r03_notes.md -- so the stream form runs them in line: 0.3 s of C5's total.)
-    const char* ce = psf_exp_env("PSF_CHOL");
-    const bool stream = ce ? !std::strcmp(ce, "stream") : m * m * sizeof(double) > (16ull << 30);
-    if (stream) return build_sqrt_sigma2_stream(h, nf_r2, s2, b2p1, d_sigma_packed);
-  }
-  struct DenseGuard { double* dS = nullptr; int* dinfo = nullptr; ~DenseGuard() { hipFree(dinfo); hipFree(dS); } } dg;      // every exit releases both
+  // Cholesky on the key's chunk stream (build_sqrt_sigma2_stream).  Above 16 GB (m >= 46 341) Sigma_2 is assembled there panel by panel, no dense matrix (C5: 10.1 s
+  // against 21.1 s for a dense left-looking form, and 121 GB less memory); below, the hybrid (round 6): Sigma_2 dense AT ONCE, the factorisation on the chunk stream
+  // (k_chol_update_big: 64 TFLOP/s against the 44 of the LDS-staged GEMM of the dense form), panels copied out of the dense matrix.  PSF_CHOL=stream (experiments
+  // build): the stream form at every size.
+  const char* ce = psf_exp_env("PSF_CHOL");
+  const bool stream = ce ? !std::strcmp(ce, "stream") : m * m * sizeof(double) > (16ull << 30);
+  if (stream) return build_sqrt_sigma2_stream(h, nf_r2, s2, b2p1, d_sigma_packed);
+  struct DenseGuard { double* dS = nullptr; ~DenseGuard() { hipFree(dS); } } dg;      // every exit releases it
   double*& dS = dg.dS;
   HIP_TRY(hipMalloc(&dS, m * m * sizeof(double)));
   HIP_TRY(hipMemset(dS, 0, m * m * sizeof(double)));
@@ -830,81 +773,7 @@ static psf_status build_sqrt_sigma2(psfp_handle* h, double s_cov, const double* 
   hipLaunchKernelGGL(k_sigma2_rrt, dim3(tiles, tiles), dim3(256), 3 * 2 * 4096, 0, h->dR, h->ldr, h->mb, m, nf_r2, s2, b2p1, d_sigma_packed, dS, m, (size_t)0, (size_t)0);
   hipLaunchKernelGGL(k_sigma2, dim3(tiles, tiles), dim3(256), 0, 0, h->dR, h->ldr, h->mb, h->w, m, nf_r2, s2, b2p1, d_sigma_packed, dS, m, (size_t)0, (size_t)0, 1);
   HIP_TRY(hipGetLastError());
-  {
-    // The hybrid (round 6, the default below 16 GB): Sigma_2 dense AT ONCE (above), the factorisation on the key's chunk stream (k_chol_update_big: 64 TFLOP/s against
-    // the 44 of the LDS-staged GEMM of the dense left-looking form), panels copied out of the dense matrix.  PSF_CHOL=gemm (experiments build): the dense form.
-    const char* ce2 = psf_exp_env("PSF_CHOL");
-    if (!(ce2 && (!std::strcmp(ce2, "gemm") || !std::strcmp(ce2, "right")))) return build_sqrt_sigma2_stream(h, nf_r2, s2, b2p1, d_sigma_packed, dS);
-  }
-  // blocked Cholesky of the lower triangle, panel width 128 (psf_chol_kernels.hpp): left-looking on the FP64 GEMM; PSF_CHOL=right: the right-looking
-  // kernels of rounds 1-2 (comparison arm)
-  int*& dinfo = dg.dinfo;
-  HIP_TRY(hipMalloc(&dinfo, sizeof(int)));
-  HIP_TRY(hipMemset(dinfo, 0, sizeof(int)));
-#ifdef PSF_EXPERIMENTS
-  const char* chol_env = psf_exp_env("PSF_CHOL");
-  if (chol_env && !std::strcmp(chol_env, "right")) {
-    for (size_t off = 0; off < m; off += CH_NB) {
-      const int nb = (int)(m - off < (size_t)CH_NB ? m - off : (size_t)CH_NB);
-      hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(256), (size_t)nb * (CH_NB + 1) * sizeof(double), 0, dS, m, off, nb, dinfo);
-      const size_t rest = m - off - nb;
-      if (rest == 0) break;
-      const size_t trsm_lds = ((size_t)nb * (nb + 1) / 2 + (size_t)nb * 64) * sizeof(double);
-      hipLaunchKernelGGL(k_chol_trsm, dim3((unsigned)((rest + 63) / 64)), dim3(64), trsm_lds, 0, dS, m, off, nb, m, dinfo);
-      const size_t nt = (rest + 127) / 128;
-      hipLaunchKernelGGL(k_chol_syrk, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 2 * 4096 * sizeof(double), 0, dS, m, off, m, (int)nt, dinfo);
-    }
-  } else
-#endif
-  {
-    if (gemm_prepare() != hipSuccess) return PSF_ERR_HIP;
-    GemmWorkspace w;
-    w.bytes = (size_t)900 * GM_T * GM_T * sizeof(double);              // < 384 + 512 (tile, split) pairs per launch, see launch_gemm
-    double* dLi = nullptr;
-    hipStream_t sm = nullptr, sd = nullptr;                            // products / diagonal blocks
-    hipEvent_t evTile = nullptr, evDiag = nullptr;
-    auto cleanup = [&]() { if (sm) hipStreamDestroy(sm); if (sd) hipStreamDestroy(sd); if (evTile) hipEventDestroy(evTile); if (evDiag) hipEventDestroy(evDiag); hipFree(w.ws); hipFree(dLi); };
-    if (hipMalloc(&w.ws, w.bytes) != hipSuccess || hipMalloc(&dLi, CH_NB * CH_NB * sizeof(double)) != hipSuccess ||
-        hipStreamCreateWithFlags(&sm, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&sd, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&evTile, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&evDiag, hipEventDisableTiming) != hipSuccess ||
-        !prepare_chol_diag() ||
-        hipDeviceSynchronize() != hipSuccess) {                        // (k_sigma2 ran on the default stream)
-      cleanup(); return PSF_ERR_HIP;
-    }
-    // Look-ahead: the factorisation of a diagonal block is one workgroup walking 128 dependent steps (~0.2-0.35 ms, pure latency).  The update of
-    // panel j is therefore cut in two: its first row tile (the diagonal block) goes first, its factorisation + inversion then runs on a second
-    // stream BESIDE the update of the rows below, and the triangular solve of those rows (a product with the inverse) joins the two.
-    for (size_t off = 0; off < m; off += CH_NB) {
-      const size_t nb = m - off < (size_t)CH_NB ? m - off : (size_t)CH_NB;
-      const size_t rest = m - off - nb;
-      double* P = dS + off * m + off;                                  // the panel: rows off.., columns off..off+nb
-      double* P2 = P + nb * m;                                         // its rows below the diagonal block
-      if (off > 0) {                                                   // P -= L[off.., 0..off) L[off..off+nb, 0..off)^t
-        launch_gemm<true>(sm, GemmArgs{dS + off * m, m, dS + off * m, m, P, m, nb, nb, off, -1.0, 1.0, nullptr, nullptr, 0}, w);
-        hipEventRecord(evTile, sm);
-        if (rest) launch_gemm<true>(sm, GemmArgs{dS + (off + nb) * m, m, dS + off * m, m, P2, m, rest, nb, off, -1.0, 1.0, nullptr, nullptr, 0}, w);
-        hipStreamWaitEvent(sd, evTile, 0);
-      }
-      launch_chol_diag(sd, dS, m, off, (int)nb, dLi, dinfo, off);
-      hipEventRecord(evDiag, sd);
-      hipStreamWaitEvent(sm, evDiag, 0);
-      if (rest == 0) break;
-      // rows below = panel L11^-t; in place: one column tile, a workgroup reads only its own rows
-      launch_gemm<true>(sm, GemmArgs{P2, m, dLi, (size_t)CH_NB, P2, m, rest, nb, nb, 1.0, 0.0, nullptr, nullptr, 0}, w);
-    }
-    const hipError_t ce = hipStreamSynchronize(sm);
-    hipStreamSynchronize(sd);
-    cleanup();
-    if (ce != hipSuccess) return PSF_ERR_HIP;
-  }
-  HIP_TRY(hipGetLastError());
-  int info = -1;
-  HIP_TRY(hipMemcpy(&info, dinfo, sizeof(int), hipMemcpyDeviceToHost));
-  if (info != 0) return PSF_ERR_NOT_PD;                              // mp_perturbation.rs:109-110
-  hipLaunchKernelGGL(k_repack_L<false>, dim3(grid_for(tr_total_chunks(h->nbiL) * TR_CHUNK)), dim3(256), 0, 0, dS, m, m, h->dLt, h->nbiL);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  return PSF_OK;
+  return build_sqrt_sigma2_stream(h, nf_r2, s2, b2p1, d_sigma_packed, dS);
 }
 
 // A[:, m_bar:] = G - A_bar R  (gadget_classical.rs:66): the one product still on the limb kernel (setup path, R in int8)
@@ -988,8 +857,8 @@ static psf_status gen_A_R(psfp_handle* h, uint64_t seed, hipStream_t side = null
   h->r8_valid = false; h->small_state = 0;
   hipLaunchKernelGGL(k_sample_R, dim3(grid_for(h->mb * h->ldr)), dim3(256), 0, 0, seed, h->mb, h->w, h->ldr, h->dR);
   if (side) {
-    HIP_TRY(hipEventRecord(h->evIn, nullptr));
-    HIP_TRY(hipStreamWaitEvent(side, h->evIn, 0));
+    HIP_TRY(hipEventRecord(h->evSide, nullptr));
+    HIP_TRY(hipStreamWaitEvent(side, h->evSide, 0));
   }
   // gadget_classical.rs:66
   launch_zq_trapdoor(h, nullptr, side);
@@ -1062,12 +931,12 @@ psf_status psfp_trap_gen(psfp_handle* h, uint64_t seed) {
   PSFP_QUIESCE(h);
   KeygenClock kc("psfp");
   // A = [A_bar | G - A_bar R] (13 ms at C3) on the handle's low-priority stream beside the factorisation of Sigma_2, which needs R alone
-  const psf_status rcg = gen_A_R(h, seed, h->aux);
+  const psf_status rcg = gen_A_R(h, seed, h->side);
   if (rcg != PSF_OK) return rcg;
   kc.mark("A_bar, R (A on the side stream)");
   h->has_pub = h->has_R = true;
   const psf_status rc = build_sqrt_sigma2(h, h->prm.s);            // mp_perturbation.rs:227-231
-  HIP_TRY(hipStreamSynchronize(h->aux));
+  HIP_TRY(hipStreamSynchronize(h->side));
   if (rc != PSF_OK) { h->has_key = false; return rc; }
   kc.mark("sqrt(Sigma_2)");
   h->has_key = true;
@@ -1213,24 +1082,183 @@ psf_status psfp_export_gadget_basis(const psfp_handle* h, int64_t* Sk, double* g
 }
 
 // ---- the hot path -------------------------------------------------------------------------------------------
-// One samp_p pass over B rows (mp_perturbation.rs:304-336).  By default everything runs in order on the caller's stream.
-// With PSF_PIPELINE=1 consecutive calls alternate between two sets of intermediates: normals + FP64 product of call i+1 on
-// stream s1, sampling stages of call i on stream aux, the caller's stream joins at the end (measured zero-sum on MI355X,
-// profiles/r01_notes.md, hence off by default; covered by tests/test_gpu_pipeline_mode.py).
+// The stages behind the FP64 product (mp_perturbation.rs:316-335), each enqueued on `st` for the whole batch.
+
+// One or two preimages: rounding and the shares of A p in one launch behind the product (k_round_syndrome_small), summed by the syndrome stage
+// (rt: 16-row tiles of x per wave; two: 27 + 10 us against 34 + 14 with one, tools/fused_tail_ab.sh)
+struct FusedTail { bool on = false; int ntask = 0, rt = 2, bc = 0; };
+
+// p_i <- D_{Z,r,x_i}
+static void round_stage(psfp_handle* h, hipStream_t st, uint64_t seed, uint64_t first_index, size_t B, const FusedTail& ft) {
+  const size_t ld = h->ld, m = h->m;
+  if (ft.on) {      // and every 16-row tile's share of A p
+    ScopedTimer t(h, st, "k_round+A p");
+    StreamGeom g;
+    g.ntile = ft.ntask; g.ncg = 1; g.ntask = ft.ntask; g.bc = ft.bc;
+    const StreamFuse fz{seed, first_index, m, h->szR, h->dP, ld, h->dA32T, h->n, h->q, h->dPartF, h->dFail};
+    const size_t row_hi2 = h->structured ? h->mb : h->M_pad;
+    if (ft.rt == 1) hipLaunchKernelGGL((k_round_syndrome_small<1>), dim3((unsigned)((g.ntask + 3) / 4)), dim3(256), 0, st, h->dX, ld, row_hi2, g, fz);
+    else hipLaunchKernelGGL((k_round_syndrome_small<2>), dim3((unsigned)((g.ntask + 3) / 4)), dim3(256), 0, st, h->dX, ld, row_hi2, g, fz);
+    return;
+  }
+  ScopedTimer t(h, st, "k_perturb_round");
+  const char* renv = psf_exp_env("PSF_ROUND");                 // "wave": the round-2 kernel (comparison arm; same bits)
+  if (h->szR.sh == 16 && !(renv && !std::strcmp(renv, "wave"))) {
+    uint32_t seg = prl_segment(m * B);
+    if (const char* e = psf_exp_env("PSF_PRL_SEG")) { const long v = std::atol(e); if (v >= 64 && v <= PRL_SEG && v % 64 == 0) seg = (uint32_t)v; }      // samples per wave (experiments)
+    const size_t waves = (m * B + seg - 1) / seg;
+    if (h->szF && !(renv && !std::strcmp(renv, "lean"))) {     // the table screen ("lean": the fp32 screen of rounds 3-4, comparison arm; same bits)
+      // a segment that is one row of the [coordinate][preimage] matrix never wraps: the sample's position is its offset (no division per sample)
+      uint32_t segt = seg;
+      if (B % 64 == 0 && B >= 1024 && B <= (size_t)PRL_SEG && (size_t)seg > B) segt = (uint32_t)B;      // (short rows: every workgroup loads the table, 0.14 against 0.09 ms at 64 preimages)
+      const size_t wavest = (m * B + segt - 1) / segt;
+      if ((size_t)segt == B)
+        hipLaunchKernelGGL(k_perturb_round_tab<true>, dim3((unsigned)((wavest + 3) / 4)), dim3(256), (size_t)h->szR.n_int * h->szF * sizeof(uint32_t), st, seed, first_index, m, B, ld,
+                           h->dX, h->szR, h->dP, h->dFail, segt, SzTable{h->dSzTab, h->szF, h->szR.n_int});
+      else
+        hipLaunchKernelGGL(k_perturb_round_tab<false>, dim3((unsigned)((wavest + 3) / 4)), dim3(256), (size_t)h->szR.n_int * h->szF * sizeof(uint32_t), st, seed, first_index, m, B, ld,
+                           h->dX, h->szR, h->dP, h->dFail, segt, SzTable{h->dSzTab, h->szF, h->szR.n_int});
+    } else
+    hipLaunchKernelGGL(k_perturb_round_lean, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, seed, first_index, m, B, ld, h->dX, h->szR, h->dP, h->dFail, seg);
+  } else {
+    const size_t waves = (m * B + PR_SEG - 1) / PR_SEG;
+    hipLaunchKernelGGL(k_perturb_round_wave, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, seed, first_index, m, B, ld, h->dX, h->szR, h->dP, h->dFail);
+  }
+}
+
+// mp_perturbation.rs:318 -- v = u - A p
+static void syndrome_stage(psfp_handle* h, hipStream_t st, size_t B, const uint64_t* d_u, const FusedTail& ft) {
+  const size_t ld = h->ld;
+  ScopedTimer t(h, st, "k_zq_matmul(syndrome)");
+  if (ft.on)      // the tasks of the product left their shares of A p in dPartF: summed and taken from u, one wave per output
+    hipLaunchKernelGGL((k_zq_combine_wave<true>), dim3((unsigned)((h->n * B + 3) / 4)), dim3(256), 0, st, ZQ_SYNDROME, h->dPartF, ft.ntask, h->n, h->n, (size_t)ft.bc, B, h->q, d_u, h->dV, ld, (size_t)0);
+  else launch_zq_mfma(h, st, ZQ_SYNDROME, h->dP, h->dP8, B, d_u, h->dV, ld);
+}
+
+// mp_perturbation.rs:321-326 -- z <- D_{Lambda_v(G), r sqrt(b^2+1)}
+static void gadget_stage(psfp_handle* h, hipStream_t st, uint64_t seed, uint64_t first_index, size_t B) {
+  const size_t ld = h->ld;
+  ScopedTimer t(h, st, "k_gadget");
+  const char* genv = psf_exp_env("PSF_GADGET_WAVE");            // max n B served by the one-wave-per-problem kernel (0: never)
+  const size_t wave_max = genv ? (size_t)std::atol(genv) : 2048;    // measured at C3 (n = 512): 45 / 44 / 55 us at 1 / 2 / 4 preimages (a row per problem: 58); 91 against 58 at 8
+  const char* genvq = psf_exp_env("PSF_GADGET_QUAD");          // max n B served by the four-lanes-per-problem kernel (0: never)
+  const size_t quad_max = genvq ? (size_t)std::atol(genvq) : 98304;      // measured at C3 (tools/gadget_mid_ab.py): 0.092 / 0.092 / 0.12 / 0.24 ms at 16 / 32 / 64 / 128 preimages against
+                                                                            // 0.12 / 0.18 / 0.33 / 0.35; 0.39 against 0.33 (queue kernel) at 256
+  const char* genvr = psf_exp_env("PSF_GADGET_ROW");           // max n B served by the sixteen-lanes-per-problem form of k_gadget_quad (0: never)
+  const size_t row_max = genvr ? (size_t)std::atol(genvr) : 10240;      // measured at C3 (tools/tail_ab.py k_gadget): 0.058 / 0.071 / 0.088 ms at 8 / 16 / 24 preimages against 0.091 (one
+                                                                          // wave per problem at 8, a quad per problem at 16 and 24); 0.107 against 0.091 at 32
+  if (h->gadget_queue && h->n * B <= wave_max) {               // a single call / a handful of preimages: the chain of k draws is the launch time
+    GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
+    hipLaunchKernelGGL(k_gadget_wave, dim3((unsigned)((h->n * B + 3) / 4)), dim3(256), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q,
+                       h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail);
+  } else if (h->gadget_queue && h->n * B <= row_max && h->k <= 64) {       // a few thousand problems: a DPP row per problem, one round per draw
+    GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
+    if (h->k <= 32)
+      hipLaunchKernelGGL((k_gadget_quad<2, 16>), dim3((unsigned)((h->n * B + 15) / 16)), dim3(256), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q,
+                         h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail);
+    else
+      hipLaunchKernelGGL((k_gadget_quad<4, 16>), dim3((unsigned)((h->n * B + 15) / 16)), dim3(256), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q,
+                         h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail);
+  } else if (h->gadget_queue && h->n * B <= quad_max && h->k <= 64) {      // tens to a few hundred preimages: a quad per problem
+    GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
+    if (h->k <= 32)
+      hipLaunchKernelGGL(k_gadget_quad<8>, dim3((unsigned)((h->n * B + 63) / 64)), dim3(256), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q,
+                         h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail);
+    else
+      hipLaunchKernelGGL(k_gadget_quad<16>, dim3((unsigned)((h->n * B + 63) / 64)), dim3(256), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q,
+                         h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail);
+  } else if (h->gadget_queue) {
+    GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
+    int P = gq_problems_for((uint32_t)h->k, h->n * B);
+    if (const char* e = psf_exp_env("PSF_GQ_P")) { const int v = std::atoi(e); if (v >= 1 && v <= 128 && (v & (v - 1)) == 0) P = v; }      // problems per wave (experiments)
+    const size_t per_wg = (size_t)GQ_WAVES * P;
+    if (P == 128)
+      hipLaunchKernelGGL(k_gadget_queue<true>, dim3((unsigned)((h->n * B + per_wg - 1) / per_wg)), dim3(256), gadget_queue_lds_bytes(h->k, P), st, seed,
+                         first_index, (uint32_t)h->n, (uint32_t)h->k, h->q, h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail, P);
+    else
+      hipLaunchKernelGGL(k_gadget_queue<false>, dim3((unsigned)((h->n * B + per_wg - 1) / per_wg)), dim3(256), gadget_queue_lds_bytes(h->k, P), st, seed,
+                         first_index, (uint32_t)h->n, (uint32_t)h->k, h->q, h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail, P);
+  } else {
+    GadgetTables tb{h->dSk, h->dGso, h->dNorm2, h->dSz};
+    hipLaunchKernelGGL(k_gadget, dim3((unsigned)((B + 255) / 256), (unsigned)h->n), dim3(256), gadget_lds_bytes(h->k), st, seed, first_index,
+                       (uint32_t)h->n, (uint32_t)h->k, h->q, h->prm.gp.base, B, ld, h->dV, tb, h->dZlo, h->dZhi, h->dFail);
+  }
+}
+
+// mp_perturbation.rs:328-335 -- e = p + [R; I] z
+static void recombine_stage(psfp_handle* h, hipStream_t st, size_t B, int64_t* d_e) {
+  const size_t ld = h->ld, m = h->m;
+  ScopedTimer t(h, st, "k_recombine");
+  // a handful of preimages: R streamed once by one wave per row (PSF_RECOMBINE_SMALL = largest batch it serves, 0: never)
+  size_t small_max = 4;
+  if (const char* e = psf_exp_env("PSF_RECOMBINE_SMALL")) small_max = (size_t)std::atol(e);
+  if (small_max > 4) small_max = 4;
+  const size_t small_lds = 32 * (h->ldr / 16) * B;
+  if (B <= small_max && small_lds <= 150 * 1024) {
+    const unsigned wgs = (unsigned)std::min<size_t>((h->mb + 7) / 8, small_lds > 64 * 1024 ? 256 : 512);
+    ensure_small_copies(h, st);
+    if (h->small_state == 2) {
+      if (B == 1) hipLaunchKernelGGL(k_recombine_small2<1>, dim3(wgs), dim3(512), small_lds, st, h->dR2, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
+      else if (B == 2) hipLaunchKernelGGL(k_recombine_small2<2>, dim3(wgs), dim3(512), small_lds, st, h->dR2, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
+      else hipLaunchKernelGGL(k_recombine_small2<4>, dim3(wgs), dim3(512), small_lds, st, h->dR2, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
+      return;
+    }
+    if (B == 1) hipLaunchKernelGGL(k_recombine_small<1>, dim3(wgs), dim3(512), small_lds, st, h->dR, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
+    else if (B == 2) hipLaunchKernelGGL(k_recombine_small<2>, dim3(wgs), dim3(512), small_lds, st, h->dR, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
+    else hipLaunchKernelGGL(k_recombine_small<4>, dim3(wgs), dim3(512), small_lds, st, h->dR, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
+    return;
+  }
+  // 5 ... 448 preimages: 64 x 64 tiles over all of K, operands through an LDS-DMA ring, no atomics (k_recombine_wg); PSF_RECOMBINE_STREAM=0: the tiled kernel below
+  // (experiments build; same rows): 0.067 against 0.091 ms at 16, 0.081 against 0.155 at 64 preimages of C3 (tools/tail_ab.py)
+  size_t rs_max = 448;      // column groups of 64 preimages beyond 64 (blockIdx.y; R comes from L2 / the Infinity Cache for all but the first): 0.157 -> 0.107 ms at 65, 0.266 -> 0.115 at 128,
+                            // 0.247 -> 0.174 at 192, 0.238 -> 0.210 at 256, 0.353 -> 0.299 at 384; 0.248 -> 0.390 at 512 (the 256 x 256 tiles), 0.575 -> 0.729 at 1000 preimages
+  if (const char* e = psf_exp_env("PSF_RECOMBINE_STREAM")) rs_max = (size_t)std::min<long>(std::atol(e), 1024);
+  if (B <= rs_max && h->ldr % 128 == 0 && h->mb >= 64) {
+    const int nbf = B > 64 ? 4 : (int)((B + 15) / 16), nk2 = (int)(h->ldr / 128);
+    const unsigned ngy = (unsigned)((B + 63) / 64);
+    hipLaunchKernelGGL(k_recombine_bottom, dim3((unsigned)((B + 63) / 64), (unsigned)((h->w + 63) / 64)), dim3(256), 0, st, h->mb, h->w,
+                       h->dZlo, h->dZhi, ld, h->dP, B, d_e, m, 0);
+    const unsigned grid = (unsigned)((h->mb + 63) / 64);
+#define RW_GO(nb, nw) hipLaunchKernelGGL((k_recombine_wg<nb, nw>), dim3(grid, ngy), dim3(64 * nw), RW_LDS, st, h->dR, h->ldr, h->mb, nk2, h->dZlo, h->dZhi, ld, \
+                                     h->dFail, h->dP, B, d_e, m)
+    if (nbf == 1) RW_GO(1, 4); else if (nbf == 2) RW_GO(2, 8); else if (nbf == 3) RW_GO(3, 8); else RW_GO(4, 8);      // (four waves at 33 ... 64 preimages: 0.147 against 0.081 ms)
+#undef RW_GO
+    return;
+  }
+  // one digit plane (decided on the device by the gadget kernel): 256 x 256 tiles; otherwise, or for shapes the big tile does not fit, the 128 x 128 kernel
+  // (beyond 448 preimages also for batches that are not multiples of 256: the last tile is ragged -- its loads of z past the batch stay inside the planes or their slack,
+  // the stores are masked -- and still cheaper than the 128 x 128 kernel: 0.437 -> 0.29 ms at 704, 0.548 -> 0.30 at 832 preimages; PSF_RECOMBINE_RAGGED=0: multiples only)
+  const bool ragged_ok = !(psf_exp_env("PSF_RECOMBINE_RAGGED") && std::atoi(psf_exp_env("PSF_RECOMBINE_RAGGED")) == 0);
+  const bool big = (B % 256 == 0 || (B > rs_max && ragged_ok)) && h->mb >= 512 && (h->ldr / 64) % 2 == 0;
+  if (big) {
+    const unsigned nbx = (unsigned)((B + 255) / 256), nby = (unsigned)(h->mb_pad / 256);
+    const unsigned nsup = ((nbx + 3) / 4) * ((nby + 7) / 8);                 // super-tiles of 4 x 8 tiles, dealt to the XCDs in rounds of eight
+    ensure_R8(h, st);
+    hipLaunchKernelGGL(k_recombine_mfma_big, dim3(((nsup + 7) / 8) * 8 * 32), dim3(512), RCB_LDS, st, rcb_packed() ? h->dR8 : h->dR, rcb_packed() ? 1 : 0, h->ldr, h->mb,
+                       (int)(h->ldr / 128), h->dZlo, ld, h->dFail, h->dP, B, d_e, m, nbx, nby);
+  }
+  // few preimages: cut K over blockIdx.z (an even number of K steps each, at least 8) until ~2048 workgroups; the partial sums are added into a zeroed E
+  const unsigned tiles = (unsigned)((B + 127) / 128) * (unsigned)((h->mb + 127) / 128);
+  const int nks = (int)(h->ldr / 64);
+  int rsplits = 1, kps = nks;
+  if (!big && tiles < 1024 && nks >= 16) {
+    rsplits = (int)(2048 / tiles);
+    kps = (nks + rsplits - 1) / rsplits;
+    if (kps < 8) kps = 8;
+    kps += kps & 1;
+    rsplits = (nks + kps - 1) / kps;
+  }
+  const size_t bot_cols = rsplits > 1 && h->mb > h->w ? h->mb : h->w;
+  hipLaunchKernelGGL(k_recombine_bottom, dim3((unsigned)((B + 63) / 64), (unsigned)((bot_cols + 63) / 64)), dim3(256), 0, st, h->mb, h->w,
+                     h->dZlo, h->dZhi, ld, h->dP, B, d_e, m, rsplits > 1 ? 1 : 0);      // also zeroes the top part for the split-K form
+  hipLaunchKernelGGL(k_recombine_mfma, dim3((unsigned)((B + 127) / 128), (unsigned)((h->mb + 127) / 128), (unsigned)rsplits), dim3(256), RC_LDS, st, h->dR,
+                     h->ldr, h->mb, nks, h->dZlo, h->dZhi, ld, h->dFail, h->dP, B, d_e, m, big ? 1 : 0, kps);
+}
+
+// One samp_p pass over B rows (mp_perturbation.rs:304-336), everything in order on the caller's stream.
 static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_e, hipStream_t st) {
   const size_t ld = h->ld, m = h->m;
   const size_t nbj = h->nbj;
-  const bool pipe = h->pipeline;
-  hipStream_t user_st = st, s2 = st;
-  int cur = 0;
-  if (pipe) {
-    cur = (int)(h->ncall++ & 1);
-    select_set(h, cur);
-    HIP_TRY(hipEventRecord(h->evIn, user_st));            // u is ready on the caller's stream from here on
-    HIP_TRY(hipStreamWaitEvent(h->s1, h->evP[cur], 0));   // the previous user of this buffer set has finished
-    st = h->s1;
-    s2 = h->aux;
-  }
   if (!h->keep_fail) hipMemsetAsync(h->dFail, 0, 4 * sizeof(int), st);      // [0] sampler failure, [1] some |z| > 127, [2] some |p| >= 2^15 (third digit plane of the syndrome product in use)
   psf_status gate_rc = PSF_OK;
   auto u_gate = [&]() { if (h->before_u) { auto f = std::move(h->before_u); h->before_u = nullptr; gate_rc = f(); } };
@@ -1238,7 +1266,7 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
      // workgroup per preimage (k_samp_p_small).  PSF_FUSED_MAX = largest batch it serves (0: never).  Stage exports need the intermediates: not here.
     size_t fused_max = 64;
     if (const char* e = psf_exp_env("PSF_FUSED_MAX")) fused_max = (size_t)std::atol(e);
-    if (!pipe && !h->structured && !h->no_slice && h->gadget_queue && m <= (size_t)FS_MAX_M && h->n <= 64 && B <= fused_max) {
+    if (!h->structured && !h->no_slice && h->gadget_queue && m <= (size_t)FS_MAX_M && h->n <= 64 && B <= fused_max) {
       u_gate();
       if (gate_rc != PSF_OK) return gate_rc;
       ScopedTimer t(h, st, "k_samp_p_small");
@@ -1246,7 +1274,7 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
       hipLaunchKernelGGL(k_samp_p_small, dim3((unsigned)B), dim3(FS_THREADS), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, (uint32_t)h->mb, h->q, h->two64,
                          h->prm.gp.base, h->dLt, h->dA, h->dR, h->ldr, h->szR, tq, d_u, d_e, h->dFail);
       HIP_TRY(hipGetLastError());
-      h->last_stream = user_st;
+      h->last_stream = st;
       if (h->multi_t0 && h->multi_launched_ms < 0.0)
         h->multi_launched_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - *h->multi_t0).count();
       return PSF_OK;
@@ -1274,8 +1302,8 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
   if (const char* e = psf_exp_env("PSF_STREAM_WG")) wg_min = std::atol(e) > 0 ? (size_t)std::atol(e) : (size_t)-1;
   size_t wg_max = 64;            // measured at C3 (tools/stream_wg_ab.py): 0.91-0.96 against 1.26 ms at 33 ... 64 preimages; 241 workgroups on 256 CUs, each as long as its pair of
                                  // chains: 0.87 ms would be the matrix pipe's time on 241 CUs.  Beyond 64 preimages the forms tried (column groups of 64 with one or two
-                                 // workgroups per CU, column groups of 128 on halves of eight waves) end within 5 % of the one-wave tasks: PSF_STREAM_WG_MAX (<= 1024)
-  if (const char* e = psf_exp_env("PSF_STREAM_WG_MAX")) wg_max = std::min<size_t>((size_t)std::atol(e), 1024);      // (beyond 64: the experiments build's halves of eight waves)
+                                 // workgroups per CU, column groups of 128 on halves of eight waves) end within 5 % of the one-wave tasks: PSF_STREAM_WG_MAX (<= 64)
+  if (const char* e = psf_exp_env("PSF_STREAM_WG_MAX")) wg_max = std::min<size_t>((size_t)std::atol(e), 64);
   // Beyond 128 preimages with an ODD number of column groups of 64 (129-192, 257-320, ... 897-960): the same tiles, the column groups of a tile group on one XCD -- the
   // one-wave tasks take as long as for the next even count there (192 preimages cost what 256 do: their eight-wave workgroups hold 4 + 4 tasks, column groups of a
   // tile group side by side), the tiles' workgroups are all of one length: 2.8-2.9 against 3.7-3.9 ms at 129-192, 4.8 / 5.9 at 320, 6.6 / 7.9 at 448, 8.6 / 9.9 at 576,
@@ -1284,10 +1312,10 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
   // a small factor (m < 16 384: few tile groups, the launch lasts one chain): the tiles' waves hold 2 x 2 MFMA tiles against the one-wave tasks' 2 x 4 -- half the chain
   // (m = 932: 0.035 against 0.061 ms at 97 ... 1024 preimages, whatever the parity): the tiles from 65 preimages on
   const bool small_factor = h->mL < 16384;
-  bool wg192 = stream && ((B > 128 && B <= 960 && (((B + 63) / 64) & 1) != 0) || B > 1088 || (small_factor && B > 64)) && wg_max <= 64 && !psf_exp_env("PSF_TRMM_STREAM_SHAPE");      // (1025-1088: 15.9 against 16.5)
+  bool wg192 = stream && ((B > 128 && B <= 960 && (((B + 63) / 64) & 1) != 0) || B > 1088 || (small_factor && B > 64)) && !psf_exp_env("PSF_TRMM_STREAM_SHAPE");      // (1025-1088: 15.9 against 16.5)
   if (const char* e = psf_exp_env("PSF_STREAM_WG192")) {
     long lo = 0, hi = 0;
-    wg192 = std::sscanf(e, "%ld:%ld", &lo, &hi) == 2 && lo >= 65 && hi <= 2048 && stream && B >= (size_t)lo && B <= (size_t)hi && wg_max <= 64 && !psf_exp_env("PSF_TRMM_STREAM_SHAPE");
+    wg192 = std::sscanf(e, "%ld:%ld", &lo, &hi) == 2 && lo >= 65 && hi <= 2048 && stream && B >= (size_t)lo && B <= (size_t)hi && !psf_exp_env("PSF_TRMM_STREAM_SHAPE");
   }
   const bool wg = stream && ((B >= wg_min && B <= wg_max) || wg192) && !psf_exp_env("PSF_TRMM_STREAM_SHAPE");
   // 17 ... 32 preimages: 64 x 32 tiles of the same ring (k_trmm_stream_wg32); PSF_STREAM_WG32=0 keeps the one-wave tasks (experiments build; same bits)
@@ -1295,7 +1323,7 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
   // 65 ... 96 preimages: the first 64 on the 64 x 64 tiles, the rest on the 64 x 32 tiles, two launches over one normals stream of six fragments (0.94 + 0.65 ms against 1.80 for
   // the one-wave tasks, which pay for 128 columns); PSF_STREAM_WG96=0 keeps those (experiments build; same bits)
   const bool wg96 = stream && !wg && !small_factor && B >= 65 && B <= 96 && !psf_exp_env("PSF_TRMM_STREAM_SHAPE") && !(psf_exp_env("PSF_STREAM_WG96") && std::atoi(psf_exp_env("PSF_STREAM_WG96")) == 0);
-  if (wg) { RT = 2; NB = (B <= 64 || wg192) ? 4 : 8; }      // column groups of 64 (halves of four waves) or 128 preimages (halves of eight waves)
+  if (wg) { RT = 2; NB = 4; }                    // column groups of 64 preimages (halves of four waves)
   if (wg32 || wg96) { RT = 2; NB = 2; }          // (wg96: three column groups of 32 = the six fragments of the stream)
   if (const char* e = psf_exp_env("PSF_TRMM_STREAM_SHAPE")) std::sscanf(e, "%d,%d", &RT, &NB);
   if (!(NB == 1 || NB == 2 || NB == 4 || NB == 8)) NB = 1;
@@ -1318,28 +1346,24 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
   }
   // One or two preimages: rounding and syndrome in ONE launch behind the product (k_round_syndrome_small, psf_stream_kernels.hpp) once the transposed compact copy
   // of A is there (built beside the first small calls after a key change, as the other compact copies)
-  bool fused_tail = false;
-  int fused_ntask = 0, fused_rt = 2;      // two 16-row tiles per wave: 27 + 10 us against 34 + 14 with one (tools/fused_tail_ab.sh)
-  if (stream && bc && B <= 2 && RT == 2 && NB == 1 && !h->structured && !pipe && h->szR.sh == 16 && !(h->prm.flags & PSFP_FLAG_NO_PERTURB)) {
+  FusedTail ft;
+  ft.bc = bc;
+  if (stream && bc && B <= 2 && RT == 2 && NB == 1 && !h->structured && h->szR.sh == 16 && !(h->prm.flags & PSFP_FLAG_NO_PERTURB)) {
     ensure_small_copies(h, st);
     const char* fe = psf_exp_env("PSF_FUSED_TAIL");
     if (h->dA32T && (h->small_state == 2 || h->small_state == 3) && !(fe && std::atoi(fe) == 0)) {
-      if (const char* e = psf_exp_env("PSF_FUSED_RT")) fused_rt = std::atoi(e) == 1 ? 1 : 2;
-      fused_ntask = ((int)((h->mL + 15) / 16) + fused_rt - 1) / fused_rt;      // one wave per fused_rt 16-row tiles of x
-      const size_t need = (size_t)fused_ntask * h->n * 2;
+      if (const char* e = psf_exp_env("PSF_FUSED_RT")) ft.rt = std::atoi(e) == 1 ? 1 : 2;
+      ft.ntask = ((int)((h->mL + 15) / 16) + ft.rt - 1) / ft.rt;      // one wave per ft.rt 16-row tiles of x
+      const size_t need = (size_t)ft.ntask * h->n * 2;
       if (need > h->partF_cap) {
         hipFree(h->dPartF); h->dPartF = nullptr; h->partF_cap = 0;
         if (hipMalloc(&h->dPartF, need * sizeof(uint64_t)) == hipSuccess) h->partF_cap = need; else (void)hipGetLastError();
       }
-      fused_tail = h->dPartF != nullptr;
+      ft.on = h->dPartF != nullptr;
     }
   }
   {  // x = sqrt(Sigma_2) d   (structured: the m_bar x m_bar block L_1 d_1; rows from m_bar on already hold x_bot = h d_2)
     ScopedTimer t(h, st, "k_trmm_f64");
-    // default: k_trmm_f64_big (one workgroup per CU, accumulators in AccVGPRs); PSF_TRMM_VARIANT=1: k_trmm_f64_reg (two 128 x 128 workgroups per CU,
-    // operands streamed into registers), 0: k_trmm_f64 (LDS-staged, round 1).  Same bits from all three.
-    const char* venv = psf_exp_env("PSF_TRMM_VARIANT");      // read per call: the tests compare the kernels inside one process
-    const int variant = venv ? std::atoi(venv) : 2;
     const size_t row_hi = h->structured ? h->mb : h->M_pad;
     if (stream && wg96) {
       StreamGeom g;
@@ -1373,19 +1397,10 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
       g.ntask = g.ntile * g.ncg;
       g.bc = 0;
       const unsigned nwg = (unsigned)((g.ntask + 1) / 2);
-      if (NB == 4) {         // column groups of 64 preimages: one workgroup of 2 x 4 waves per CU, rounds of four k-steps; several groups: those of a tile group on one XCD
-        const unsigned grid64 = ncg > 1 ? 8 * ((nwg + 7) / 8) : nwg;
-        if (compact) hipLaunchKernelGGL((k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 1, 2>), dim3(grid64), dim3(512), TSW_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
-        else hipLaunchKernelGGL((k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 0, 2>), dim3(grid64), dim3(512), TSW_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
-      }
-#ifdef PSF_EXPERIMENTS
-      else {                 // column groups of 128 preimages: 2 x 8 waves, rounds of two k-steps (96 KiB); the column groups of a tile group on one XCD.  Measured against the
-                             // one-wave tasks (tools/stream_wg_ab.py): 1.93 / 1.91 ms at 128, 3.55 / 3.72 at 256, 7.16 / 7.58 at 512, 14.25 / 14.33 at 1024 preimages -- not kept
-        const unsigned grid = ncg > 1 ? 8 * ((nwg + 7) / 8) : nwg;
-        if (compact) hipLaunchKernelGGL((k_trmm_stream_wg<2, TSW_NBUF, 1, 4>), dim3(grid), dim3(1024), TSW128_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
-        else hipLaunchKernelGGL((k_trmm_stream_wg<2, TSW_NBUF, 0, 4>), dim3(grid), dim3(1024), TSW128_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
-      }
-#endif
+      // column groups of 64 preimages: one workgroup of 2 x 4 waves per CU, rounds of four k-steps; several groups: those of a tile group on one XCD
+      const unsigned grid64 = ncg > 1 ? 8 * ((nwg + 7) / 8) : nwg;
+      if (compact) hipLaunchKernelGGL((k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 1, 2>), dim3(grid64), dim3(512), TSW_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
+      else hipLaunchKernelGGL((k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 0, 2>), dim3(grid64), dim3(512), TSW_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
     }
     else if (stream) {
       const int ntile16 = (int)((h->mL + 15) / 16);
@@ -1411,7 +1426,7 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
       else TS_GO(1, 1, 8, 4)
 #undef TS_GO
     }
-    else if (variant == 2 || !psf_experiments_build) {
+    else {                   // k_trmm_f64_big: one workgroup per CU, accumulators in AccVGPRs
       int GR = 8, GC = 4;                                     // super-tile of an XCD's 32 resident workgroups; PSF_TRMM_GR x PSF_TRMM_GC for experiments (product = 32)
       // below 4096 preimages, or with a number of 128-column blocks that is not a multiple of four: 16 x 2 -- the grid is padded to whole super-columns, and 8 x 4 pays for up
       // to three empty column blocks (round 6, tools/tail_ab.py: 34.9 -> 32.3 ms at 2176, 47.8 -> 44.1 at 3200, 27.2 -> 26.3 at 2048; 51.9 against 52.5 at 4096: 8 x 4 stays there)
@@ -1420,12 +1435,6 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
       if (GR < 1 || GC < 1 || GR * GC != 32) { GR = 8; GC = 4; }
       hipLaunchKernelGGL(k_trmm_f64_big, dim3(tr_grid_size(((int)h->nbiL + 1) / 2, (int)nbj, GR, GC)), dim3(256), 0, st, h->dLt, h->dDt, h->dX, (int)h->nbiL, (int)nbj, h->nkb, ld, GR, GC, row_hi);
     }
-#ifdef PSF_EXPERIMENTS
-    else if (variant == 1)
-      hipLaunchKernelGGL(k_trmm_f64_reg, dim3(tr_grid_size((int)h->nbiL, (int)nbj, 8, 8)), dim3(256), 0, st, h->dLt, h->dDt, h->dX, (int)h->nbiL, (int)nbj, h->nkb, ld, 8, 8, row_hi);
-    else
-      hipLaunchKernelGGL(k_trmm_f64, dim3(tr_grid_size((int)h->nbiL, (int)nbj, 8, 8)), dim3(256), 4 * TR_CHUNK * sizeof(double), st, h->dLt, h->dDt, h->dX, (int)h->nbiL, (int)nbj, h->nkb, ld, 8, 8, row_hi);
-#endif
   }
   if (h->structured) {  // x_top -= g R d_2 (exact integer sum on the int8 matrix cores)
     ensure_R8(h, st);
@@ -1433,205 +1442,14 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
     hipLaunchKernelGGL(k_rd2_mfma, dim3((unsigned)(ld / 64), (unsigned)(round_up(h->mb, 64) / 64)), dim3(256), 3 * (1 + kFixPlanes) * 4096, st, h->dR8, h->ldr, h->dD8, h->ldr * ld, ld,
                        h->mb, h->g_const, h->dX);
   }
-  if (pipe) {
-    HIP_TRY(hipEventRecord(h->evT[cur], st));
-    HIP_TRY(hipStreamWaitEvent(s2, h->evT[cur], 0));
-    HIP_TRY(hipStreamWaitEvent(s2, h->evIn, 0));
-  }
-  // The stages behind the product, for the columns [b0, b0 + Bh) of the batch on stream sx.  Column offsets: [coord][b] matrices move by b0 elements,
-  // digit planes ([group][b][16]) by 16 b0 bytes, row-major API matrices by b0 rows; the Z_q product takes its window as (col0, ncols).
-  auto tail = [&](hipStream_t sx, size_t b0, size_t Bh) {
-    if (fused_tail) {   // p_i <- D_{Z,r,x_i} and every 16-row tile's share of A p, one launch (k_round_syndrome_small)
-      ScopedTimer t(h, sx, "k_round+A p");
-      StreamGeom g;
-      g.ntile = fused_ntask; g.ncg = 1; g.ntask = fused_ntask; g.bc = bc;
-      const StreamFuse fz{seed, first_index, m, h->szR, h->dP, ld, h->dA32T, h->n, h->q, h->dPartF, h->dFail};
-      const size_t row_hi2 = h->structured ? h->mb : h->M_pad;
-      if (fused_rt == 1) hipLaunchKernelGGL((k_round_syndrome_small<1>), dim3((unsigned)((g.ntask + 3) / 4)), dim3(256), 0, sx, h->dX, ld, row_hi2, g, fz);
-      else hipLaunchKernelGGL((k_round_syndrome_small<2>), dim3((unsigned)((g.ntask + 3) / 4)), dim3(256), 0, sx, h->dX, ld, row_hi2, g, fz);
-    }
-    if (!fused_tail) {  // p_i <- D_{Z,r,x_i}
-      ScopedTimer t(h, sx, "k_perturb_round");
-      const char* renv = psf_exp_env("PSF_ROUND");                 // "wave": the round-2 kernel (comparison arm; same bits)
-      if (h->szR.sh == 16 && !(renv && !std::strcmp(renv, "wave"))) {
-        uint32_t seg = prl_segment(m * Bh);
-        if (const char* e = psf_exp_env("PSF_PRL_SEG")) { const long v = std::atol(e); if (v >= 64 && v <= PRL_SEG && v % 64 == 0) seg = (uint32_t)v; }      // samples per wave (experiments)
-        const size_t waves = (m * Bh + seg - 1) / seg;
-        if (h->szF && !(renv && !std::strcmp(renv, "lean"))) {     // the table screen ("lean": the fp32 screen of rounds 3-4, comparison arm; same bits)
-          // a segment that is one row of the [coordinate][preimage] matrix never wraps: the sample's position is its offset (no division per sample)
-          uint32_t segt = seg;
-          if (Bh % 64 == 0 && Bh >= 1024 && Bh <= (size_t)PRL_SEG && (size_t)seg > Bh) segt = (uint32_t)Bh;      // (short rows: every workgroup loads the table, 0.14 against 0.09 ms at 64 preimages)
-          const size_t wavest = (m * Bh + segt - 1) / segt;
-          if ((size_t)segt == Bh)
-            hipLaunchKernelGGL(k_perturb_round_tab<true>, dim3((unsigned)((wavest + 3) / 4)), dim3(256), (size_t)h->szR.n_int * h->szF * sizeof(uint32_t), sx, seed, first_index + b0, m, Bh, ld,
-                               h->dX + b0, h->szR, h->dP + b0, h->dFail, segt, SzTable{h->dSzTab, h->szF, h->szR.n_int});
-          else
-            hipLaunchKernelGGL(k_perturb_round_tab<false>, dim3((unsigned)((wavest + 3) / 4)), dim3(256), (size_t)h->szR.n_int * h->szF * sizeof(uint32_t), sx, seed, first_index + b0, m, Bh, ld,
-                               h->dX + b0, h->szR, h->dP + b0, h->dFail, segt, SzTable{h->dSzTab, h->szF, h->szR.n_int});
-        } else
-        hipLaunchKernelGGL(k_perturb_round_lean, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, sx, seed, first_index + b0, m, Bh, ld, h->dX + b0, h->szR, h->dP + b0, h->dFail, seg);
-      } else {
-        const size_t waves = (m * Bh + PR_SEG - 1) / PR_SEG;
-        hipLaunchKernelGGL(k_perturb_round_wave, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, sx, seed, first_index + b0, m, Bh, ld, h->dX + b0, h->szR, h->dP + b0, h->dFail);
-      }
-    }
-    u_gate();                                                      // (host path: u reaches the device now)
-    {  // mp_perturbation.rs:318 -- v = u - A p
-      ScopedTimer t(h, sx, "k_zq_matmul(syndrome)");
-      if (fused_tail)      // the tasks of the product left their shares of A p in dPartF: summed and taken from u, one wave per output
-        hipLaunchKernelGGL((k_zq_combine_wave<true>), dim3((unsigned)((h->n * Bh + 3) / 4)), dim3(256), 0, sx, ZQ_SYNDROME, h->dPartF, fused_ntask, h->n, h->n, (size_t)bc, Bh, h->q, d_u, h->dV, ld, (size_t)0);
-      else launch_zq_mfma(h, sx, ZQ_SYNDROME, h->dP, h->dP8, Bh, d_u, h->dV, ld, b0);
-    }
-    {  // mp_perturbation.rs:321-326 -- z <- D_{Lambda_v(G), r sqrt(b^2+1)}
-      ScopedTimer t(h, sx, "k_gadget");
-      const char* genv = psf_exp_env("PSF_GADGET_WAVE");            // max n B served by the one-wave-per-problem kernel (0: never)
-      const size_t wave_max = genv ? (size_t)std::atol(genv) : 2048;    // measured at C3 (n = 512): 45 / 44 / 55 us at 1 / 2 / 4 preimages (a row per problem: 58); 91 against 58 at 8
-#ifdef PSF_EXPERIMENTS
-      const char* genv16 = psf_exp_env("PSF_GADGET_WAVE16");        // max n B served by the sixteen-lanes-per-problem kernel (0: never)
-      const size_t wave16_max = genv16 ? (size_t)std::atol(genv16) : 49152;     // measured at C3: 0.33 vs 0.48 ms at 64 preimages, 0.65 vs 0.60 at 128
-#endif
-      const char* genvq = psf_exp_env("PSF_GADGET_QUAD");          // max n B served by the four-lanes-per-problem kernel (0: never)
-      const size_t quad_max = genvq ? (size_t)std::atol(genvq) : 98304;      // measured at C3 (tools/gadget_mid_ab.py): 0.092 / 0.092 / 0.12 / 0.24 ms at 16 / 32 / 64 / 128 preimages against
-                                                                                // 0.12 / 0.18 / 0.33 / 0.35; 0.39 against 0.33 (queue kernel) at 256
-      const char* genvr = psf_exp_env("PSF_GADGET_ROW");           // max n B served by the sixteen-lanes-per-problem form of k_gadget_quad (0: never)
-      const size_t row_max = genvr ? (size_t)std::atol(genvr) : 10240;      // measured at C3 (tools/tail_ab.py k_gadget): 0.058 / 0.071 / 0.088 ms at 8 / 16 / 24 preimages against 0.091 (one
-                                                                              // wave per problem at 8, a quad per problem at 16 and 24); 0.107 against 0.091 at 32
-      if (h->gadget_queue && h->n * Bh <= wave_max) {               // a single call / a handful of preimages: the chain of k draws is the launch time
-        GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
-        hipLaunchKernelGGL(k_gadget_wave, dim3((unsigned)((h->n * Bh + 3) / 4)), dim3(256), 0, sx, seed, first_index + b0, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                           h->prm.gp.base, Bh, ld, h->dV + b0, tq, h->dZlo + 16 * b0, h->dZhi + 16 * b0, h->dFail);
-      } else if (h->gadget_queue && h->n * Bh <= row_max && h->k <= 64) {       // a few thousand problems: a DPP row per problem, one round per draw
-        GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
-        if (h->k <= 32)
-          hipLaunchKernelGGL((k_gadget_quad<2, 16>), dim3((unsigned)((h->n * Bh + 15) / 16)), dim3(256), 0, sx, seed, first_index + b0, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                             h->prm.gp.base, Bh, ld, h->dV + b0, tq, h->dZlo + 16 * b0, h->dZhi + 16 * b0, h->dFail);
-        else
-          hipLaunchKernelGGL((k_gadget_quad<4, 16>), dim3((unsigned)((h->n * Bh + 15) / 16)), dim3(256), 0, sx, seed, first_index + b0, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                             h->prm.gp.base, Bh, ld, h->dV + b0, tq, h->dZlo + 16 * b0, h->dZhi + 16 * b0, h->dFail);
-      } else if (h->gadget_queue && h->n * Bh <= quad_max && h->k <= 64) {      // tens to a few hundred preimages: a quad per problem
-        GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
-        if (h->k <= 32)
-          hipLaunchKernelGGL(k_gadget_quad<8>, dim3((unsigned)((h->n * Bh + 63) / 64)), dim3(256), 0, sx, seed, first_index + b0, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                             h->prm.gp.base, Bh, ld, h->dV + b0, tq, h->dZlo + 16 * b0, h->dZhi + 16 * b0, h->dFail);
-        else
-          hipLaunchKernelGGL(k_gadget_quad<16>, dim3((unsigned)((h->n * Bh + 63) / 64)), dim3(256), 0, sx, seed, first_index + b0, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                             h->prm.gp.base, Bh, ld, h->dV + b0, tq, h->dZlo + 16 * b0, h->dZhi + 16 * b0, h->dFail);
-#ifdef PSF_EXPERIMENTS
-      } else if (h->gadget_queue && h->n * Bh <= wave16_max) {      // up to a few hundred preimages: four problems per wave
-        GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
-        hipLaunchKernelGGL(k_gadget_wave16, dim3((unsigned)((h->n * Bh + 15) / 16)), dim3(256), 0, sx, seed, first_index + b0, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                           h->prm.gp.base, Bh, ld, h->dV + b0, tq, h->dZlo + 16 * b0, h->dZhi + 16 * b0, h->dFail);
-#endif
-      } else if (h->gadget_queue) {
-        GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
-        int P = gq_problems_for((uint32_t)h->k, h->n * Bh);
-        if (const char* e = psf_exp_env("PSF_GQ_P")) { const int v = std::atoi(e); if (v >= 1 && v <= 128 && (v & (v - 1)) == 0) P = v; }      // problems per wave (experiments)
-        const size_t per_wg = (size_t)GQ_WAVES * P;
-        if (P == 128)
-          hipLaunchKernelGGL(k_gadget_queue<true>, dim3((unsigned)((h->n * Bh + per_wg - 1) / per_wg)), dim3(256), gadget_queue_lds_bytes(h->k, P), sx, seed,
-                             first_index + b0, (uint32_t)h->n, (uint32_t)h->k, h->q, h->prm.gp.base, Bh, ld, h->dV + b0, tq, h->dZlo + 16 * b0, h->dZhi + 16 * b0, h->dFail, P);
-        else
-          hipLaunchKernelGGL(k_gadget_queue<false>, dim3((unsigned)((h->n * Bh + per_wg - 1) / per_wg)), dim3(256), gadget_queue_lds_bytes(h->k, P), sx, seed,
-                             first_index + b0, (uint32_t)h->n, (uint32_t)h->k, h->q, h->prm.gp.base, Bh, ld, h->dV + b0, tq, h->dZlo + 16 * b0, h->dZhi + 16 * b0, h->dFail, P);
-      } else {
-        GadgetTables tb{h->dSk, h->dGso, h->dNorm2, h->dSz};
-        hipLaunchKernelGGL(k_gadget, dim3((unsigned)((Bh + 255) / 256), (unsigned)h->n), dim3(256), gadget_lds_bytes(h->k), sx, seed, first_index + b0,
-                           (uint32_t)h->n, (uint32_t)h->k, h->q, h->prm.gp.base, Bh, ld, h->dV + b0, tb, h->dZlo + 16 * b0, h->dZhi + 16 * b0, h->dFail);
-      }
-    }
-    {  // mp_perturbation.rs:328-335 -- e = p + [R; I] z
-      ScopedTimer t(h, sx, "k_recombine");
-      // a handful of preimages: R streamed once by one wave per row (PSF_RECOMBINE_SMALL = largest batch it serves, 0: never)
-      size_t small_max = 4;
-      if (const char* e = psf_exp_env("PSF_RECOMBINE_SMALL")) small_max = (size_t)std::atol(e);
-      if (small_max > 4) small_max = 4;
-      const size_t small_lds = 32 * (h->ldr / 16) * Bh;
-      if (Bh <= small_max && small_lds <= 150 * 1024) {
-        const unsigned wgs = (unsigned)std::min<size_t>((h->mb + 7) / 8, small_lds > 64 * 1024 ? 256 : 512);
-        ensure_small_copies(h, sx);
-        if (h->small_state == 2) {
-          if (Bh == 1) hipLaunchKernelGGL(k_recombine_small2<1>, dim3(wgs), dim3(512), small_lds, sx, h->dR2, h->ldr, h->mb, h->w, h->dZlo + 16 * b0, h->dZhi + 16 * b0, ld, h->dP + b0, Bh, d_e + b0 * m, m);
-          else if (Bh == 2) hipLaunchKernelGGL(k_recombine_small2<2>, dim3(wgs), dim3(512), small_lds, sx, h->dR2, h->ldr, h->mb, h->w, h->dZlo + 16 * b0, h->dZhi + 16 * b0, ld, h->dP + b0, Bh, d_e + b0 * m, m);
-          else hipLaunchKernelGGL(k_recombine_small2<4>, dim3(wgs), dim3(512), small_lds, sx, h->dR2, h->ldr, h->mb, h->w, h->dZlo + 16 * b0, h->dZhi + 16 * b0, ld, h->dP + b0, Bh, d_e + b0 * m, m);
-          return;
-        }
-        if (Bh == 1) hipLaunchKernelGGL(k_recombine_small<1>, dim3(wgs), dim3(512), small_lds, sx, h->dR, h->ldr, h->mb, h->w, h->dZlo + 16 * b0, h->dZhi + 16 * b0, ld, h->dP + b0, Bh, d_e + b0 * m, m);
-        else if (Bh == 2) hipLaunchKernelGGL(k_recombine_small<2>, dim3(wgs), dim3(512), small_lds, sx, h->dR, h->ldr, h->mb, h->w, h->dZlo + 16 * b0, h->dZhi + 16 * b0, ld, h->dP + b0, Bh, d_e + b0 * m, m);
-        else hipLaunchKernelGGL(k_recombine_small<4>, dim3(wgs), dim3(512), small_lds, sx, h->dR, h->ldr, h->mb, h->w, h->dZlo + 16 * b0, h->dZhi + 16 * b0, ld, h->dP + b0, Bh, d_e + b0 * m, m);
-        return;
-      }
-      // 5 ... 448 preimages: 64 x 64 tiles over all of K, operands through an LDS-DMA ring, no atomics (k_recombine_wg); PSF_RECOMBINE_STREAM=0: the tiled kernel below
-      // (experiments build; same rows): 0.067 against 0.091 ms at 16, 0.081 against 0.155 at 64 preimages of C3 (tools/tail_ab.py)
-      size_t rs_max = 448;      // column groups of 64 preimages beyond 64 (blockIdx.y; R comes from L2 / the Infinity Cache for all but the first): 0.157 -> 0.107 ms at 65, 0.266 -> 0.115 at 128,
-                                // 0.247 -> 0.174 at 192, 0.238 -> 0.210 at 256, 0.353 -> 0.299 at 384; 0.248 -> 0.390 at 512 (the 256 x 256 tiles), 0.575 -> 0.729 at 1000 preimages
-      if (const char* e = psf_exp_env("PSF_RECOMBINE_STREAM")) rs_max = (size_t)std::min<long>(std::atol(e), 1024);
-      if (Bh <= rs_max && h->ldr % 128 == 0 && h->mb >= 64) {
-        const int nbf = Bh > 64 ? 4 : (int)((Bh + 15) / 16), nk2 = (int)(h->ldr / 128);
-        const unsigned ngy = (unsigned)((Bh + 63) / 64);
-        hipLaunchKernelGGL(k_recombine_bottom, dim3((unsigned)((Bh + 63) / 64), (unsigned)((h->w + 63) / 64)), dim3(256), 0, sx, h->mb, h->w,
-                           h->dZlo + 16 * b0, h->dZhi + 16 * b0, ld, h->dP + b0, Bh, d_e + b0 * m, m, 0);
-        const unsigned grid = (unsigned)((h->mb + 63) / 64);
-#define RW_GO(nb, nw) hipLaunchKernelGGL((k_recombine_wg<nb, nw>), dim3(grid, ngy), dim3(64 * nw), RW_LDS, sx, h->dR, h->ldr, h->mb, nk2, h->dZlo + 16 * b0, h->dZhi + 16 * b0, ld, \
-                                         h->dFail, h->dP + b0, Bh, d_e + b0 * m, m)
-        if (nbf == 1) RW_GO(1, 4); else if (nbf == 2) RW_GO(2, 8); else if (nbf == 3) RW_GO(3, 8); else RW_GO(4, 8);      // (four waves at 33 ... 64 preimages: 0.147 against 0.081 ms)
-#undef RW_GO
-        return;
-      }
-      // one digit plane (decided on the device by the gadget kernel): 256 x 256 tiles; otherwise, or for shapes the big tile does not fit, the 128 x 128 kernel
-      // (beyond 448 preimages also for batches that are not multiples of 256: the last tile is ragged -- its loads of z past the batch stay inside the planes or their slack,
-      // the stores are masked -- and still cheaper than the 128 x 128 kernel: 0.437 -> 0.29 ms at 704, 0.548 -> 0.30 at 832 preimages; PSF_RECOMBINE_RAGGED=0: multiples only)
-      const bool ragged_ok = !(psf_exp_env("PSF_RECOMBINE_RAGGED") && std::atoi(psf_exp_env("PSF_RECOMBINE_RAGGED")) == 0);
-      const bool big = (Bh % 256 == 0 || (Bh > rs_max && ragged_ok)) && b0 % 256 == 0 && h->mb >= 512 && (h->ldr / 64) % 2 == 0;
-      if (big) {
-        const unsigned nbx = (unsigned)((Bh + 255) / 256), nby = (unsigned)(h->mb_pad / 256);
-        const unsigned nsup = ((nbx + 3) / 4) * ((nby + 7) / 8);                 // super-tiles of 4 x 8 tiles, dealt to the XCDs in rounds of eight
-        ensure_R8(h, sx);
-        hipLaunchKernelGGL(k_recombine_mfma_big, dim3(((nsup + 7) / 8) * 8 * 32), dim3(512), RCB_LDS, sx, rcb_packed() ? h->dR8 : h->dR, rcb_packed() ? 1 : 0, h->ldr, h->mb,
-                           (int)(h->ldr / 128), h->dZlo + 16 * b0, ld, h->dFail, h->dP + b0, Bh, d_e + b0 * m, m, nbx, nby);
-      }
-      // few preimages: cut K over blockIdx.z (an even number of K steps each, at least 8) until ~2048 workgroups; the partial sums are added into a zeroed E
-      const unsigned tiles = (unsigned)((Bh + 127) / 128) * (unsigned)((h->mb + 127) / 128);
-      const int nks = (int)(h->ldr / 64);
-      int rsplits = 1, kps = nks;
-      if (!big && tiles < 1024 && nks >= 16) {
-        rsplits = (int)(2048 / tiles);
-        kps = (nks + rsplits - 1) / rsplits;
-        if (kps < 8) kps = 8;
-        kps += kps & 1;
-        rsplits = (nks + kps - 1) / kps;
-      }
-      const size_t bot_cols = rsplits > 1 && h->mb > h->w ? h->mb : h->w;
-      hipLaunchKernelGGL(k_recombine_bottom, dim3((unsigned)((Bh + 63) / 64), (unsigned)((bot_cols + 63) / 64)), dim3(256), 0, sx, h->mb, h->w,
-                         h->dZlo + 16 * b0, h->dZhi + 16 * b0, ld, h->dP + b0, Bh, d_e + b0 * m, m, rsplits > 1 ? 1 : 0);      // also zeroes the top part for the split-K form
-      hipLaunchKernelGGL(k_recombine_mfma, dim3((unsigned)((Bh + 127) / 128), (unsigned)((h->mb + 127) / 128), (unsigned)rsplits), dim3(256), RC_LDS, sx, h->dR,
-                         h->ldr, h->mb, nks, h->dZlo + 16 * b0, h->dZhi + 16 * b0, ld, h->dFail, h->dP + b0, Bh, d_e + b0 * m, m, big ? 1 : 0, kps);
-    }
-  };
-  // PSF_HALVES=1: the batch's two halves run these stages on two streams, so that the int8 matrix-core kernels of one half (Z_q product, recombination)
-  // can share the chip with the vector-bound samplers of the other (vector work hides behind int8 / bf16 MFMAs, unlike behind FP64 ones: profiles/r03_notes.md)
-  const char* henv = psf_exp_env("PSF_HALVES");
-  const bool halves = !pipe && henv && std::atoi(henv) != 0 && B >= 512 && B % 256 == 0;      // (at 32 / 64 preimages the two halves last as long as the whole: profiles/r06_notes.md)
-  if (!halves) {
-    tail(s2, 0, B);
-  } else {
-    const size_t Bh = B / 2;
-    HIP_TRY(hipEventRecord(h->evT[0], st));
-    HIP_TRY(hipStreamWaitEvent(h->s1, h->evT[0], 0));
-    HIP_TRY(hipStreamWaitEvent(h->aux, h->evT[0], 0));
-    tail(h->s1, 0, Bh);
-    tail(h->aux, Bh, B - Bh);
-    HIP_TRY(hipEventRecord(h->evP[0], h->s1));
-    HIP_TRY(hipEventRecord(h->evP[1], h->aux));
-    HIP_TRY(hipStreamWaitEvent(user_st, h->evP[0], 0));
-    HIP_TRY(hipStreamWaitEvent(user_st, h->evP[1], 0));
-  }
-  if (pipe) {
-    HIP_TRY(hipEventRecord(h->evP[cur], h->aux));
-    HIP_TRY(hipStreamWaitEvent(user_st, h->evP[cur], 0));   // results of this call are ordered before later work on the caller's stream
-  }
+  round_stage(h, st, seed, first_index, B, ft);
+  u_gate();                                                      // (host path: u reaches the device now)
+  syndrome_stage(h, st, B, d_u, ft);
+  gadget_stage(h, st, seed, first_index, B);
+  recombine_stage(h, st, B, d_e);
   HIP_TRY(hipGetLastError());
   if (gate_rc != PSF_OK) return gate_rc;
-  h->last_stream = user_st;
+  h->last_stream = st;
   if (h->multi_t0 && h->multi_launched_ms < 0.0)
     h->multi_launched_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - *h->multi_t0).count();
   return PSF_OK;
@@ -1640,10 +1458,9 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
 psf_status psfp_last_status(psfp_handle* h) {
   if (!h) return PSF_ERR_PARAM;
   HIP_TRY(hipStreamSynchronize(h->last_stream));
-  int f = 0, f2 = 0;
-  HIP_TRY(hipMemcpy(&f, h->sets[0].dFail, sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&f2, h->sets[1].dFail, sizeof(int), hipMemcpyDeviceToHost));
-  return (f | f2) ? PSF_ERR_SAMPLER : PSF_OK;
+  int f = 0;
+  HIP_TRY(hipMemcpy(&f, h->dFail, sizeof(int), hipMemcpyDeviceToHost));
+  return f ? PSF_ERR_SAMPLER : PSF_OK;
 }
 
 psf_status psfp_samp_p_dev(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_e, void* stream) {
@@ -1666,7 +1483,6 @@ psf_status psfp_samp_p_dev_many(psfp_handle* h, size_t count, const uint64_t* se
   if (!h->has_key || !h->has_pub) return PSF_ERR_NO_KEY;
   if (count == 0 || B == 0) return PSF_OK;
   if (count == 1) return psfp_samp_p_dev(h, seeds[0], first_indices[0], B, d_u, d_e, stream);
-  if (h->pipeline) return PSF_ERR_UNSUPPORTED;             // PSF_PIPELINE=1 alternates two sets of failure words per call: single calls only (as psfp_samp_p_async)
   HIP_TRY(hipSetDevice(h->prm.device));
   PSFP_QUIESCE(h);
   psf_status rc = ensure_batch(h, B);
@@ -1686,10 +1502,10 @@ psf_status psfp_samp_p_dev_many(psfp_handle* h, size_t count, const uint64_t* se
 
 // ---- host-pointer entry points ---------------------------------------------------------------------------------------------------------------
 constexpr size_t SIO_MAX_BYTES = (size_t)1 << 20;           // calls whose u + e fit this take the one-buffer form (at 4 MB the runtime's copies are faster again: 1.27 vs 1.17 ms at C3, 16 preimages)
-// flags of a small call into the pinned buffer: [0] = a[0] | b[0] (the two failure words psfp_last_status reads), [1 ..] = c[0 .. nc)
-__global__ void k_sio_flags(const int* __restrict__ a, const int* __restrict__ b, const int* __restrict__ c, int nc, int* __restrict__ out) {
+// flags of a small call into the pinned buffer: [0] = a[0] (the failure word psfp_last_status reads), [1 ..] = c[0 .. nc)
+__global__ void k_sio_flags(const int* __restrict__ a, const int* __restrict__ c, int nc, int* __restrict__ out) {
   const int t = threadIdx.x;
-  if (t == 0) out[0] = (a ? a[0] : 0) | (b ? b[0] : 0);
+  if (t == 0) out[0] = a[0];
   if (t >= 1 && t <= nc) out[t] = c[t - 1];
 }
 static psf_status sio_ensure(psfp_handle* h, size_t bytes) {
@@ -1703,7 +1519,7 @@ static psf_status sio_ensure(psfp_handle* h, size_t bytes) {
 static inline unsigned sio_grid(size_t words) { const size_t g = (words / 2 + 255) / 256; return (unsigned)(g < 1 ? 1 : g > 64 ? 64 : g); }
 // u -> pinned -> d_u (kernel); [the caller's launches]; d_e -> pinned, flags -> pinned (kernels); one synchronisation; pinned -> e.  `flags_out` receives
 // 1 + nc ints.  `run` enqueues the call on the null stream and returns its status.
-static psf_status sio_call(psfp_handle* h, size_t nu, size_t ne, const uint64_t* u, int64_t* e, uint64_t* d_u, int64_t* d_e, const int* fa, const int* fb, const int* fc, int nc,
+static psf_status sio_call(psfp_handle* h, size_t nu, size_t ne, const uint64_t* u, int64_t* e, uint64_t* d_u, int64_t* d_e, const int* fa, const int* fc, int nc,
                            int* flags_out, const std::function<psf_status()>& run) {
   const size_t ub = round_up(nu * 8, 64), eb = round_up(ne * 8, 64);
   psf_status rc = sio_ensure(h, ub + eb + 64);
@@ -1716,7 +1532,7 @@ static psf_status sio_call(psfp_handle* h, size_t nu, size_t ne, const uint64_t*
   rc = run();
   if (rc != PSF_OK) { hipStreamSynchronize(nullptr); return rc; }
   hipLaunchKernelGGL(k_copy_words, dim3(sio_grid(ne)), dim3(256), 0, nullptr, reinterpret_cast<const uint64_t*>(d_e), reinterpret_cast<uint64_t*>(he), ne);
-  hipLaunchKernelGGL(k_sio_flags, dim3(1), dim3(64), 0, nullptr, fa, fb, fc, nc, hf);
+  hipLaunchKernelGGL(k_sio_flags, dim3(1), dim3(64), 0, nullptr, fa, fc, nc, hf);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(nullptr));
   for (int i = 0; i <= nc; ++i) flags_out[i] = hf[i];
@@ -1822,10 +1638,7 @@ static psf_status hp_ensure(psfp_handle* h, int slot, size_t entries, size_t u_w
     hp.chunk_entries = (size_t)2 << 20;                                  // 8 MiB of int32 per chunk
     if (const char* env = std::getenv("PSF_HOST_WORKERS")) { const int v = std::atoi(env); if (v >= 1 && v <= NW) hp.nw = v; }
     if (const char* env = psf_exp_env("PSF_HOST_CHUNK_MB")) { const long v = std::atol(env); if (v >= 1 && v <= 256) hp.chunk_entries = (size_t)v << 18; }
-    if (const char* env = psf_exp_env("PSF_HOST_COPY")) {                 // sdma (default) | runtime | kernel[:workgroups]
-      if (std::strncmp(env, "runtime", 7) == 0) hp.copy_mode = 0;
-      else if (std::strncmp(env, "kernel", 6) == 0) { hp.copy_mode = 2; if (env[6] == ':') { const int g = std::atoi(env + 7); if (g >= 1 && g <= 4096) hp.copy_grid = g; } }
-    }
+    if (const char* env = psf_exp_env("PSF_HOST_COPY")) if (std::strncmp(env, "runtime", 7) == 0) hp.copy_mode = 0;      // sdma (default) | runtime
     if (hp.copy_mode == 1) {
       int dom = 0, bus = 0, dv = 0;
       HIP_TRY(hipDeviceGetAttribute(&dom, hipDeviceAttributePciDomainID, h->prm.device));
@@ -1850,7 +1663,7 @@ static psf_status hp_ensure(psfp_handle* h, int slot, size_t entries, size_t u_w
   if (entries > hp.cap_entries[slot]) {
     hipFree(hp.dE32[slot]); hp.dE32[slot] = nullptr;
     hp.cap_entries[slot] = 0;
-    HIP_TRY(hipMalloc(&hp.dE32[slot], entries * sizeof(int32_t) + 8));      // (+8: the copy kernel moves 8-byte words)
+    HIP_TRY(hipMalloc(&hp.dE32[slot], entries * sizeof(int32_t)));
     hp.cap_entries[slot] = entries;
   }
   if (u_words > hp.u_cap[slot]) {
@@ -1881,7 +1694,6 @@ psf_status psfp_samp_p_async(psfp_handle* h, uint64_t seed, uint64_t first_index
   if (!h || (B && (!u || !e))) return PSF_ERR_PARAM;
   if (!h->has_key || !h->has_pub) return PSF_ERR_NO_KEY;
   if (B == 0) return PSF_OK;
-  if (h->pipeline) return PSF_ERR_UNSUPPORTED;              // PSF_PIPELINE=1 alternates two sets of failure words per call: the synchronous forms only (as psfp_samp_p does)
   struct FailGuard { psfp_handle* h; size_t B; ~FailGuard() { h->keep_fail = false; h->nbj = round_up(B, TR_BN) / TR_BN; } } guard{h, B};
   return hp_async(h, B, u, e, true, true, nullptr, [&](size_t off, size_t cnt, const uint64_t* d_u, int64_t* d_e, hipStream_t cs) -> psf_status {
     h->keep_fail = true;                                    // the slices of a call share its failure words (cleared once, in front of the first)
@@ -1934,10 +1746,10 @@ static psf_status hp_async(psfp_handle* h, size_t B, const uint64_t* u, int64_t*
   if (const char* env = psf_exp_env("PSF_HOST_TAIL")) { const long v = std::atol(env); if (v >= 128) tail = (size_t)v; }
   bool cut = hp.slice_tail;                                 // the synchronous form only: behind an asynchronous call the next call's compute covers the transfer
   if (const char* env = psf_exp_env("PSF_HOST_ASYNC_SLICE")) cut = cut || std::atoi(env) != 0;      // experiments: 1 = asynchronous calls cut the tail slice too
-  if (cut && allow_slices && !h->no_slice && !h->pipeline && B >= 2 * tail) { cuts[1] = B - tail; cuts[2] = B; nsl = 2; }
+  if (cut && allow_slices && !h->no_slice && B >= 2 * tail) { cuts[1] = B - tail; cuts[2] = B; nsl = 2; }
   if (const char* env = psf_exp_env("PSF_HOST_SLICE")) {    // experiments: equal slices of this many rows (at most four)
     const long v = std::atol(env);
-    if (v >= 128 && allow_slices && !h->no_slice && !h->pipeline && (size_t)v < B) {
+    if (v >= 128 && allow_slices && !h->no_slice && (size_t)v < B) {
       nsl = 0;
       for (size_t off = 0; off < B && nsl < 4; off += (size_t)v) cuts[nsl++] = off;
       cuts[nsl] = B;
@@ -1968,9 +1780,9 @@ static psf_status hp_async(psfp_handle* h, size_t B, const uint64_t* u, int64_t*
   const int nw = hp.nw;
   int dbg = 0;
   if (const char* env = psf_exp_env("PSF_HOST_DEBUG")) dbg = std::atoi(env);      // measurement only: 1 = no widening, 2 = no copies either (e is NOT filled)
-  const int copy_mode = hp.copy_mode, copy_grid = hp.copy_grid;
+  const int copy_mode = hp.copy_mode;
   const bool plain_widen = psf_exp_env("PSF_HOST_PLAIN_WIDEN") != nullptr;      // measurement only: the scalar loop with ordinary stores
-  auto worker = [&hp, slot, src, e, total, CE, nchunks, nsl, device, slice_end, slice_ev, nw, dbg, copy_mode, copy_grid, plain_widen](int w) {
+  auto worker = [&hp, slot, src, e, total, CE, nchunks, nsl, device, slice_end, slice_ev, nw, dbg, copy_mode, plain_widen](int w) {
     if (hipSetDevice(device) != hipSuccess) { hp.status[slot] = (int)PSF_ERR_HIP; return; }
     auto widen = [&](size_t c, int k) {
       if (copy_mode == 1 ? (dbg < 2 && !hp.sdma.wait(hp.sigC[slot][w][k])) : hipEventSynchronize(hp.evC[slot][w][k]) != hipSuccess) { hp.status[slot] = (int)PSF_ERR_HIP; return; }
@@ -1981,11 +1793,6 @@ static psf_status hp_async(psfp_handle* h, size_t B, const uint64_t* u, int64_t*
       if (plain_widen) { for (size_t i = 0; i < cnt; ++i) dst[i] = (int64_t)hs[i]; }
       else widen_rows(dst, hs, cnt);
     };
-    auto move_chunk = [&](int32_t* dst, const int32_t* from, size_t cnt) -> hipError_t {
-      if (copy_mode == 0) return hipMemcpyAsync(dst, from, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, hp.copy);
-      hipLaunchKernelGGL(k_copy_words, dim3(copy_grid), dim3(256), 0, hp.copy, reinterpret_cast<const uint64_t*>(from), reinterpret_cast<uint64_t*>(dst), (cnt + 1) / 2);
-      return hipGetLastError();
-    };
     long prev = -1; int pk = 0, k = 0;
     for (size_t c = (size_t)w; c < nchunks; c += (size_t)nw) {
       const size_t b0 = c * CE, cnt = total - b0 < CE ? total - b0 : CE;
@@ -1995,7 +1802,7 @@ static psf_status hp_async(psfp_handle* h, size_t B, const uint64_t* u, int64_t*
         if (hipEventSynchronize(slice_ev[j]) != hipSuccess ||
             (dbg < 2 && !hp.sdma.start(hp.hbuf[slot][w][k], src + b0, cnt * sizeof(int32_t), hp.sigC[slot][w][k]))) { hp.status[slot] = (int)PSF_ERR_HIP; break; }
       } else if (hipStreamWaitEvent(hp.copy, slice_ev[j], 0) != hipSuccess ||
-                 (dbg < 2 ? move_chunk(hp.hbuf[slot][w][k], src + b0, cnt) : hipSuccess) != hipSuccess ||
+                 (dbg < 2 ? hipMemcpyAsync(hp.hbuf[slot][w][k], src + b0, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, hp.copy) : hipSuccess) != hipSuccess ||
                  hipEventRecord(hp.evC[slot][w][k], hp.copy) != hipSuccess) { hp.status[slot] = (int)PSF_ERR_HIP; break; }
       if (prev >= 0) widen((size_t)prev, pk);
       prev = (long)c; pk = k; k ^= 1;
@@ -2048,16 +1855,16 @@ psf_status psfp_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index, size
   if (!h->has_key || !h->has_pub) return PSF_ERR_NO_KEY;
   if (B == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(h->prm.device));
-  if (B * h->m < ((size_t)1 << 20) || h->no_slice || h->pipeline) {
+  if (B * h->m < ((size_t)1 << 20) || h->no_slice) {
     // a single call / a handful of preimages (or a stage export): nothing to overlap -- straight through on the default stream
     psf_status rc = psfp_wait(h);
     if (rc != PSF_OK) return rc;
     rc = ensure_batch(h, B);
     if (rc != PSF_OK) return rc;
-    if (!h->no_slice && !h->pipeline && B * (h->n + h->m) * 8 <= SIO_MAX_BYTES && !psf_exp_env("PSF_HOST_STRAIGHT")) {
+    if (!h->no_slice && B * (h->n + h->m) * 8 <= SIO_MAX_BYTES && !psf_exp_env("PSF_HOST_STRAIGHT")) {
       if (h->timing) clear_slots(h);
       int fl[1] = {0};
-      rc = sio_call(h, B * h->n, B * h->m, u, e, h->dU, h->dE, h->sets[0].dFail, h->sets[1].dFail, nullptr, 0, fl,
+      rc = sio_call(h, B * h->n, B * h->m, u, e, h->dU, h->dE, h->dFail, nullptr, 0, fl,
                     [&]() { return run_samp_p(h, seed, first_index, B, h->dU, h->dE, nullptr); });
       if (rc != PSF_OK) return rc;
       return fl[0] ? PSF_ERR_SAMPLER : PSF_OK;
@@ -2284,8 +2091,6 @@ psf_status psfp_enable_timing(psfp_handle* h, int on) {
 psf_status psfp_get_timing(psfp_handle* h, char* names, size_t names_len, double* ms, size_t* count) {
   if (!h || !count) return PSF_ERR_PARAM;
   HIP_TRY(hipStreamSynchronize(h->last_stream));
-  HIP_TRY(hipStreamSynchronize(h->aux));
-  HIP_TRY(hipStreamSynchronize(h->s1));
   std::string joined;
   std::vector<std::string> names_v;
   std::vector<double> sums;
