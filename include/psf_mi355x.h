@@ -144,6 +144,30 @@ psf_status psf_poly_mul_negacyclic_dev(int device, uint64_t q, size_t n, size_t 
 psf_status psf_ntt_forward_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, int io_bits, uint32_t* d_hat, void* stream);
 psf_status psf_poly_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, const uint32_t* d_hat, size_t hat_stride, const void* d_b, void* d_out, int io_bits,
                                 void* stream);
+/* R_q coefficient maps of the ML-KEM-style schemes, on a flat array of `len` coefficients (any number of polynomials, or of the entries of a
+ * MatPolynomialRingZq, n coefficients each, constant term first).  Exact integer arithmetic, bit for bit against the big-integer definitions:
+ *   compress   (LossyCompressionFIPS203::lossy_compress, lossy_compression_fips203.rs:89-112):   y = floor((x 2^d + floor(q/2)) / q) mod 2^d,
+ *              x read as its residue mod q;
+ *   decompress (lossy_decompress, :143-172):   x = floor((y q + 2^(d-1)) / 2^d) mod q for any signed y, written as the least non-negative
+ *              residue (the reference stores the unreduced value, which can be q, or anything when y is outside [0, 2^d): the same element of R_q);
+ *   encode     (encode_value_in_polynomialringzq, common_encodings.rs:49-91, after the base-`base` digits of the value): out = digit floor(q/base) mod q;
+ *   decode     (decode_value_from_polynomialringzq, :125-151, before the digits are composed): digit = floor((base c + floor(q/(2 base))) / q) mod base,
+ *              c read as its residue mod q.
+ * Splitting a value into digits and composing digits into a value stay with the caller (tools_amd/encodings.py), as does reducing a PolyOverZ of
+ * degree >= n.  Limits: 2 <= q < 2^62 (q < 2 PSF_ERR_PARAM, q >= 2^62 PSF_ERR_UNSUPPORTED); d < 1 PSF_ERR_PARAM (the reference panics), d > 63
+ * PSF_ERR_UNSUPPORTED (a compressed value is an int64); base < 2 PSF_ERR_PARAM, base >= 2^63 PSF_ERR_UNSUPPORTED.  len = 0 is PSF_OK.  Every
+ * argument is checked before the first HIP call.  The host-pointer forms run on the device (no CPU fallback; PSF_ERR_HIP without one). */
+psf_status psf_lossy_compress(int device, uint64_t q, uint32_t d, size_t len, const uint64_t* x, int64_t* y);
+psf_status psf_lossy_decompress(int device, uint64_t q, uint32_t d, size_t len, const int64_t* y, uint64_t* x);
+psf_status psf_encode_digits(int device, uint64_t q, uint64_t base, size_t len, const uint64_t* digits, uint64_t* out);
+psf_status psf_decode_digits(int device, uint64_t q, uint64_t base, size_t len, const uint64_t* coeffs, uint64_t* digits);
+/* The same maps on DEVICE buffers, ordered on `stream`, nothing allocated per call.  io_bits = 64: the word types of the host forms;
+ * io_bits = 16: uint16 words in and out (a compressed y is read mod 2^d, so signed or unsigned is the same), for q <= 2^16, d <= 16,
+ * base <= 2^16 (PSF_ERR_UNSUPPORTED otherwise); any other io_bits PSF_ERR_PARAM.  Pointers need only the alignment of their word. */
+psf_status psf_lossy_compress_dev(int device, uint64_t q, uint32_t d, size_t len, const void* d_x, void* d_y, int io_bits, void* stream);
+psf_status psf_lossy_decompress_dev(int device, uint64_t q, uint32_t d, size_t len, const void* d_y, void* d_x, int io_bits, void* stream);
+psf_status psf_encode_digits_dev(int device, uint64_t q, uint64_t base, size_t len, const void* d_digits, void* d_out, int io_bits, void* stream);
+psf_status psf_decode_digits_dev(int device, uint64_t q, uint64_t base, size_t len, const void* d_coeffs, void* d_digits, int io_bits, void* stream);
 /* rot_minus_matrix (rotation_matrix.rs:85-96): mat[rows x cols] -> out[rows x rows*cols] */
 psf_status psf_rot_minus_matrix(const int64_t* mat, size_t rows, size_t cols, int64_t* out);
 
