@@ -144,6 +144,30 @@ psf_status psf_poly_mul_negacyclic_dev(int device, uint64_t q, size_t n, size_t 
 psf_status psf_ntt_forward_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, int io_bits, uint32_t* d_hat, void* stream);
 psf_status psf_poly_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, const uint32_t* d_hat, size_t hat_stride, const void* d_b, void* d_out, int io_bits,
                                 void* stream);
+/* MatPolynomialRingZq * MatPolynomialRingZq (gpv_ring.rs:245, gadget_ring.rs:78 and :190-202, short_basis_ring.rs:183-198):
+ * C[c] = op(A[c]) . B[c] over R_q = Z_q[X]/(X^n + 1), for c < count, on DEVICE buffers in the caller's stream, nothing allocated per call.
+ * Matrices of polynomials are row-major; each polynomial is n coefficients, constant term first.
+ *   A[c]: at d_a + c * a_stride polynomials; a_stride = 0 means one A for every batch.
+ *         trans_a = 0: A is rows x inner and op(A) = A;  trans_a = 1: A is stored inner x rows and op(A) = A^T.
+ *   B[c]: inner x cols, contiguous after B[c-1].   C[c]: rows x cols, contiguous after C[c-1].
+ *   io_bits = 64: a uint64 (any value), b int64 (any value), out uint64 in [0, q); every 2 <= q < 2^62 and n <= 8192.
+ *   io_bits = 16: the 16-bit contract of psf_poly_mul_negacyclic_dev (a uint16 in [0, q), b int16 in (-q, q), out uint16); NTT primes q < 2^14 with
+ *                 n = 128 ... 1024 (a wave kernel), PSF_ERR_UNSUPPORTED otherwise.
+ * Exact for every inner <= 2^20 (PSF_ERR_UNSUPPORTED above).  When (q, n) has a wave kernel, one wave owns (batch, output column, tile of output
+ * rows): B[c][k][j] is transformed once per tile, the leaf products are summed at one Montgomery scale, and each output polynomial takes one inverse
+ * transform.  Every other q runs an exact schoolbook kernel.
+ * PSF_ERR_PARAM: q <= 1 or q >= 2^62, n outside 1 ... 8192 (the codes of the pair product), rows, inner or cols = 0, trans_a not 0 / 1, io_bits not 16 / 64,
+ * a NULL pointer when count > 0, a byte count that overflows size_t, or an output range that overlaps an input range.  count = 0 is PSF_OK.
+ * Every check runs before the first HIP call; on PSF_ERR_PARAM / PSF_ERR_UNSUPPORTED nothing is launched and nothing is written.  A valid call
+ * without a device is PSF_ERR_HIP (no CPU fallback). */
+psf_status psf_matpoly_mul_negacyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
+                                          int trans_a, const void* d_b, void* d_c, int io_bits, void* stream);
+/* The same with A given by its images from psf_ntt_forward_dev (rows * inner images per batch, in A's storage order).  hat_stride is in 32-bit words;
+ * 0 means one set of images for every batch (staged in LDS when its rows * inner * n words fit).  The shapes of psf_poly_mul_hat_dev only. */
+psf_status psf_matpoly_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint32_t* d_hat, size_t hat_stride,
+                                   int trans_a, const void* d_b, void* d_c, int io_bits, void* stream);
+/* host buffers, one product C = A . B (rows x inner, inner x cols -> rows x cols); allocates per call, like psf_poly_mul_negacyclic */
+psf_status psf_matpoly_mul_negacyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, uint64_t* c);
 /* R_q coefficient maps of the ML-KEM-style schemes, on a flat array of `len` coefficients (any number of polynomials, or of the entries of a
  * MatPolynomialRingZq, n coefficients each, constant term first).  Exact integer arithmetic, bit for bit against the big-integer definitions:
  *   compress   (LossyCompressionFIPS203::lossy_compress, lossy_compression_fips203.rs:89-112):   y = floor((x 2^d + floor(q/2)) / q) mod 2^d,

@@ -2,7 +2,8 @@
 
 Host-side mirror of the reference's interface for this path (src/primitive/psf.rs:39-81):
 GadgetParameters.init_default, PSFPerturbation / PSFGPV / PSFGPVRing with
-trap_gen / samp_d / samp_p / f_a / check_domain; compression (LossyCompressionFIPS203) and encodings (utils::common_encodings).
+trap_gen / samp_d / samp_p / f_a / check_domain; compression (LossyCompressionFIPS203), encodings (utils::common_encodings) and
+rq (MatPolynomialRingZq matrix products).
 Everything computes on the GPU through the C ABI.
 """
 from ._ffi import PsfError, LIB_PATH  # noqa: F401
@@ -12,3 +13,4 @@ from . import textio  # noqa: F401
 from . import serde_json  # noqa: F401
 from . import compression  # noqa: F401
 from . import encodings  # noqa: F401
+from . import rq  # noqa: F401

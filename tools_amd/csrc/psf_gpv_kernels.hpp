@@ -148,6 +148,51 @@ __global__ __launch_bounds__(256) void k_polymul_negacyclic(uint64_t q, uint64_t
   }
 }
 
+// ---- R_q matrix product C[c] = op(A[c]) B[c] (MatPolynomialRingZq * MatPolynomialRingZq) for every q < 2^62 without a wave NTT ---------------------
+// A[c]: rows x inner polynomials at A + c * a_stride polynomials (trans_a: stored inner x rows), B[c]: inner x cols, C[c]: rows x cols.  One workgroup
+// per output polynomial (c, i, j) at a time; per 256-coefficient chunk of it and per k < inner, A[c][i][k] and B[c][k][j] are staged in LDS (reduced mod
+// q) and thread t adds the terms of coefficient chunk + t.  Exact: for q < 2^31 the positive and negative parts are summed over all of `inner` in
+// 128 bits (inner n < 2^33 terms below 2^62) and reduced once; above, every term is reduced.
+__global__ __launch_bounds__(256) void k_matpoly_negacyclic(uint64_t q, uint64_t two64, uint32_t n, size_t count, size_t rows, size_t inner, size_t cols,
+                                                            const uint64_t* __restrict__ A, size_t a_stride, int trans_a, const int64_t* __restrict__ Bp,
+                                                            uint64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) uint64_t mp_smem[];   // a[n] | b[n]
+  uint64_t* sa = mp_smem;
+  uint64_t* sb = mp_smem + n;
+  const bool small = q <= 0x7fffffffull;
+  const size_t outs = count * rows * cols;
+  for (size_t o = blockIdx.x; o < outs; o += gridDim.x) {
+    const size_t j = o % cols, ci = o / cols, i = ci % rows, c = ci / rows;
+    for (uint32_t c0 = 0; c0 < n; c0 += 256) {
+      const uint32_t cc = c0 + threadIdx.x;
+      Acc128 P{0, 0}, N{0, 0};
+      uint64_t pos = 0, neg = 0;
+      for (size_t k = 0; k < inner; ++k) {
+        const uint64_t* pa = A + (c * a_stride + (trans_a ? k * rows + i : i * inner + k)) * n;
+        const int64_t* pb = Bp + ((c * inner + k) * cols + j) * n;
+        __syncthreads();
+        for (uint32_t t = threadIdx.x; t < n; t += 256) {
+          sa[t] = pa[t] % q;
+          const int64_t v = pb[t] % (int64_t)q;
+          sb[t] = (uint64_t)(v < 0 ? v + (int64_t)q : v);
+        }
+        __syncthreads();
+        if (cc >= n) continue;
+        if (small) {
+          for (uint32_t t = 0; t <= cc; ++t) acc128_add(P, (int64_t)(sa[t] * sb[cc - t]));
+          for (uint32_t t = cc + 1; t < n; ++t) acc128_add(N, (int64_t)(sa[t] * sb[n + cc - t]));
+        } else {
+          for (uint32_t t = 0; t <= cc; ++t) { pos += mulmod_dev(sa[t], sb[cc - t], q); if (pos >= q) pos -= q; }
+          for (uint32_t t = cc + 1; t < n; ++t) { neg += mulmod_dev(sa[t], sb[n + cc - t], q); if (neg >= q) neg -= q; }
+        }
+      }
+      if (cc >= n) continue;
+      if (small) { pos = acc128_mod(P, q, two64); neg = acc128_mod(N, q, two64); }
+      out[o * n + cc] = pos >= neg ? pos - neg : pos + q - neg;
+    }
+  }
+}
+
 // The NTT forms of this product (one transform per wavefront, Montgomery arithmetic) are in psf_ntt_kernels.hpp / psf_ntt.hip.
 
 }  // namespace psf

@@ -258,4 +258,42 @@ psf_status ntt_ring_fa_dev(int device, uint64_t q, size_t n, uint32_t K, const u
   return PSF_OK;
 }
 
+
+psf_status ntt_matmul_dev(int device, uint64_t q, size_t n, const NttMatShape& s, const void* d_a, size_t a_stride, bool hat, const void* d_b, void* d_c,
+                          int io_bits, hipStream_t st) {
+  psf_status rc;
+  Plan* P = plan_for(device, q, n, &rc);
+  if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
+  if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
+  const size_t zn = (P->tb.qb == 12 ? 4u : 2u) << P->pl.L;
+  const bool stage = hat && a_stride == 0 && (zn + s.rows * s.inner * n) * sizeof(uint32_t) <= 64 * 1024;   // one A for all: its images in LDS
+  if (s.count == 0) return PSF_OK;
+  NTT_TRY(hipSetDevice(device));
+  const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
+    constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
+    const NttDev a = dev_args(P, Kern<LN, LDV, QBV>::E, Kern<LN, LDV, QBV>::E + 1);
+    MatArgs m;
+    m.count = s.count; m.rows = s.rows; m.inner = s.inner; m.cols = s.cols; m.a_stride = a_stride; m.trans_a = s.trans_a;
+    m.tiles = (s.rows + MatTile<LN>::RT - 1) / MatTile<LN>::RT;
+    m.items = s.count * s.cols * m.tiles;
+    const int r1 = (int)((1u << 16) % P->tb.q);
+    m.r1 = r1 > (int)(P->tb.q / 2) ? r1 - (int)P->tb.q : r1;
+    const size_t smem = (zn + (stage ? s.rows * s.inner * n : 0)) * sizeof(uint32_t);
+    const dim3 grid(wave_grid(m.items));
+    auto go = [&](auto io) {
+      constexpr int IO = decltype(io)::value;
+      if (!hat) hipLaunchKernelGGL((k_matpoly_mul<LN, LDV, QBV, IO, 0>), grid, dim3(256), smem, st, a, m, d_a, d_b, d_c);
+      else if (!stage) hipLaunchKernelGGL((k_matpoly_mul<LN, LDV, QBV, IO, 1>), grid, dim3(256), smem, st, a, m, d_a, d_b, d_c);
+      else hipLaunchKernelGGL((k_matpoly_mul<LN, LDV, QBV, IO, 2>), grid, dim3(256), smem, st, a, m, d_a, d_b, d_c);
+    };
+    if constexpr (QBV != 0) {
+      if (io_bits == 16) { go(ic<16>{}); return; }
+    }
+    go(ic<64>{});
+  });
+  if (!ok) return PSF_ERR_UNSUPPORTED;                      // route 2 without an instantiated shape: nothing was launched
+  NTT_TRY(hipGetLastError());
+  return PSF_OK;
+}
+
 }  // namespace psf

@@ -20,4 +20,10 @@ psf_status ntt_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, const
 // u_b = sum_{j < K} a_j * sigma_{b,j}: sigma B rows of K*n int64, u B rows of n uint64 (PSFGPVRing::f_a, gpv_ring.rs:243-247)
 psf_status ntt_ring_fa_dev(int device, uint64_t q, size_t n, uint32_t K, const uint32_t* d_hat, const int64_t* d_sigma, uint64_t* d_u, size_t B, hipStream_t st);
 
+// C[c] = op(A[c]) B[c] over R_q for `count` batches of matrices of polynomials (psf_matpoly_mul_*_dev; arguments checked by the caller), route 2 only:
+// hat = false: A as polynomials in the io_bits layout of a, a_stride in polynomials; hat = true: A as images, a_stride in words.  0: one A for all.
+struct NttMatShape { size_t count, rows, inner, cols; int trans_a; };
+psf_status ntt_matmul_dev(int device, uint64_t q, size_t n, const NttMatShape& s, const void* d_a, size_t a_stride, bool hat, const void* d_b, void* d_c,
+                          int io_bits, hipStream_t st);
+
 }  // namespace psf

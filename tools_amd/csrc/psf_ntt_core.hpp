@@ -109,6 +109,20 @@ template <int QB, int LOGN, int LD> struct Bounds16 {
   static_assert(make().ok, "bound analysis failed");
 };
 
+// The schedule of acc_tick.  16-bit form: a summand (leaf product) is at most xc; an accumulator is a 24-bit multiply operand whose product with a
+// centred constant (|r1| < ZM) must leave room for the reduction, so it stays at most XA = min(2^23 - 1, LIM / ZM).  The fold x -> mont(r1 x)
+// leaves at most XR = rb(XA ZM); T = (XA - XR) / xc more summands fit before the next one.  After the last summand |acc| <= XA, and one
+// reduction brings it to rb(XA) <= xc.  32-bit form: md.add keeps every sum canonical, nothing to fold (T = 0: acc_tick does nothing).
+template <class BD, bool LAZY> struct AccSched { static constexpr long long XA = 0, XR = 0, T = 0; };
+template <class BD> struct AccSched<BD, true> {
+  static constexpr long long XA = BD::I24 < BD::LIM / BD::ZM ? BD::I24 : BD::LIM / BD::ZM;
+  static constexpr long long XR = BD::rb(XA * BD::ZM);
+  static constexpr long long T = (XA - XR) / BD::r.xc;
+  static_assert(T >= 1 && T < (1ll << 30), "at least one summand between folds");
+  static_assert(XR + T * BD::r.xc <= XA, "accumulator bound");
+  static_assert(BD::rb(XA) <= BD::r.xc, "the closed sum must start the inverse transform within xc");
+};
+
 // ---- arithmetic policies --------------------------------------------------------------------------------------------------------------------------
 // Both expose: V (lane value), mul(z, x) = z x R^-1, add, sub, mont(x) = x R^-1 (uniform reduction), canon(x) in [0, q).
 template <class W, int QB_> struct Mod16 {
@@ -303,7 +317,33 @@ template <class W, class M, class BD, int LOGN, int LD> struct Core {
       }
     }
   }
+
+  // ---- sums of leaf products at ONE Montgomery scale (the R_q matrix product: acc_i = sum_k a_ik * b_k, one inverse transform per output) ---------
+  // acc_add adds a leaf product into an accumulator; acc_tick, called once after every summand k (all accumulators got one), keeps them in range;
+  // acc_close brings an accumulator under the bound the inverse transform starts from.  The scale never changes between summands, so any number of
+  // them can be summed; the one extra uniform reduction of acc_close is the R^-1 that fin_fa carries (Kern::E + 1), as in k_ring_fa.
+  using AS = AccSched<BD, M::lazy>;
+  static PSF_NTT_FN void acc_add(V (&acc)[C], const V (&c)[C], const M& md) {
+#pragma unroll
+    for (int r = 0; r < C; ++r) acc[r] = md.add(acc[r], c[r]);
+  }
+  // r1 = R mod q in the centred form: mul(r1, x) = x R R^-1 = x mod q, |result| <= XR
+  template <int RT> static PSF_NTT_FN void acc_tick(V (&acc)[RT][C], const M& md, V r1, int& since) {
+    if constexpr (M::lazy) {
+      if (++since == (int)AS::T) {
+        since = 0;
+#pragma unroll
+        for (int t = 0; t < RT; ++t)
+#pragma unroll
+          for (int r = 0; r < C; ++r) acc[t][r] = md.mul(r1, acc[t][r]);
+      }
+    }
+  }
+  static PSF_NTT_FN void acc_close(V (&acc)[C], const M& md) {
+    if constexpr (M::lazy) reduce_all(acc, md);
+  }
 };
+
 
 }  // namespace ntt
 }  // namespace psf

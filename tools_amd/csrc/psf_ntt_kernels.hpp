@@ -4,6 +4,8 @@
 //   k_ntt_mul_hat      out = a * b with a given by its image
 //   k_ring_fa          u = sum_j a_j * sigma_j (PSFGPVRing::f_a, gpv_ring.rs:243-247) from the cached images of a: K forward transforms,
 //                      K leaf products accumulated, ONE inverse transform per preimage
+//   k_matpoly_mul      C = op(A) B over R_q for batches of matrices of polynomials: B transformed once per row tile, sums of leaf products at one
+//                      Montgomery scale (Core::acc_add / acc_tick), ONE inverse transform per output polynomial
 // 16-bit I/O (a: uint16 in [0, q), b: int16 in (-q, q), out: uint16) beside the 64-bit ABI of psf_poly_mul_negacyclic.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -318,6 +320,87 @@ __global__ __launch_bounds__(256) void k_ring_fa(NttDev p, const uint32_t* __res
     KN::K::inverse(acc, md, zi, lane);
     KN::K::finish(acc, md, (V)(QB != 0 ? p.fin_fa : p.fin));
     KN::template store<64>(acc, u, pr, lane);
+  }
+}
+
+// C[c] = op(A[c]) B[c] over R_q (MatPolynomialRingZq * MatPolynomialRingZq: gpv_ring.rs:245, gadget_ring.rs:78 and :190-202,
+// short_basis_ring.rs:183-198).  Row-major matrices of polynomials; A[c] is rows x inner (trans_a = 0) or stored inner x rows (trans_a = 1).
+struct MatArgs {
+  size_t count, rows, inner, cols;
+  size_t a_stride;           // HAT = 0: polynomials between the A of consecutive batches; HAT = 1: words between their images; 0: one A for all
+  size_t tiles, items;       // row tiles per (batch, column); count * cols * tiles
+  int trans_a;
+  int r1;                    // R mod q, centred (the fold of acc_tick; 16-bit form only)
+};
+// One wave per work item (batch c, output column j, tile of RT output rows), RT accumulators in registers.  For every k < inner the wave transforms
+// B[c][k][j] once and adds the leaf products with the images of A[c][i][k] (i in the tile) into the accumulators; then one inverse transform and one
+// finish per output polynomial.  HAT = 0: A as polynomials (IO layout of a), transformed here; 1: A as images (psf_ntt_forward_dev) in global
+// memory; 2: one set of images for every batch, staged in LDS behind the zetas.
+template <int LOGN> struct MatTile { static constexpr int C = 1 << (LOGN - 6), RT = 32 / C > 8 ? 8 : 32 / C; };   // RT * C = 32 accumulator registers
+template <int LOGN, int LD, int QB, int IO, int HAT>
+__global__ __launch_bounds__(256) void k_matpoly_mul(NttDev p, MatArgs m, const void* __restrict__ A, const void* __restrict__ B, void* __restrict__ out) {
+  using KN = Kern<LOGN, LD, QB>;
+  using V = typename KN::V;
+  constexpr int C = KN::C, RT = MatTile<LOGN>::RT;
+  extern __shared__ __attribute__((aligned(16))) uint32_t mm_smem[];   // zetas [ZN] (| images [rows * inner][C][64] when HAT = 2)
+  uint32_t* zt = mm_smem;
+  const uint32_t* ah = mm_smem + KN::ZN;
+  if constexpr (HAT == 2) {
+    const size_t words = m.rows * m.inner * (size_t)KN::N;
+    for (size_t i = threadIdx.x; i < words; i += blockDim.x) mm_smem[KN::ZN + i] = reinterpret_cast<const uint32_t*>(A)[i];
+  }
+  KN::load_tables(zt, p);
+  const auto md = make_policy<QB>(p, KN::L);
+  const int lane = DevWave::lane();
+  const size_t waves = (size_t)gridDim.x * (blockDim.x >> 6);
+  const uint32_t* zf = zt;
+  const uint32_t* zi = zt + (1 << KN::L);
+  for (size_t it = (size_t)blockIdx.x * (blockDim.x >> 6) + wave_in_block(); it < m.items; it += waves) {
+    const size_t tile = it % m.tiles, cj = it / m.tiles, j = cj % m.cols, c = cj / m.cols, i0 = tile * RT;
+    const int nr = (int)(m.rows - i0 < (size_t)RT ? m.rows - i0 : (size_t)RT);
+    V acc[RT][C];
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+      for (int r = 0; r < C; ++r) acc[t][r] = 0;
+    int since = 0;
+    const size_t dia = m.trans_a ? 1 : m.inner;                         // A[i][k] -> A[i + 1][k] in storage order
+    for (size_t k = 0; k < m.inner; ++k) {
+      V b[C];
+      KN::template load<IO, true>(b, B, (c * m.inner + k) * m.cols + j, lane, md, p);
+      KN::K::forward(b, md, zf, lane);
+      const size_t ia0 = m.trans_a ? k * m.rows + i0 : i0 * m.inner + k;
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        if (t < nr) {
+          const size_t ia = ia0 + t * dia;
+          V a[C], pr[C];
+          if constexpr (HAT == 0) {
+            KN::template load<IO, false>(a, A, c * m.a_stride + ia, lane, md, p);
+            KN::K::forward(a, md, zf, lane);
+          } else if constexpr (HAT == 1) {
+            const uint32_t* h = reinterpret_cast<const uint32_t*>(A) + c * m.a_stride + ia * KN::N;
+#pragma unroll
+            for (int r = 0; r < C; ++r) a[r] = (V)h[r * 64 + lane];
+          } else {
+#pragma unroll
+            for (int r = 0; r < C; ++r) a[r] = (V)ah[ia * KN::N + r * 64 + lane];
+          }
+          KN::K::leafmul(pr, a, b, md, zf, lane);
+          KN::K::acc_add(acc[t], pr, md);
+        }
+      }
+      KN::K::acc_tick(acc, md, (V)m.r1, since);
+    }
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      if (t < nr) {
+        KN::K::acc_close(acc[t], md);
+        KN::K::inverse(acc[t], md, zi, lane);
+        KN::K::finish(acc[t], md, (V)(QB != 0 ? p.fin_fa : p.fin));
+        KN::template store<IO>(acc[t], out, (c * m.rows + i0 + t) * m.cols + j, lane);
+      }
+    }
   }
 }
 

@@ -1118,6 +1118,94 @@ psf_status psf_poly_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, 
   return ntt_mul_hat_dev(device, q, n, count, d_hat, hat_stride, d_b, d_out, io_bits, (hipStream_t)stream);
 }
 
+}  // extern "C"
+
+// ---- R_q matrix products (MatPolynomialRingZq * MatPolynomialRingZq: gpv_ring.rs:245, gadget_ring.rs:78 and :190-202, short_basis_ring.rs:183-198) ----
+// Every argument is checked here, before the first HIP call (plan_for allocates on the device, so it comes after).  hat: A given by its images.
+static constexpr size_t kMatpolyMaxInner = (size_t)1 << 20;
+static psf_status matpoly_check(uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride, bool hat,
+                                int trans_a, const void* d_b, const void* d_c, int io_bits) {
+  if (q <= 1 || q >= (1ull << 62) || n < 1 || n > 8192) return PSF_ERR_PARAM;
+  if (rows == 0 || inner == 0 || cols == 0 || (trans_a != 0 && trans_a != 1) || (io_bits != 16 && io_bits != 64)) return PSF_ERR_PARAM;
+  if (count && (!d_a || !d_b || !d_c)) return PSF_ERR_PARAM;
+  // byte ranges of A (all batches), B and C; any product that overflows size_t is a malformed call
+  const size_t w = io_bits / 8, wa = hat ? sizeof(uint32_t) : w;
+  size_t ri, ic, rc, a_one, a_all = 0, b_all, c_all;
+  if (__builtin_mul_overflow(rows, inner, &ri) || __builtin_mul_overflow(inner, cols, &ic) || __builtin_mul_overflow(rows, cols, &rc) ||
+      __builtin_mul_overflow(ri, n, &a_one) || __builtin_mul_overflow(ic, n, &ic) || __builtin_mul_overflow(rc, n, &rc) ||
+      __builtin_mul_overflow(ic, count, &b_all) || __builtin_mul_overflow(b_all, w, &b_all) || __builtin_mul_overflow(rc, count, &c_all) ||
+      __builtin_mul_overflow(c_all, w, &c_all) || __builtin_mul_overflow(a_one, wa, &a_one))
+    return PSF_ERR_PARAM;
+  if (count) {                                              // A: the last batch starts (count - 1) * a_stride polynomials (hat: words) in
+    size_t off;
+    if (__builtin_mul_overflow(count - 1, a_stride, &off) || __builtin_mul_overflow(off, hat ? sizeof(uint32_t) : w * n, &off) ||
+        __builtin_add_overflow(off, a_one, &a_all))
+      return PSF_ERR_PARAM;
+    const uintptr_t a0 = (uintptr_t)d_a, b0 = (uintptr_t)d_b, c0 = (uintptr_t)d_c;
+    if (a0 + a_all < a0 || b0 + b_all < b0 || c0 + c_all < c0) return PSF_ERR_PARAM;
+    if ((c0 < a0 + a_all && a0 < c0 + c_all) || (c0 < b0 + b_all && b0 < c0 + c_all)) return PSF_ERR_PARAM;   // the output overlaps an input
+  }
+  if (inner > kMatpolyMaxInner) return PSF_ERR_UNSUPPORTED;
+  const int route = ntt_route(q, n);                        // host tables only (device -1): no HIP call
+  if ((hat || io_bits == 16) && route != 2) return PSF_ERR_UNSUPPORTED;
+  if (io_bits == 16 && q >= (1ull << 14)) return PSF_ERR_UNSUPPORTED;     // 16-bit words: the wave kernels of q < 2^14
+  return PSF_OK;
+}
+
+static psf_status matpoly_dev_any(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
+                                  bool hat, int trans_a, const void* d_b, void* d_c, int io_bits, hipStream_t st) {
+  const psf_status chk = matpoly_check(q, n, count, rows, inner, cols, d_a, a_stride, hat, trans_a, d_b, d_c, io_bits);
+  if (chk != PSF_OK || count == 0) return chk;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
+  if (ntt_route(q, n) == 2) return ntt_matmul_dev(device, q, n, NttMatShape{count, rows, inner, cols, trans_a}, d_a, a_stride, hat, d_b, d_c, io_bits, st);
+  HIP_TRY(hipSetDevice(device));                            // every other q < 2^62 at 64-bit words: the exact schoolbook kernel
+  const uint64_t two64 = (uint64_t)((((u128)1) << 64) % q);
+  const size_t outs = count * rows * cols;
+  if (2 * n * sizeof(uint64_t) > 64 * 1024) {               // n > 4096: above the default LDS limit, raised once per process and device
+    static std::mutex mu; static std::vector<int> raised;
+    std::lock_guard<std::mutex> lk(mu);
+    if (std::find(raised.begin(), raised.end(), device) == raised.end()) {
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_matpoly_negacyclic), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      raised.push_back(device);
+    }
+  }
+  hipLaunchKernelGGL(k_matpoly_negacyclic, dim3((unsigned)(outs < 16384 ? outs : 16384)), dim3(256), 2 * n * sizeof(uint64_t), st, q, two64, (uint32_t)n,
+                     count, rows, inner, cols, (const uint64_t*)d_a, a_stride, trans_a, (const int64_t*)d_b, (uint64_t*)d_c);
+  HIP_TRY(hipGetLastError());
+  return PSF_OK;
+}
+
+extern "C" {
+
+psf_status psf_matpoly_mul_negacyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
+                                          int trans_a, const void* d_b, void* d_c, int io_bits, void* stream) {
+  return matpoly_dev_any(device, q, n, count, rows, inner, cols, d_a, a_stride, false, trans_a, d_b, d_c, io_bits, (hipStream_t)stream);
+}
+psf_status psf_matpoly_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint32_t* d_hat, size_t hat_stride,
+                                   int trans_a, const void* d_b, void* d_c, int io_bits, void* stream) {
+  return matpoly_dev_any(device, q, n, count, rows, inner, cols, d_hat, hat_stride, true, trans_a, d_b, d_c, io_bits, (hipStream_t)stream);
+}
+psf_status psf_matpoly_mul_negacyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, uint64_t* c) {
+  // the same checks on the host buffers (one batch), then device copies
+  const psf_status chk = matpoly_check(q, n, 1, rows, inner, cols, a, 0, false, 0, b, c, 64);
+  if (chk != PSF_OK) return chk;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
+  HIP_TRY(hipSetDevice(device));
+  const size_t na = rows * inner * n, nb = inner * cols * n, nc = rows * cols * n;
+  uint64_t *da = nullptr, *dc = nullptr; int64_t* db = nullptr;
+  auto done = [&](psf_status st) { hipFree(da); hipFree(db); hipFree(dc); return st; };
+  if (hipMalloc(&da, na * sizeof(uint64_t)) != hipSuccess || hipMalloc(&db, nb * sizeof(int64_t)) != hipSuccess ||
+      hipMalloc(&dc, nc * sizeof(uint64_t)) != hipSuccess) return done(PSF_ERR_HIP);
+  if (hipMemcpy(da, a, na * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(db, b, nb * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) return done(PSF_ERR_HIP);
+  const psf_status rc = matpoly_dev_any(device, q, n, 1, rows, inner, cols, da, 0, false, 0, db, dc, 64, nullptr);
+  if (rc != PSF_OK) return done(rc);
+  if (hipMemcpy(c, dc, nc * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
+  return done(PSF_OK);
+}
+
 // MatQ::gso (gpv.rs:88-91) as a free function: rows of an integer matrix -> their Gram-Schmidt vectors
 psf_status psf_gso_rows(int device, const int32_t* basis_t, size_t rows, size_t width, double* out) {
   if (!basis_t || !out || rows < 1 || width < 1) return PSF_ERR_PARAM;

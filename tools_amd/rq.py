@@ -1,0 +1,45 @@
+"""MatPolynomialRingZq * MatPolynomialRingZq over R_q = Z_q[X]/(X^n + 1) through the C ABI (psf_matpoly_mul_*, include/psf_mi355x.h).
+
+The reference multiplies matrices of polynomials at gpv_ring.rs:245 (a * sigma), gadget_ring.rs:78 (a_bar * r), gadget_ring.rs:190-202 (is_trapdoor)
+and short_basis_ring.rs:183-198 (is_basis).  A matrix of polynomials is an array (rows, cols, n): row-major, constant term first."""
+import ctypes as C
+
+import numpy as np
+
+from ._ffi import check, lib
+
+
+def _p(a, t):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+def matpoly_mul(A, B, q, device=0):
+    """A (rows, inner, n) times B (inner, cols, n) mod (X^n + 1, q) on the device; returns (rows, cols, n) uint64 in [0, q).
+    Signed entries are read as integers (reduced mod q), unsigned ones as residues."""
+    A, B = np.asarray(A), np.asarray(B)
+    if A.ndim != 3 or B.ndim != 3 or A.shape[1] != B.shape[0] or A.shape[2] != B.shape[2]:
+        raise ValueError(f"matpoly_mul: shapes {A.shape} x {B.shape}")
+    rows, inner, n = A.shape
+    cols = B.shape[1]
+    a = np.ascontiguousarray(np.mod(A.astype(np.int64), np.int64(q)).astype(np.uint64) if A.dtype.kind == "i" else A, dtype=np.uint64)
+    b = np.ascontiguousarray(np.mod(B, q).astype(np.int64) if B.dtype.kind == "u" else B, dtype=np.int64)
+    c = np.empty((rows, cols, n), dtype=np.uint64)
+    check(lib().psf_matpoly_mul_negacyclic(C.c_int(device), C.c_uint64(q), C.c_size_t(n), C.c_size_t(rows), C.c_size_t(inner), C.c_size_t(cols),
+                                           _p(a, C.c_uint64), _p(b, C.c_int64), _p(c, C.c_uint64)), "matpoly_mul")
+    return c
+
+
+def matpoly_mul_dev(d_a, d_b, d_c, q, n, count, rows, inner, cols, a_stride=0, trans_a=0, io_bits=64, device=0, stream=None):
+    """psf_matpoly_mul_negacyclic_dev on device buffers (raw pointers, e.g. torch `data_ptr()`), in `stream`, nothing allocated:
+    C[c] = op(A[c]) B[c] for c < count; a_stride in polynomials (0: one A for every batch), trans_a = 1: A stored inner x rows."""
+    check(lib().psf_matpoly_mul_negacyclic_dev(C.c_int(device), C.c_uint64(q), C.c_size_t(n), C.c_size_t(count), C.c_size_t(rows), C.c_size_t(inner),
+                                               C.c_size_t(cols), C.c_void_p(d_a), C.c_size_t(a_stride), C.c_int(trans_a), C.c_void_p(d_b), C.c_void_p(d_c),
+                                               C.c_int(io_bits), C.c_void_p(stream or 0)), "matpoly_mul_dev")
+
+
+def matpoly_mul_hat_dev(d_hat, d_b, d_c, q, n, count, rows, inner, cols, hat_stride=0, trans_a=0, io_bits=64, device=0, stream=None):
+    """psf_matpoly_mul_hat_dev: the same with A given by its images (psf_ntt_forward_dev, rows * inner of them per batch in A's storage order);
+    hat_stride in 32-bit words, 0: one set of images for every batch."""
+    check(lib().psf_matpoly_mul_hat_dev(C.c_int(device), C.c_uint64(q), C.c_size_t(n), C.c_size_t(count), C.c_size_t(rows), C.c_size_t(inner),
+                                        C.c_size_t(cols), C.c_void_p(d_hat), C.c_size_t(hat_stride), C.c_int(trans_a), C.c_void_p(d_b), C.c_void_p(d_c),
+                                        C.c_int(io_bits), C.c_void_p(stream or 0)), "matpoly_mul_hat_dev")
