@@ -167,10 +167,9 @@ struct psfp_handle {
 };
 
 // The compact copies follow the key without ever blocking a call: the first small call after a key change launches the two packers on its stream and goes on with
-// the full-size matrices; a later call finds their event complete and switches over.  PSF_SMALL_COMPACT=0: never.
+// the full-size matrices; a later call finds their event complete and switches over.
 static void ensure_small_copies(psfp_handle* h, hipStream_t st) {
-  static const bool on = [] { const char* e = psf_exp_env("PSF_SMALL_COMPACT"); return !e || std::atoi(e) != 0; }();
-  if (!on || (h->prm.flags & PSFP_FLAG_NO_PERTURB) || h->small_state >= 2) return;
+  if ((h->prm.flags & PSFP_FLAG_NO_PERTURB) || h->small_state >= 2) return;
   if (h->small_state == 1) {
     if (hipEventQuery(h->evSmall) == hipSuccess) h->small_state = *h->hR2bad ? 3 : 2;
     return;
@@ -191,11 +190,6 @@ static void ensure_small_copies(psfp_handle* h, hipStream_t st) {
   h->small_state = 1;
 }
 
-// PSF_RECOMBINE_PACKED=0: k_recombine_mfma_big fetches its R tiles from the row-major matrix as in rounds 2-4 (comparison arm; same bits)
-static bool rcb_packed() {
-  static const bool on = [] { const char* e = psf_exp_env("PSF_RECOMBINE_PACKED"); return !e || std::atoi(e) != 0; }();
-  return on;
-}
 // the tile-packed copy of R, rebuilt on `st` when R has changed since
 // (as the compact copies above: the stream that packs is ordered behind the pack by itself; every OTHER stream that reads dR8 before the pack is known to have
 // completed waits for its event -- back-to-back device-pointer calls on different non-blocking streams)
@@ -791,62 +785,6 @@ static void split_A(psfp_handle* h, hipStream_t st = nullptr) {
   hipLaunchKernelGGL(k_split_A, dim3(grid_for(h->n_pad * h->K_pad)), dim3(256), 0, st, h->dA, h->m, h->n, h->m, h->n_pad, h->K_pad, h->NA, h->dA8);
 }
 
-// out = (mode syndrome) U - A P  or  (mode f_a) A P for the columns [col0, col0 + ncols), with P (K x ld int32) first cut into digit planes
-static void launch_zq_mfma(psfp_handle* h, hipStream_t st, int mode, const int32_t* P, int8_t* P8, size_t ncols, const uint64_t* U, uint64_t* out, size_t ldo, size_t col0 = 0) {
-  const size_t ld = h->ld;
-  {  // a handful of preimages: A streamed once as 64-bit words (k_syndrome_small; PSF_SYNDROME_SMALL = largest batch it serves, 0: never)
-    size_t small_max = 1;                                             // measured at C3: 39 vs 48 us at one preimage, 52 vs 50 at two, 81 vs 50 at four (64-bit multiply-adds)
-    if (const char* e = psf_exp_env("PSF_SYNDROME_SMALL")) small_max = (size_t)std::atol(e);
-    if (small_max > 4) small_max = 4;
-    const int splits = (int)((h->m + SYN_KLEN - 1) / SYN_KLEN);
-    if (mode == ZQ_SYNDROME && P == h->dP && ncols <= small_max && splits <= h->zq_split_cap && splits <= 64) {
-      const int rows_per_wg = 16;
-      dim3 grid((unsigned)splits, (unsigned)((h->n + rows_per_wg - 1) / rows_per_wg));
-      ensure_small_copies(h, st);
-      if (h->dA32 && (h->small_state == 2 || h->small_state == 3)) {
-        if (ncols == 1) hipLaunchKernelGGL(k_syndrome_small32<1>, grid, dim3(512), 0, st, h->dA32, h->n, h->m, P, ld, ncols, h->q, rows_per_wg, h->dPart, h->n_pad, col0);
-        else if (ncols == 2) hipLaunchKernelGGL(k_syndrome_small32<2>, grid, dim3(512), 0, st, h->dA32, h->n, h->m, P, ld, ncols, h->q, rows_per_wg, h->dPart, h->n_pad, col0);
-        else hipLaunchKernelGGL(k_syndrome_small32<4>, grid, dim3(512), 0, st, h->dA32, h->n, h->m, P, ld, ncols, h->q, rows_per_wg, h->dPart, h->n_pad, col0);
-      } else
-      if (ncols == 1) hipLaunchKernelGGL(k_syndrome_small<1>, grid, dim3(512), 0, st, h->dA, h->n, h->m, P, ld, ncols, h->q, rows_per_wg, h->dPart, h->n_pad, col0);
-      else if (ncols == 2) hipLaunchKernelGGL(k_syndrome_small<2>, grid, dim3(512), 0, st, h->dA, h->n, h->m, P, ld, ncols, h->q, rows_per_wg, h->dPart, h->n_pad, col0);
-      else hipLaunchKernelGGL(k_syndrome_small<4>, grid, dim3(512), 0, st, h->dA, h->n, h->m, P, ld, ncols, h->q, rows_per_wg, h->dPart, h->n_pad, col0);
-      hipLaunchKernelGGL((k_zq_combine_wave<false>), dim3((unsigned)((h->n * ncols + 3) / 4)), dim3(256), 0, st, mode, h->dPart, splits, h->n, h->n_pad, ld, ncols, h->q, U, out, ldo, col0);
-      return;
-    }
-  }
-  size_t cw = round_up(ncols, 64);                                    // the product works on 64-column tiles
-  if (col0 + cw > ld) cw = ld - col0;
-  hipLaunchKernelGGL(k_split_P, dim3(grid_for(h->K_pad / 16 * cw, 256, 256 * 64)), dim3(256), 0, st, P, h->m, ld, h->K_pad / 16, P8, h->dFail, col0, cw);
-  {  // PSF_ZQ_PLANES3=1: the third digit plane of p is multiplied whether or not it holds anything (comparison arm; same residues)
-    static const bool force3 = [] { const char* e = psf_exp_env("PSF_ZQ_PLANES3"); return e && std::atoi(e) != 0; }();
-    if (force3) hipMemsetAsync(h->dFail + 2, 1, sizeof(int), st);
-  }
-  const int nks = (int)(h->K_pad / 64);
-  const int splits = zq_plan(h, ncols, h->zq_split_cap), zq_ks = (nks + splits - 1) / splits;
-  dim3 grid((unsigned)((ncols + 63) / 64), (unsigned)(h->n_pad / 64), (unsigned)splits);
-  int fold128 = zq_ks <= 32 ? 1 : 0;                                  // short splits (few preimages): one 128-bit fold per output; long ones: the per-class fold
-  if (const char* e = psf_exp_env("PSF_ZQ_FOLD128")) fold128 = std::atoi(e);
-  // a power-of-two modulus covered by the digits of A: the classes from NA on vanish mod q (pw[NA] = 0) and their digit pairs are skipped (PSF_ZQ_POW2=0: multiplied anyway)
-  bool pow2 = (h->q & (h->q - 1)) == 0 && h->NA <= 8 && h->zc.pw[h->NA] == 0;
-  if (const char* e = psf_exp_env("PSF_ZQ_POW2")) pow2 = pow2 && std::atoi(e) != 0;
-#define ZQL(NA_, F_, P_) hipLaunchKernelGGL((k_zq_mfma<NA_, F_, P_>), grid, dim3(256), 2 * (NA_ + 3) * 4096, st, h->dA8, h->n_pad, h->K_pad, P8, ld, zq_ks, h->zc, (int)h->wide, h->dPart, col0, h->dFail)
-#define ZQM(NA_)                                                                                                        \
-  case NA_:                                                                                                             \
-    if (fold128) { if (pow2) ZQL(NA_, true, true); else ZQL(NA_, true, false); }                                         \
-    else { if (pow2) ZQL(NA_, false, true); else ZQL(NA_, false, false); }                                               \
-    break;
-  switch (h->NA) { ZQM(1) ZQM(2) ZQM(3) ZQM(4) ZQM(5) ZQM(6) ZQM(7) ZQM(8) default: break; }
-  if (splits >= 16 && h->n * ncols <= 16384)      // a single call: few outputs, many splits -- one wave per output
-    hipLaunchKernelGGL((k_zq_combine_wave<false>), dim3((unsigned)((h->n * ncols + 3) / 4)), dim3(256), 0, st, mode, h->dPart, splits, h->n, h->n_pad, ld, ncols,
-                       h->q, U, out, ldo, col0);
-  else
-    hipLaunchKernelGGL(k_zq_combine, dim3(grid_for(h->n * ncols, 256, 256 * 32)), dim3(256), 0, st, mode, h->dPart, splits, h->n, h->n_pad, ld, ncols,
-                       h->q, U, out, ldo, col0);
-#undef ZQM
-#undef ZQL
-}
-
 // A_bar <- U(Z_q^{n x m_bar}), R <- PlusMinusOneZero, A = [A_bar | G - A_bar R] (gen_trapdoor, gadget_classical.rs:56-68, tag = I)
 // side: nullptr, or a non-blocking stream on which A = [A_bar | G - A_bar R] and its digit planes are computed while the caller goes on with R alone (the
 // factorisation of Sigma_2 needs R, not A: psfp_trap_gen); the caller synchronises `side` before anything reads A
@@ -1082,220 +1020,104 @@ psf_status psfp_export_gadget_basis(const psfp_handle* h, int64_t* Sk, double* g
 }
 
 // ---- the hot path -------------------------------------------------------------------------------------------
-// The stages behind the FP64 product (mp_perturbation.rs:316-335), each enqueued on `st` for the whole batch.
+// One samp_p call (mp_perturbation.rs:304-336): plan_samp_p makes every form choice (the experiment switches of this path are read there and in plan_zq only),
+// prepare_samp_p runs the side effects the plan names, each once, and the stage launchers enqueue what the plan says on `st`, each stage for the whole batch.
+static bool small_usable(const psfp_handle* h) { return h->small_state == 2 || h->small_state == 3; }
+static const auto by_cols = [](size_t b, auto k1, auto k2, auto k4) { return b == 1 ? k1 : b == 2 ? k2 : k4; };      // the <1, 2, 4> instantiation for b preimages
 
-// One or two preimages: rounding and the shares of A p in one launch behind the product (k_round_syndrome_small), summed by the syndrome stage
-// (rt: 16-row tiles of x per wave; two: 27 + 10 us against 34 + 14 with one, tools/fused_tail_ab.sh)
-struct FusedTail { bool on = false; int ntask = 0, rt = 2, bc = 0; };
+struct ZqPlan {      // out = (syndrome) U - A P  or  (f_a) A P over ncols preimages
+  enum Form : uint8_t { SMALL, SMALL32, MFMA } form = MFMA;      // A streamed once as 64-bit words / as its compact 32-bit copy; P's digit planes on the int8 matrix cores
+  int splits = 1, ks = 0;                                         // K splits (SMALL: of SYN_KLEN columns; MFMA: of ks K-steps)
+  bool fold128 = false, pow2 = false, wave_combine = true;        // k_zq_mfma's template arguments; the splits summed by one wave per output (k_zq_combine_wave)
+};
 
-// p_i <- D_{Z,r,x_i}
-static void round_stage(psfp_handle* h, hipStream_t st, uint64_t seed, uint64_t first_index, size_t B, const FusedTail& ft) {
-  const size_t ld = h->ld, m = h->m;
-  if (ft.on) {      // and every 16-row tile's share of A p
-    ScopedTimer t(h, st, "k_round+A p");
-    StreamGeom g;
-    g.ntile = ft.ntask; g.ncg = 1; g.ntask = ft.ntask; g.bc = ft.bc;
-    const StreamFuse fz{seed, first_index, m, h->szR, h->dP, ld, h->dA32T, h->n, h->q, h->dPartF, h->dFail};
-    const size_t row_hi2 = h->structured ? h->mb : h->M_pad;
-    if (ft.rt == 1) hipLaunchKernelGGL((k_round_syndrome_small<1>), dim3((unsigned)((g.ntask + 3) / 4)), dim3(256), 0, st, h->dX, ld, row_hi2, g, fz);
-    else hipLaunchKernelGGL((k_round_syndrome_small<2>), dim3((unsigned)((g.ntask + 3) / 4)), dim3(256), 0, st, h->dX, ld, row_hi2, g, fz);
-    return;
-  }
-  ScopedTimer t(h, st, "k_perturb_round");
-  const char* renv = psf_exp_env("PSF_ROUND");                 // "wave": the round-2 kernel (comparison arm; same bits)
-  if (h->szR.sh == 16 && !(renv && !std::strcmp(renv, "wave"))) {
-    uint32_t seg = prl_segment(m * B);
-    if (const char* e = psf_exp_env("PSF_PRL_SEG")) { const long v = std::atol(e); if (v >= 64 && v <= PRL_SEG && v % 64 == 0) seg = (uint32_t)v; }      // samples per wave (experiments)
-    const size_t waves = (m * B + seg - 1) / seg;
-    if (h->szF && !(renv && !std::strcmp(renv, "lean"))) {     // the table screen ("lean": the fp32 screen of rounds 3-4, comparison arm; same bits)
-      // a segment that is one row of the [coordinate][preimage] matrix never wraps: the sample's position is its offset (no division per sample)
-      uint32_t segt = seg;
-      if (B % 64 == 0 && B >= 1024 && B <= (size_t)PRL_SEG && (size_t)seg > B) segt = (uint32_t)B;      // (short rows: every workgroup loads the table, 0.14 against 0.09 ms at 64 preimages)
-      const size_t wavest = (m * B + segt - 1) / segt;
-      if ((size_t)segt == B)
-        hipLaunchKernelGGL(k_perturb_round_tab<true>, dim3((unsigned)((wavest + 3) / 4)), dim3(256), (size_t)h->szR.n_int * h->szF * sizeof(uint32_t), st, seed, first_index, m, B, ld,
-                           h->dX, h->szR, h->dP, h->dFail, segt, SzTable{h->dSzTab, h->szF, h->szR.n_int});
-      else
-        hipLaunchKernelGGL(k_perturb_round_tab<false>, dim3((unsigned)((wavest + 3) / 4)), dim3(256), (size_t)h->szR.n_int * h->szF * sizeof(uint32_t), st, seed, first_index, m, B, ld,
-                           h->dX, h->szR, h->dP, h->dFail, segt, SzTable{h->dSzTab, h->szF, h->szR.n_int});
-    } else
-    hipLaunchKernelGGL(k_perturb_round_lean, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, seed, first_index, m, B, ld, h->dX, h->szR, h->dP, h->dFail, seg);
-  } else {
-    const size_t waves = (m * B + PR_SEG - 1) / PR_SEG;
-    hipLaunchKernelGGL(k_perturb_round_wave, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, seed, first_index, m, B, ld, h->dX, h->szR, h->dP, h->dFail);
-  }
-}
-
-// mp_perturbation.rs:318 -- v = u - A p
-static void syndrome_stage(psfp_handle* h, hipStream_t st, size_t B, const uint64_t* d_u, const FusedTail& ft) {
-  const size_t ld = h->ld;
-  ScopedTimer t(h, st, "k_zq_matmul(syndrome)");
-  if (ft.on)      // the tasks of the product left their shares of A p in dPartF: summed and taken from u, one wave per output
-    hipLaunchKernelGGL((k_zq_combine_wave<true>), dim3((unsigned)((h->n * B + 3) / 4)), dim3(256), 0, st, ZQ_SYNDROME, h->dPartF, ft.ntask, h->n, h->n, (size_t)ft.bc, B, h->q, d_u, h->dV, ld, (size_t)0);
-  else launch_zq_mfma(h, st, ZQ_SYNDROME, h->dP, h->dP8, B, d_u, h->dV, ld);
-}
-
-// mp_perturbation.rs:321-326 -- z <- D_{Lambda_v(G), r sqrt(b^2+1)}
-static void gadget_stage(psfp_handle* h, hipStream_t st, uint64_t seed, uint64_t first_index, size_t B) {
-  const size_t ld = h->ld;
-  ScopedTimer t(h, st, "k_gadget");
-  const char* genv = psf_exp_env("PSF_GADGET_WAVE");            // max n B served by the one-wave-per-problem kernel (0: never)
-  const size_t wave_max = genv ? (size_t)std::atol(genv) : 2048;    // measured at C3 (n = 512): 45 / 44 / 55 us at 1 / 2 / 4 preimages (a row per problem: 58); 91 against 58 at 8
-  const char* genvq = psf_exp_env("PSF_GADGET_QUAD");          // max n B served by the four-lanes-per-problem kernel (0: never)
-  const size_t quad_max = genvq ? (size_t)std::atol(genvq) : 98304;      // measured at C3 (tools/gadget_mid_ab.py): 0.092 / 0.092 / 0.12 / 0.24 ms at 16 / 32 / 64 / 128 preimages against
-                                                                            // 0.12 / 0.18 / 0.33 / 0.35; 0.39 against 0.33 (queue kernel) at 256
-  const char* genvr = psf_exp_env("PSF_GADGET_ROW");           // max n B served by the sixteen-lanes-per-problem form of k_gadget_quad (0: never)
-  const size_t row_max = genvr ? (size_t)std::atol(genvr) : 10240;      // measured at C3 (tools/tail_ab.py k_gadget): 0.058 / 0.071 / 0.088 ms at 8 / 16 / 24 preimages against 0.091 (one
-                                                                          // wave per problem at 8, a quad per problem at 16 and 24); 0.107 against 0.091 at 32
-  if (h->gadget_queue && h->n * B <= wave_max) {               // a single call / a handful of preimages: the chain of k draws is the launch time
-    GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
-    hipLaunchKernelGGL(k_gadget_wave, dim3((unsigned)((h->n * B + 3) / 4)), dim3(256), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                       h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail);
-  } else if (h->gadget_queue && h->n * B <= row_max && h->k <= 64) {       // a few thousand problems: a DPP row per problem, one round per draw
-    GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
-    if (h->k <= 32)
-      hipLaunchKernelGGL((k_gadget_quad<2, 16>), dim3((unsigned)((h->n * B + 15) / 16)), dim3(256), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                         h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail);
-    else
-      hipLaunchKernelGGL((k_gadget_quad<4, 16>), dim3((unsigned)((h->n * B + 15) / 16)), dim3(256), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                         h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail);
-  } else if (h->gadget_queue && h->n * B <= quad_max && h->k <= 64) {      // tens to a few hundred preimages: a quad per problem
-    GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
-    if (h->k <= 32)
-      hipLaunchKernelGGL(k_gadget_quad<8>, dim3((unsigned)((h->n * B + 63) / 64)), dim3(256), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                         h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail);
-    else
-      hipLaunchKernelGGL(k_gadget_quad<16>, dim3((unsigned)((h->n * B + 63) / 64)), dim3(256), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q,
-                         h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail);
-  } else if (h->gadget_queue) {
-    GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
-    int P = gq_problems_for((uint32_t)h->k, h->n * B);
-    if (const char* e = psf_exp_env("PSF_GQ_P")) { const int v = std::atoi(e); if (v >= 1 && v <= 128 && (v & (v - 1)) == 0) P = v; }      // problems per wave (experiments)
-    const size_t per_wg = (size_t)GQ_WAVES * P;
-    if (P == 128)
-      hipLaunchKernelGGL(k_gadget_queue<true>, dim3((unsigned)((h->n * B + per_wg - 1) / per_wg)), dim3(256), gadget_queue_lds_bytes(h->k, P), st, seed,
-                         first_index, (uint32_t)h->n, (uint32_t)h->k, h->q, h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail, P);
-    else
-      hipLaunchKernelGGL(k_gadget_queue<false>, dim3((unsigned)((h->n * B + per_wg - 1) / per_wg)), dim3(256), gadget_queue_lds_bytes(h->k, P), st, seed,
-                         first_index, (uint32_t)h->n, (uint32_t)h->k, h->q, h->prm.gp.base, B, ld, h->dV, tq, h->dZlo, h->dZhi, h->dFail, P);
-  } else {
-    GadgetTables tb{h->dSk, h->dGso, h->dNorm2, h->dSz};
-    hipLaunchKernelGGL(k_gadget, dim3((unsigned)((B + 255) / 256), (unsigned)h->n), dim3(256), gadget_lds_bytes(h->k), st, seed, first_index,
-                       (uint32_t)h->n, (uint32_t)h->k, h->q, h->prm.gp.base, B, ld, h->dV, tb, h->dZlo, h->dZhi, h->dFail);
-  }
-}
-
-// mp_perturbation.rs:328-335 -- e = p + [R; I] z
-static void recombine_stage(psfp_handle* h, hipStream_t st, size_t B, int64_t* d_e) {
-  const size_t ld = h->ld, m = h->m;
-  ScopedTimer t(h, st, "k_recombine");
-  // a handful of preimages: R streamed once by one wave per row (PSF_RECOMBINE_SMALL = largest batch it serves, 0: never)
-  size_t small_max = 4;
-  if (const char* e = psf_exp_env("PSF_RECOMBINE_SMALL")) small_max = (size_t)std::atol(e);
-  if (small_max > 4) small_max = 4;
-  const size_t small_lds = 32 * (h->ldr / 16) * B;
-  if (B <= small_max && small_lds <= 150 * 1024) {
-    const unsigned wgs = (unsigned)std::min<size_t>((h->mb + 7) / 8, small_lds > 64 * 1024 ? 256 : 512);
-    ensure_small_copies(h, st);
-    if (h->small_state == 2) {
-      if (B == 1) hipLaunchKernelGGL(k_recombine_small2<1>, dim3(wgs), dim3(512), small_lds, st, h->dR2, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
-      else if (B == 2) hipLaunchKernelGGL(k_recombine_small2<2>, dim3(wgs), dim3(512), small_lds, st, h->dR2, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
-      else hipLaunchKernelGGL(k_recombine_small2<4>, dim3(wgs), dim3(512), small_lds, st, h->dR2, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
-      return;
-    }
-    if (B == 1) hipLaunchKernelGGL(k_recombine_small<1>, dim3(wgs), dim3(512), small_lds, st, h->dR, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
-    else if (B == 2) hipLaunchKernelGGL(k_recombine_small<2>, dim3(wgs), dim3(512), small_lds, st, h->dR, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
-    else hipLaunchKernelGGL(k_recombine_small<4>, dim3(wgs), dim3(512), small_lds, st, h->dR, h->ldr, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
-    return;
-  }
-  // 5 ... 448 preimages: 64 x 64 tiles over all of K, operands through an LDS-DMA ring, no atomics (k_recombine_wg); PSF_RECOMBINE_STREAM=0: the tiled kernel below
-  // (experiments build; same rows): 0.067 against 0.091 ms at 16, 0.081 against 0.155 at 64 preimages of C3 (tools/tail_ab.py)
-  size_t rs_max = 448;      // column groups of 64 preimages beyond 64 (blockIdx.y; R comes from L2 / the Infinity Cache for all but the first): 0.157 -> 0.107 ms at 65, 0.266 -> 0.115 at 128,
-                            // 0.247 -> 0.174 at 192, 0.238 -> 0.210 at 256, 0.353 -> 0.299 at 384; 0.248 -> 0.390 at 512 (the 256 x 256 tiles), 0.575 -> 0.729 at 1000 preimages
-  if (const char* e = psf_exp_env("PSF_RECOMBINE_STREAM")) rs_max = (size_t)std::min<long>(std::atol(e), 1024);
-  if (B <= rs_max && h->ldr % 128 == 0 && h->mb >= 64) {
-    const int nbf = B > 64 ? 4 : (int)((B + 15) / 16), nk2 = (int)(h->ldr / 128);
-    const unsigned ngy = (unsigned)((B + 63) / 64);
-    hipLaunchKernelGGL(k_recombine_bottom, dim3((unsigned)((B + 63) / 64), (unsigned)((h->w + 63) / 64)), dim3(256), 0, st, h->mb, h->w,
-                       h->dZlo, h->dZhi, ld, h->dP, B, d_e, m, 0);
-    const unsigned grid = (unsigned)((h->mb + 63) / 64);
-#define RW_GO(nb, nw) hipLaunchKernelGGL((k_recombine_wg<nb, nw>), dim3(grid, ngy), dim3(64 * nw), RW_LDS, st, h->dR, h->ldr, h->mb, nk2, h->dZlo, h->dZhi, ld, \
-                                     h->dFail, h->dP, B, d_e, m)
-    if (nbf == 1) RW_GO(1, 4); else if (nbf == 2) RW_GO(2, 8); else if (nbf == 3) RW_GO(3, 8); else RW_GO(4, 8);      // (four waves at 33 ... 64 preimages: 0.147 against 0.081 ms)
-#undef RW_GO
-    return;
-  }
-  // one digit plane (decided on the device by the gadget kernel): 256 x 256 tiles; otherwise, or for shapes the big tile does not fit, the 128 x 128 kernel
-  // (beyond 448 preimages also for batches that are not multiples of 256: the last tile is ragged -- its loads of z past the batch stay inside the planes or their slack,
-  // the stores are masked -- and still cheaper than the 128 x 128 kernel: 0.437 -> 0.29 ms at 704, 0.548 -> 0.30 at 832 preimages; PSF_RECOMBINE_RAGGED=0: multiples only)
-  const bool ragged_ok = !(psf_exp_env("PSF_RECOMBINE_RAGGED") && std::atoi(psf_exp_env("PSF_RECOMBINE_RAGGED")) == 0);
-  const bool big = (B % 256 == 0 || (B > rs_max && ragged_ok)) && h->mb >= 512 && (h->ldr / 64) % 2 == 0;
-  if (big) {
-    const unsigned nbx = (unsigned)((B + 255) / 256), nby = (unsigned)(h->mb_pad / 256);
-    const unsigned nsup = ((nbx + 3) / 4) * ((nby + 7) / 8);                 // super-tiles of 4 x 8 tiles, dealt to the XCDs in rounds of eight
-    ensure_R8(h, st);
-    hipLaunchKernelGGL(k_recombine_mfma_big, dim3(((nsup + 7) / 8) * 8 * 32), dim3(512), RCB_LDS, st, rcb_packed() ? h->dR8 : h->dR, rcb_packed() ? 1 : 0, h->ldr, h->mb,
-                       (int)(h->ldr / 128), h->dZlo, ld, h->dFail, h->dP, B, d_e, m, nbx, nby);
-  }
-  // few preimages: cut K over blockIdx.z (an even number of K steps each, at least 8) until ~2048 workgroups; the partial sums are added into a zeroed E
-  const unsigned tiles = (unsigned)((B + 127) / 128) * (unsigned)((h->mb + 127) / 128);
-  const int nks = (int)(h->ldr / 64);
-  int rsplits = 1, kps = nks;
-  if (!big && tiles < 1024 && nks >= 16) {
-    rsplits = (int)(2048 / tiles);
-    kps = (nks + rsplits - 1) / rsplits;
-    if (kps < 8) kps = 8;
-    kps += kps & 1;
-    rsplits = (nks + kps - 1) / kps;
-  }
-  const size_t bot_cols = rsplits > 1 && h->mb > h->w ? h->mb : h->w;
-  hipLaunchKernelGGL(k_recombine_bottom, dim3((unsigned)((B + 63) / 64), (unsigned)((bot_cols + 63) / 64)), dim3(256), 0, st, h->mb, h->w,
-                     h->dZlo, h->dZhi, ld, h->dP, B, d_e, m, rsplits > 1 ? 1 : 0);      // also zeroes the top part for the split-K form
-  hipLaunchKernelGGL(k_recombine_mfma, dim3((unsigned)((B + 127) / 128), (unsigned)((h->mb + 127) / 128), (unsigned)rsplits), dim3(256), RC_LDS, st, h->dR,
-                     h->ldr, h->mb, nks, h->dZlo, h->dZhi, ld, h->dFail, h->dP, B, d_e, m, big ? 1 : 0, kps);
-}
-
-// One samp_p pass over B rows (mp_perturbation.rs:304-336), everything in order on the caller's stream.
-static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_e, hipStream_t st) {
-  const size_t ld = h->ld, m = h->m;
-  const size_t nbj = h->nbj;
-  if (!h->keep_fail) hipMemsetAsync(h->dFail, 0, 4 * sizeof(int), st);      // [0] sampler failure, [1] some |z| > 127, [2] some |p| >= 2^15 (third digit plane of the syndrome product in use)
-  psf_status gate_rc = PSF_OK;
-  auto u_gate = [&]() { if (h->before_u) { auto f = std::move(h->before_u); h->before_u = nullptr; gate_rc = f(); } };
-  {  // small parameter sets, few preimages (the reference's own benchmarks: n = 8, one call; benches/psf.rs:51-66): the whole call in ONE launch, one
-     // workgroup per preimage (k_samp_p_small).  PSF_FUSED_MAX = largest batch it serves (0: never).  Stage exports need the intermediates: not here.
-    size_t fused_max = 64;
-    if (const char* e = psf_exp_env("PSF_FUSED_MAX")) fused_max = (size_t)std::atol(e);
-    if (!h->structured && !h->no_slice && h->gadget_queue && m <= (size_t)FS_MAX_M && h->n <= 64 && B <= fused_max) {
-      u_gate();
-      if (gate_rc != PSF_OK) return gate_rc;
-      ScopedTimer t(h, st, "k_samp_p_small");
-      GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
-      hipLaunchKernelGGL(k_samp_p_small, dim3((unsigned)B), dim3(FS_THREADS), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, (uint32_t)h->mb, h->q, h->two64,
-                         h->prm.gp.base, h->dLt, h->dA, h->dR, h->ldr, h->szR, tq, d_u, d_e, h->dFail);
-      HIP_TRY(hipGetLastError());
-      h->last_stream = st;
-      if (h->multi_t0 && h->multi_launched_ms < 0.0)
-        h->multi_launched_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - *h->multi_t0).count();
-      return PSF_OK;
+static ZqPlan plan_zq(const psfp_handle* h, size_t ncols, bool syndrome) {
+  ZqPlan z;
+  if (syndrome) {  // a handful of preimages: A streamed once as 64-bit words (k_syndrome_small; PSF_SYNDROME_SMALL = largest batch it serves, 0: never)
+    size_t small_max = 1;                                             // measured at C3: 39 vs 48 us at one preimage, 52 vs 50 at two, 81 vs 50 at four (64-bit multiply-adds)
+    if (const char* e = psf_exp_env("PSF_SYNDROME_SMALL")) small_max = std::min<size_t>((size_t)std::atol(e), 4);
+    z.splits = (int)((h->m + SYN_KLEN - 1) / SYN_KLEN);
+    if (ncols <= small_max && z.splits <= h->zq_split_cap && z.splits <= 64) {
+      z.form = h->dA32 && small_usable(h) ? ZqPlan::SMALL32 : ZqPlan::SMALL;
+      return z;
     }
   }
+  const int nks = (int)(h->K_pad / 64);
+  z.splits = zq_plan(h, ncols, h->zq_split_cap);
+  z.ks = (nks + z.splits - 1) / z.splits;
+  z.fold128 = z.ks <= 32;                                             // short splits (few preimages): one 128-bit fold per output; long ones: the per-class fold
+  if (const char* e = psf_exp_env("PSF_ZQ_FOLD128")) z.fold128 = std::atoi(e) != 0;
+  // a power-of-two modulus covered by the digits of A: the classes from NA on vanish mod q (pw[NA] = 0) and their digit pairs are skipped
+  z.pow2 = (h->q & (h->q - 1)) == 0 && h->NA <= 8 && h->zc.pw[h->NA] == 0;
+  z.wave_combine = z.splits >= 16 && h->n * ncols <= 16384;          // a single call: few outputs, many splits -- one wave per output
+  return z;
+}
+
+static void launch_zq(psfp_handle* h, hipStream_t st, const ZqPlan& z, int mode, const int32_t* P, int8_t* P8, size_t ncols, const uint64_t* U, uint64_t* out, size_t ldo) {
+  const size_t ld = h->ld;
+  if (z.form == ZqPlan::MFMA) {
+    const size_t cw = std::min(round_up(ncols, 64), ld);            // the product works on 64-column tiles
+    hipLaunchKernelGGL(k_split_P, dim3(grid_for(h->K_pad / 16 * cw, 256, 256 * 64)), dim3(256), 0, st, P, h->m, ld, h->K_pad / 16, P8, h->dFail, (size_t)0, cw);
+    const dim3 grid((unsigned)((ncols + 63) / 64), (unsigned)(h->n_pad / 64), (unsigned)z.splits);
+    auto fp = [&](auto k_tt, auto k_tf, auto k_ft, auto k_ff) { return z.fold128 ? (z.pow2 ? k_tt : k_tf) : (z.pow2 ? k_ft : k_ff); };      // <NA, fold128, pow2>
+#define ZQM(NA_) case NA_: hipLaunchKernelGGL(fp(k_zq_mfma<NA_, true, true>, k_zq_mfma<NA_, true, false>, k_zq_mfma<NA_, false, true>, k_zq_mfma<NA_, false, false>), grid, dim3(256), \
+                                              2 * (NA_ + 3) * 4096, st, h->dA8, h->n_pad, h->K_pad, P8, ld, z.ks, h->zc, (int)h->wide, h->dPart, (size_t)0, h->dFail); break;
+    switch (h->NA) { ZQM(1) ZQM(2) ZQM(3) ZQM(4) ZQM(5) ZQM(6) ZQM(7) ZQM(8) default: break; }
+#undef ZQM
+  } else {      // 16 rows per workgroup
+    const dim3 grid((unsigned)z.splits, (unsigned)((h->n + 15) / 16));
+    if (z.form == ZqPlan::SMALL32)
+      hipLaunchKernelGGL(by_cols(ncols, k_syndrome_small32<1>, k_syndrome_small32<2>, k_syndrome_small32<4>), grid, dim3(512), 0, st, h->dA32, h->n, h->m, P, ld, ncols, h->q, 16,
+                         h->dPart, h->n_pad, (size_t)0);
+    else
+      hipLaunchKernelGGL(by_cols(ncols, k_syndrome_small<1>, k_syndrome_small<2>, k_syndrome_small<4>), grid, dim3(512), 0, st, h->dA, h->n, h->m, P, ld, ncols, h->q, 16,
+                         h->dPart, h->n_pad, (size_t)0);
+  }
+  hipLaunchKernelGGL(z.wave_combine ? k_zq_combine_wave<false> : k_zq_combine, dim3(z.wave_combine ? (unsigned)((h->n * ncols + 3) / 4) : grid_for(h->n * ncols, 256, 256 * 32)),
+                     dim3(256), 0, st, mode, h->dPart, z.splits, h->n, h->n_pad, ld, ncols, h->q, U, out, ldo, (size_t)0);
+}
+
+struct SampPlan {      // every form choice of one samp_p call, with the launch parameters the choices fix
+  bool one_launch = false;                                   // k_samp_p_small: the whole call
+  int bc = 0; uint32_t ncf = 0, nseg = 0; size_t nwaves = 0;  // normals: dense stream of bc preimages; layout code (h->normals_ncf; 0 = chunk stream); positions per wave, waves
+  enum Product : uint8_t { TASKS, TILES64, TILES32, TILES96, BIG } product = BIG;      // x = sqrt(Sigma_2) d
+  int RT = 2, NB = 1, ncg = 1;                               // TASKS: RT 16-row tiles x NB fragments per wave; column groups of 16 NB preimages
+  bool compact = false; int GR = 8, GC = 4;                  // the streaming kernels read the compact normals stream; BIG: super-tile of an XCD's 32 resident workgroups
+  bool tail = false; int tail_ntask = 0, tail_rt = 2;        // rounding and the shares of A p in one launch behind the product (k_round_syndrome_small)
+  enum Round : uint8_t { ROUND_TAB, ROUND_TAB_ROW, ROUND_LEAN, ROUND_WAVE } round = ROUND_WAVE;
+  uint32_t seg = 0; size_t rwaves = 0;                       // rounding: samples per wave, waves
+  ZqPlan syn;                                                // v = u - A p without the fused tail
+  enum Gadget : uint8_t { G_WAVE, G_ROW, G_QUAD, G_QUEUE, G_LOCKSTEP } gadget = G_LOCKSTEP;
+  bool k32 = false; int gq_p = 0;                            // G_ROW, G_QUAD: the k <= 32 instantiation (else k <= 64); G_QUEUE: problems per wave
+  enum Recombine : uint8_t { R_SMALL, R_SMALL2, R_WG, R_TILES } recombine = R_TILES;
+  size_t rc_lds = 0; unsigned rc_wgs = 0; int nbf = 0;       // R_SMALL(2): LDS, workgroups; R_WG: fragments of 16 preimages per column group
+  bool rc_big = false; int rsplits = 1, kps = 0;             // R_TILES: the 256 x 256 tiles first; k_recombine_mfma over rsplits pieces of kps K-steps
+  bool small_copies = false, r8 = false;                     // prepare_samp_p: ensure_small_copies, ensure_R8
+};
+
+// The forms of a call of B preimages, from the handle as it stands at the start of the call (after ensure_batch)
+static SampPlan plan_samp_p(const psfp_handle* h, size_t B) {
+  SampPlan p;
+  const size_t m = h->m;
+  // small parameter sets, few preimages (the reference's own benchmarks: n = 8, one call; benches/psf.rs:51-66): the whole call in ONE launch, one
+  // workgroup per preimage (k_samp_p_small).  PSF_FUSED_MAX = largest batch it serves (0: never).  Stage exports need the intermediates: not here.
+  size_t fused_max = 64;
+  if (const char* e = psf_exp_env("PSF_FUSED_MAX")) fused_max = (size_t)std::atol(e);
+  p.one_launch = !h->structured && !h->no_slice && h->gadget_queue && m <= (size_t)FS_MAX_M && h->n <= 64 && B <= fused_max;
+  if (p.one_launch) return p;
   // Small batches (one samp_p call of the reference is ONE preimage, psf.rs:48-80): the streaming product, bound by reading the factor once, fed by
   // the compact normals stream.  PSF_TRMM_STREAM_MAX = largest batch it serves (0 switches it off); PSF_TRMM_STREAM_SHAPE = "RT,NB" forces a tile
-  // shape, PSF_COMPACT_D=0 the chunk-stream layout of the normals (experiments; same bits).
+  // shape (and turns the shared tiles off), PSF_COMPACT_D=0 the chunk-stream layout of the normals (experiments; same bits).
   // measured at C3: the streaming forms win up to 1472 preimages and again at 1537 ... 1728 (round 6, tools/tail_ab.py k_trmm_f64: k_trmm_f64_big costs 22.2-22.5 ms for anything
   // between 1025 and 1536 preimages and 27.2 up to 2048, the 64 x 64 tiles ~0.97 ms per round of 256 workgroups: 16.5 ms at 1152, 18.6 at 1280, 21.8 at 1472, 23.8 at 1600, 26.9 at 1792)
-  size_t stream_max = 1472;
-  bool stream = B <= stream_max || (B >= 1537 && B <= 1728) || (h->mL < 16384 && B <= 2048);      // (a small factor: k_trmm_f64_big is a fixed 0.23 ms at m = 932 whatever the batch, the
-                                                                                                  // tiles 0.04 ms at 1100 ... 2048 preimages: no reason to leave them before the stream's limit)
-  if (const char* e = psf_exp_env("PSF_TRMM_STREAM_MAX")) {
-    stream_max = (size_t)std::atol(e);
-    if (stream_max > 2048) stream_max = 2048;      // 128 column fragments: beyond, the over-read of the compact normals stream would leave TS_SLACK_DOUBLES
-    stream = B <= stream_max;
-  }
+  bool stream = B <= 1472 || (B >= 1537 && B <= 1728) || (h->mL < 16384 && B <= 2048);      // (a small factor: k_trmm_f64_big is a fixed 0.23 ms at m = 932 whatever the batch, the
+                                                                                            // tiles 0.04 ms at 1100 ... 2048 preimages: no reason to leave them before the stream's limit)
+  // (PSF_TRMM_STREAM_MAX <= 2048 = 128 column fragments: beyond, the over-read of the compact normals stream would leave TS_SLACK_DOUBLES)
+  if (const char* e = psf_exp_env("PSF_TRMM_STREAM_MAX")) stream = B <= std::min<size_t>((size_t)std::atol(e), 2048);
+  const char* shape = psf_exp_env("PSF_TRMM_STREAM_SHAPE");
   // tile shape per wave (RT 16-row tiles x NB fragments of 16 preimages) and workgroup form, from tools/probe_stream.hip at the C3 shape
   // (profiles/r04_probe_stream.log): <= 16 preimages the launch is bound by reading the factor, beyond that by the longest MFMA chain
-  int RT = 2, NB = B <= 16 ? 1 : B <= 64 ? 2 : 4;
+  p.NB = B <= 16 ? 1 : B <= 64 ? 2 : 4;
   // more than wg_min preimages: 64 x 64 tiles whose four waves share the operands through LDS (k_trmm_stream_wg); PSF_STREAM_WG=0 keeps the one-wave tasks,
   // PSF_STREAM_WG=<B> moves the threshold (experiments build; same bits)
   size_t wg_min = 33;
@@ -1312,141 +1134,316 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
   // a small factor (m < 16 384: few tile groups, the launch lasts one chain): the tiles' waves hold 2 x 2 MFMA tiles against the one-wave tasks' 2 x 4 -- half the chain
   // (m = 932: 0.035 against 0.061 ms at 97 ... 1024 preimages, whatever the parity): the tiles from 65 preimages on
   const bool small_factor = h->mL < 16384;
-  bool wg192 = stream && ((B > 128 && B <= 960 && (((B + 63) / 64) & 1) != 0) || B > 1088 || (small_factor && B > 64)) && !psf_exp_env("PSF_TRMM_STREAM_SHAPE");      // (1025-1088: 15.9 against 16.5)
+  bool wg192 = stream && ((B > 128 && B <= 960 && (((B + 63) / 64) & 1) != 0) || B > 1088 || (small_factor && B > 64)) && !shape;      // (1025-1088: 15.9 against 16.5)
   if (const char* e = psf_exp_env("PSF_STREAM_WG192")) {
     long lo = 0, hi = 0;
-    wg192 = std::sscanf(e, "%ld:%ld", &lo, &hi) == 2 && lo >= 65 && hi <= 2048 && stream && B >= (size_t)lo && B <= (size_t)hi && !psf_exp_env("PSF_TRMM_STREAM_SHAPE");
+    wg192 = std::sscanf(e, "%ld:%ld", &lo, &hi) == 2 && lo >= 65 && hi <= 2048 && stream && B >= (size_t)lo && B <= (size_t)hi && !shape;
   }
-  const bool wg = stream && ((B >= wg_min && B <= wg_max) || wg192) && !psf_exp_env("PSF_TRMM_STREAM_SHAPE");
+  const bool wg = stream && ((B >= wg_min && B <= wg_max) || wg192) && !shape;
   // 17 ... 32 preimages: 64 x 32 tiles of the same ring (k_trmm_stream_wg32); PSF_STREAM_WG32=0 keeps the one-wave tasks (experiments build; same bits)
-  const bool wg32 = stream && !wg && B >= 17 && B <= 32 && !psf_exp_env("PSF_TRMM_STREAM_SHAPE") && !(psf_exp_env("PSF_STREAM_WG32") && std::atoi(psf_exp_env("PSF_STREAM_WG32")) == 0);
+  const char* e32 = psf_exp_env("PSF_STREAM_WG32");
+  const bool wg32 = stream && !wg && B >= 17 && B <= 32 && !shape && !(e32 && std::atoi(e32) == 0);
   // 65 ... 96 preimages: the first 64 on the 64 x 64 tiles, the rest on the 64 x 32 tiles, two launches over one normals stream of six fragments (0.94 + 0.65 ms against 1.80 for
   // the one-wave tasks, which pay for 128 columns); PSF_STREAM_WG96=0 keeps those (experiments build; same bits)
-  const bool wg96 = stream && !wg && !small_factor && B >= 65 && B <= 96 && !psf_exp_env("PSF_TRMM_STREAM_SHAPE") && !(psf_exp_env("PSF_STREAM_WG96") && std::atoi(psf_exp_env("PSF_STREAM_WG96")) == 0);
-  if (wg) { RT = 2; NB = 4; }                    // column groups of 64 preimages (halves of four waves)
-  if (wg32 || wg96) { RT = 2; NB = 2; }          // (wg96: three column groups of 32 = the six fragments of the stream)
-  if (const char* e = psf_exp_env("PSF_TRMM_STREAM_SHAPE")) std::sscanf(e, "%d,%d", &RT, &NB);
-  if (!(NB == 1 || NB == 2 || NB == 4 || NB == 8)) NB = 1;
-  const int ncg = (int)((B + 16 * (size_t)NB - 1) / (16 * (size_t)NB));
-  bool compact = stream && !h->structured;
-  if (const char* e = psf_exp_env("PSF_COMPACT_D")) compact = compact && std::atoi(e) != 0;
+  const char* e96 = psf_exp_env("PSF_STREAM_WG96");
+  const bool wg96 = stream && !wg && !small_factor && B >= 65 && B <= 96 && !shape && !(e96 && std::atoi(e96) == 0);
+  if (wg) p.NB = 4;                    // column groups of 64 preimages (halves of four waves)
+  if (wg32 || wg96) p.NB = 2;          // (wg96: three column groups of 32 = the six fragments of the stream)
+  if (shape) std::sscanf(shape, "%d,%d", &p.RT, &p.NB);
+  if (!(p.NB == 1 || p.NB == 2 || p.NB == 4 || p.NB == 8)) p.NB = 1;
+  p.ncg = (int)((B + 16 * (size_t)p.NB - 1) / (16 * (size_t)p.NB));
+  const char* ecd = psf_exp_env("PSF_COMPACT_D");
+  p.compact = stream && !h->structured && !(ecd && std::atoi(ecd) == 0);
   // <= 16 preimages in one fragment: the dense stream of bc = 1, 2, 4, 8, 16 preimages (PSF_COMPACT_D=1 keeps the fragment stream)
-  int bc = 0;
-  if (compact && NB == 1 && ncg == 1 && !(psf_exp_env("PSF_COMPACT_D") && std::atoi(psf_exp_env("PSF_COMPACT_D")) == 1)) { bc = 1; while ((size_t)bc < B) bc <<= 1; }
-  const uint32_t ncf = bc ? 0x100u + (uint32_t)bc : compact ? (uint32_t)(ncg * NB) : 0u;      // layout code of the normals stream (k_normals_wave)
-  h->normals_ncf = ncf;
-  {  // mp_perturbation.rs:315 -- d <- N(0,1)^m
-    ScopedTimer t(h, st, "k_normals");
-    const size_t npos = bc ? h->nkb * 4 * 4 * (size_t)bc : ncf ? h->nkb * 4 * (size_t)ncf * 64 : nbj * h->nkb * TR_CHUNK;
-    uint32_t nseg = nr_segment(npos);
-    if (const char* e = psf_exp_env("PSF_NR_SEG")) { const long v = std::atol(e); if (v >= 64 && v <= NR_SEG && v % 64 == 0) nseg = (uint32_t)v; }      // positions per wave (experiments)
-    const size_t nwaves = (npos + nseg - 1) / nseg;
-    const NormalsFixed fx = h->structured ? NormalsFixed{h->mb, h->dD8, h->ldr * ld, ld, h->dX, h->h_const} : NormalsFixed{0, nullptr, 0, 0, nullptr, 0.0};
-    hipLaunchKernelGGL(k_normals_wave, dim3((unsigned)((nwaves + 3) / 4)), dim3(256), 0, st, seed, first_index, m, B, h->nkb, nbj, h->dDt, h->dFail, fx, ncf, nseg);
-  }
+  if (p.compact && p.NB == 1 && p.ncg == 1 && !(ecd && std::atoi(ecd) == 1)) { p.bc = 1; while ((size_t)p.bc < B) p.bc <<= 1; }
+  p.ncf = p.bc ? 0x100u + (uint32_t)p.bc : p.compact ? (uint32_t)(p.ncg * p.NB) : 0u;
+  const size_t npos = p.bc ? h->nkb * 4 * 4 * (size_t)p.bc : p.ncf ? h->nkb * 4 * (size_t)p.ncf * 64 : h->nbj * h->nkb * TR_CHUNK;
+  p.nseg = nr_segment(npos);
+  if (const char* e = psf_exp_env("PSF_NR_SEG")) { const long v = std::atol(e); if (v >= 64 && v <= NR_SEG && v % 64 == 0) p.nseg = (uint32_t)v; }      // positions per wave (experiments)
+  p.nwaves = (npos + p.nseg - 1) / p.nseg;
+  if (!stream) {                 // k_trmm_f64_big: one workgroup per CU, accumulators in AccVGPRs
+    p.product = SampPlan::BIG;   // super-tile of an XCD's 32 resident workgroups; PSF_TRMM_GR x PSF_TRMM_GC for experiments (product = 32)
+    // below 4096 preimages, or with a number of 128-column blocks that is not a multiple of four: 16 x 2 -- the grid is padded to whole super-columns, and 8 x 4 pays for up
+    // to three empty column blocks (round 6, tools/tail_ab.py: 34.9 -> 32.3 ms at 2176, 47.8 -> 44.1 at 3200, 27.2 -> 26.3 at 2048; 51.9 against 52.5 at 4096: 8 x 4 stays there)
+    if (B < 4096 || h->nbj % 4 != 0) { p.GR = 16; p.GC = 2; }
+    if (const char* e1 = psf_exp_env("PSF_TRMM_GR")) if (const char* e2 = psf_exp_env("PSF_TRMM_GC")) { p.GR = std::atoi(e1); p.GC = std::atoi(e2); }
+    if (p.GR < 1 || p.GC < 1 || p.GR * p.GC != 32) { p.GR = 8; p.GC = 4; }
+  } else p.product = wg96 ? SampPlan::TILES96 : wg32 ? SampPlan::TILES32 : wg ? SampPlan::TILES64 : SampPlan::TASKS;
   // One or two preimages: rounding and syndrome in ONE launch behind the product (k_round_syndrome_small, psf_stream_kernels.hpp) once the transposed compact copy
   // of A is there (built beside the first small calls after a key change, as the other compact copies)
-  FusedTail ft;
-  ft.bc = bc;
-  if (stream && bc && B <= 2 && RT == 2 && NB == 1 && !h->structured && h->szR.sh == 16 && !(h->prm.flags & PSFP_FLAG_NO_PERTURB)) {
-    ensure_small_copies(h, st);
+  if (stream && p.bc && B <= 2 && p.RT == 2 && p.NB == 1 && !h->structured && h->szR.sh == 16 && !(h->prm.flags & PSFP_FLAG_NO_PERTURB)) {
+    p.small_copies = true;
     const char* fe = psf_exp_env("PSF_FUSED_TAIL");
-    if (h->dA32T && (h->small_state == 2 || h->small_state == 3) && !(fe && std::atoi(fe) == 0)) {
-      if (const char* e = psf_exp_env("PSF_FUSED_RT")) ft.rt = std::atoi(e) == 1 ? 1 : 2;
-      ft.ntask = ((int)((h->mL + 15) / 16) + ft.rt - 1) / ft.rt;      // one wave per ft.rt 16-row tiles of x
-      const size_t need = (size_t)ft.ntask * h->n * 2;
-      if (need > h->partF_cap) {
-        hipFree(h->dPartF); h->dPartF = nullptr; h->partF_cap = 0;
-        if (hipMalloc(&h->dPartF, need * sizeof(uint64_t)) == hipSuccess) h->partF_cap = need; else (void)hipGetLastError();
-      }
-      ft.on = h->dPartF != nullptr;
+    if (h->dA32T && small_usable(h) && !(fe && std::atoi(fe) == 0)) {
+      // (tail_rt: 16-row tiles of x per wave; two: 27 + 10 us against 34 + 14 with one, tools/fused_tail_ab.sh)
+      if (const char* e = psf_exp_env("PSF_FUSED_RT")) p.tail_rt = std::atoi(e) == 1 ? 1 : 2;
+      p.tail_ntask = ((int)((h->mL + 15) / 16) + p.tail_rt - 1) / p.tail_rt;      // one wave per tail_rt 16-row tiles of x
+      p.tail = true;                                                               // (if prepare_samp_p finds room for its residues)
     }
   }
-  {  // x = sqrt(Sigma_2) d   (structured: the m_bar x m_bar block L_1 d_1; rows from m_bar on already hold x_bot = h d_2)
-    ScopedTimer t(h, st, "k_trmm_f64");
-    const size_t row_hi = h->structured ? h->mb : h->M_pad;
-    if (stream && wg96) {
-      StreamGeom g;
-      g.ntile = ((int)((h->mL + 15) / 16) + 3) / 4;
-      g.ncg = 1;
-      g.ntask = g.ntile;
-      g.bc = 0;
-      g.ncf = 6;
-      const unsigned grid = (unsigned)((g.ntask + 1) / 2);
-      g.cf_base = 0;
-      if (compact) hipLaunchKernelGGL((k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 1, 2>), dim3(grid), dim3(512), TSW_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
-      else hipLaunchKernelGGL((k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 0, 2>), dim3(grid), dim3(512), TSW_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
-      g.cf_base = 4;
-      if (compact) hipLaunchKernelGGL((k_trmm_stream_wg32<TSW_H, TSW_NBUF, 1>), dim3(grid), dim3(512), TSW32_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
-      else hipLaunchKernelGGL((k_trmm_stream_wg32<TSW_H, TSW_NBUF, 0>), dim3(grid), dim3(512), TSW32_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
+  p.r8 = h->structured;          // x_top -= g R d_2 reads the tile-packed R
+  // p_i <- D_{Z,r,x_i}
+  const char* renv = psf_exp_env("PSF_ROUND");                 // "wave": the round-2 kernel (comparison arm; same bits)
+  if (h->szR.sh == 16 && !(renv && !std::strcmp(renv, "wave"))) {
+    p.seg = prl_segment(m * B);
+    if (const char* e = psf_exp_env("PSF_PRL_SEG")) { const long v = std::atol(e); if (v >= 64 && v <= PRL_SEG && v % 64 == 0) p.seg = (uint32_t)v; }      // samples per wave (experiments)
+    p.round = SampPlan::ROUND_LEAN;
+    if (h->szF && !(renv && !std::strcmp(renv, "lean"))) {     // the table screen ("lean": the fp32 screen of rounds 3-4, comparison arm; same bits)
+      // a segment that is one row of the [coordinate][preimage] matrix never wraps: the sample's position is its offset (no division per sample)
+      if (B % 64 == 0 && B >= 1024 && B <= (size_t)PRL_SEG && (size_t)p.seg > B) p.seg = (uint32_t)B;      // (short rows: every workgroup loads the table, 0.14 against 0.09 ms at 64 preimages)
+      p.round = (size_t)p.seg == B ? SampPlan::ROUND_TAB_ROW : SampPlan::ROUND_TAB;
     }
-    else if (stream && wg32) {
-      StreamGeom g;
-      g.ntile = ((int)((h->mL + 15) / 16) + 3) / 4;
-      g.ncg = ncg;
-      g.ntask = g.ntile * g.ncg;
-      g.bc = 0;
-      const unsigned grid = (unsigned)((g.ntask + 1) / 2);
-      if (compact) hipLaunchKernelGGL((k_trmm_stream_wg32<TSW_H, TSW_NBUF, 1>), dim3(grid), dim3(512), TSW32_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
-      else hipLaunchKernelGGL((k_trmm_stream_wg32<TSW_H, TSW_NBUF, 0>), dim3(grid), dim3(512), TSW32_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
+    p.rwaves = (m * B + p.seg - 1) / p.seg;
+  } else p.rwaves = (m * B + PR_SEG - 1) / PR_SEG;
+  // mp_perturbation.rs:318 -- v = u - A p (the Z_q product unless the fused tail left the shares of A p)
+  p.syn = plan_zq(h, B, true);
+  p.small_copies |= p.syn.form != ZqPlan::MFMA;
+  // mp_perturbation.rs:321-326 -- z <- D_{Lambda_v(G), r sqrt(b^2+1)}
+  const size_t nB = h->n * B;
+  const char* genv = psf_exp_env("PSF_GADGET_WAVE");            // max n B served by the one-wave-per-problem kernel (0: never)
+  const size_t wave_max = genv ? (size_t)std::atol(genv) : 2048;    // measured at C3 (n = 512): 45 / 44 / 55 us at 1 / 2 / 4 preimages (a row per problem: 58); 91 against 58 at 8
+  const char* genvq = psf_exp_env("PSF_GADGET_QUAD");          // max n B served by the four-lanes-per-problem kernel (0: never)
+  const size_t quad_max = genvq ? (size_t)std::atol(genvq) : 98304;      // measured at C3 (tools/gadget_mid_ab.py): 0.092 / 0.092 / 0.12 / 0.24 ms at 16 / 32 / 64 / 128 preimages against
+                                                                            // 0.12 / 0.18 / 0.33 / 0.35; 0.39 against 0.33 (queue kernel) at 256
+  const char* genvr = psf_exp_env("PSF_GADGET_ROW");           // max n B served by the sixteen-lanes-per-problem form of k_gadget_quad (0: never)
+  const size_t row_max = genvr ? (size_t)std::atol(genvr) : 10240;      // measured at C3 (tools/tail_ab.py k_gadget): 0.058 / 0.071 / 0.088 ms at 8 / 16 / 24 preimages against 0.091 (one
+                                                                          // wave per problem at 8, a quad per problem at 16 and 24); 0.107 against 0.091 at 32
+  p.k32 = h->k <= 32;
+  if (!h->gadget_queue) p.gadget = SampPlan::G_LOCKSTEP;
+  else if (nB <= wave_max) p.gadget = SampPlan::G_WAVE;              // a single call / a handful of preimages: the chain of k draws is the launch time
+  else if (nB <= row_max && h->k <= 64) p.gadget = SampPlan::G_ROW;  // a few thousand problems: a DPP row per problem, one round per draw
+  else if (nB <= quad_max && h->k <= 64) p.gadget = SampPlan::G_QUAD;      // tens to a few hundred preimages: a quad per problem
+  else {
+    p.gadget = SampPlan::G_QUEUE;
+    p.gq_p = gq_problems_for((uint32_t)h->k, nB);
+    if (const char* e = psf_exp_env("PSF_GQ_P")) { const int v = std::atoi(e); if (v >= 1 && v <= 128 && (v & (v - 1)) == 0) p.gq_p = v; }      // problems per wave (experiments)
+  }
+  // mp_perturbation.rs:328-335 -- e = p + [R; I] z
+  // a handful of preimages: R streamed once by one wave per row (PSF_RECOMBINE_SMALL = largest batch it serves, 0: never)
+  size_t small_max = 4;
+  if (const char* e = psf_exp_env("PSF_RECOMBINE_SMALL")) small_max = std::min<size_t>((size_t)std::atol(e), 4);
+  p.rc_lds = 32 * (h->ldr / 16) * B;
+  // 5 ... 448 preimages: 64 x 64 tiles over all of K, operands through an LDS-DMA ring, no atomics (k_recombine_wg); PSF_RECOMBINE_STREAM=0: the tiled kernel below
+  // (experiments build; same rows): 0.067 against 0.091 ms at 16, 0.081 against 0.155 at 64 preimages of C3 (tools/tail_ab.py)
+  size_t rs_max = 448;      // column groups of 64 preimages beyond 64 (blockIdx.y; R comes from L2 / the Infinity Cache for all but the first): 0.157 -> 0.107 ms at 65, 0.266 -> 0.115 at 128,
+                            // 0.247 -> 0.174 at 192, 0.238 -> 0.210 at 256, 0.353 -> 0.299 at 384; 0.248 -> 0.390 at 512 (the 256 x 256 tiles), 0.575 -> 0.729 at 1000 preimages
+  if (const char* e = psf_exp_env("PSF_RECOMBINE_STREAM")) rs_max = (size_t)std::min<long>(std::atol(e), 1024);
+  if (B <= small_max && p.rc_lds <= 150 * 1024) {
+    p.recombine = h->small_state == 2 ? SampPlan::R_SMALL2 : SampPlan::R_SMALL;
+    p.rc_wgs = (unsigned)std::min<size_t>((h->mb + 7) / 8, p.rc_lds > 64 * 1024 ? 256 : 512);
+    p.small_copies = true;
+  } else if (B <= rs_max && h->ldr % 128 == 0 && h->mb >= 64) {
+    p.recombine = SampPlan::R_WG;
+    p.nbf = B > 64 ? 4 : (int)((B + 15) / 16);      // (four waves at 33 ... 64 preimages: 0.147 against 0.081 ms)
+  } else {
+    // one digit plane (decided on the device by the gadget kernel): 256 x 256 tiles; otherwise, or for shapes the big tile does not fit, the 128 x 128 kernel
+    // (beyond 448 preimages also for batches that are not multiples of 256: the last tile is ragged -- its loads of z past the batch stay inside the planes or their slack,
+    // the stores are masked -- and still cheaper than the 128 x 128 kernel: 0.437 -> 0.29 ms at 704, 0.548 -> 0.30 at 832 preimages)
+    p.recombine = SampPlan::R_TILES;
+    p.rc_big = (B % 256 == 0 || B > rs_max) && h->mb >= 512 && (h->ldr / 64) % 2 == 0;
+    p.r8 = p.r8 || p.rc_big;
+    // few preimages: cut K over blockIdx.z (an even number of K steps each, at least 8) until ~2048 workgroups; the partial sums are added into a zeroed E
+    const unsigned tiles = (unsigned)((B + 127) / 128) * (unsigned)((h->mb + 127) / 128);
+    const int nks = (int)(h->ldr / 64);
+    p.kps = nks;
+    if (!p.rc_big && tiles < 1024 && nks >= 16) {
+      const int splits = (int)(2048 / tiles);
+      p.kps = std::max((nks + splits - 1) / splits, 8);
+      p.kps += p.kps & 1;
+      p.rsplits = (nks + p.kps - 1) / p.kps;
     }
-    else if (stream && wg) {
-      StreamGeom g;
-      g.ntile = ((int)((h->mL + 15) / 16) + 3) / 4;
-      g.ncg = ncg;
-      g.ntask = g.ntile * g.ncg;
-      g.bc = 0;
-      const unsigned nwg = (unsigned)((g.ntask + 1) / 2);
-      // column groups of 64 preimages: one workgroup of 2 x 4 waves per CU, rounds of four k-steps; several groups: those of a tile group on one XCD
-      const unsigned grid64 = ncg > 1 ? 8 * ((nwg + 7) / 8) : nwg;
-      if (compact) hipLaunchKernelGGL((k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 1, 2>), dim3(grid64), dim3(512), TSW_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
-      else hipLaunchKernelGGL((k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 0, 2>), dim3(grid64), dim3(512), TSW_LDS, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
+  }
+  return p;
+}
+
+// The side effects a plan names, each once per call: the compact copies (built beside the call; a later call's plan finds them usable), room for the fused
+// tail's partial residues, the tile-packed R
+static void prepare_samp_p(psfp_handle* h, hipStream_t st, SampPlan& p) {
+  if (p.small_copies) ensure_small_copies(h, st);
+  if (p.tail) {
+    const size_t need = (size_t)p.tail_ntask * h->n * 2;
+    if (need > h->partF_cap) {
+      hipFree(h->dPartF); h->dPartF = nullptr; h->partF_cap = 0;
+      if (hipMalloc(&h->dPartF, need * sizeof(uint64_t)) == hipSuccess) h->partF_cap = need; else (void)hipGetLastError();
     }
-    else if (stream) {
-      const int ntile16 = (int)((h->mL + 15) / 16);
-      auto go = [&](auto kern, int rt, int half) {
-        StreamGeom g;
-        g.ntile = (ntile16 + rt - 1) / rt;
-        g.ncg = ncg;
-        g.ntask = g.ntile * g.ncg;
-        g.bc = bc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((g.ntask + 2 * half - 1) / (2 * half))), dim3(128 * half), 0, st, h->dLt, h->dDt, h->dX, g, h->nkb, ld, row_hi);
-      };
-#define TS_GO(rt, nb, pd, half) { if (compact) go(k_trmm_stream<rt, nb, pd, half, 1>, rt, half); else go(k_trmm_stream<rt, nb, pd, half, 0>, rt, half); }
-      if (bc && RT == 2 && NB == 1) go(k_trmm_stream<2, 1, 12, 2, 2>, 2, 2);
-      else if (bc && NB == 1) go(k_trmm_stream<1, 1, 8, 4, 2>, 1, 4);
-      else if (RT == 2 && NB == 1) TS_GO(2, 1, 12, 2)
-      else if (RT == 2 && NB == 2 && B <= 32) TS_GO(2, 2, 8, 2)
-      else if (RT == 2 && NB == 2) TS_GO(2, 2, 16, 4)
-      else if (RT == 2 && NB == 4) TS_GO(2, 4, 8, 4)
-      else if (RT == 4 && NB == 2) TS_GO(4, 2, 10, 4)
-      else if (RT == 1 && NB == 8) TS_GO(1, 8, 8, 4)
-      else if (RT == 1 && NB == 4) TS_GO(1, 4, 8, 4)
-      else if (RT == 1 && NB == 2) TS_GO(1, 2, 8, 4)
-      else TS_GO(1, 1, 8, 4)
+    p.tail = h->dPartF != nullptr;      // (no room: the syndrome stage takes the Z_q product)
+  }
+  if (p.r8) ensure_R8(h, st);
+}
+
+// mp_perturbation.rs:315 -- d <- N(0,1)^m
+static void normals_stage(psfp_handle* h, hipStream_t st, const SampPlan& p, uint64_t seed, uint64_t first_index, size_t B) {
+  ScopedTimer t(h, st, "k_normals");
+  const NormalsFixed fx = h->structured ? NormalsFixed{h->mb, h->dD8, h->ldr * h->ld, h->ld, h->dX, h->h_const} : NormalsFixed{0, nullptr, 0, 0, nullptr, 0.0};
+  hipLaunchKernelGGL(k_normals_wave, dim3((unsigned)((p.nwaves + 3) / 4)), dim3(256), 0, st, seed, first_index, h->m, B, h->nkb, h->nbj, h->dDt, h->dFail, fx, p.ncf, p.nseg);
+}
+
+// x = sqrt(Sigma_2) d   (structured: the m_bar x m_bar block L_1 d_1; rows from m_bar on already hold x_bot = h d_2)
+static void product_stage(psfp_handle* h, hipStream_t st, const SampPlan& p, size_t B) {
+  ScopedTimer t(h, st, "k_trmm_f64");
+  const size_t row_hi = h->structured ? h->mb : h->M_pad;
+  if (p.product == SampPlan::BIG) {      // k_trmm_f64_big: one workgroup per CU, accumulators in AccVGPRs
+    hipLaunchKernelGGL(k_trmm_f64_big, dim3(tr_grid_size(((int)h->nbiL + 1) / 2, (int)h->nbj, p.GR, p.GC)), dim3(256), 0, st, h->dLt, h->dDt, h->dX, (int)h->nbiL, (int)h->nbj,
+                       h->nkb, h->ld, p.GR, p.GC, row_hi);
+    return;
+  }
+  auto geom = [&](int rt, int ncg, int bc) { StreamGeom g; g.ntile = ((int)((h->mL + 15) / 16) + rt - 1) / rt; g.ncg = ncg; g.ntask = g.ntile * ncg; g.bc = bc; return g; };
+  auto go = [&](auto kern, const StreamGeom& g, unsigned grid, unsigned block, size_t lds) { hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, st, h->dLt, h->dDt, h->dX, g, h->nkb, h->ld, row_hi); };
+  auto cd = [&](auto k0, auto k1) { return p.compact ? k1 : k0; };      // the chunk stream / the compact stream of the normals
+  const auto wg64 = cd(k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 0, 2>, k_trmm_stream_wg<TSW64_H, TSW64_NBUF, 1, 2>);
+  const auto wg32 = cd(k_trmm_stream_wg32<TSW_H, TSW_NBUF, 0>, k_trmm_stream_wg32<TSW_H, TSW_NBUF, 1>);
+  StreamGeom g = geom(4, p.product == SampPlan::TILES96 ? 1 : p.ncg, 0);      // the tiles: 64 rows, a workgroup per pair of tasks
+  const unsigned nwg = (unsigned)((g.ntask + 1) / 2);
+  if (p.product == SampPlan::TILES96) {      // two launches over one stream of six fragments: columns 0-63 on the 64 x 64 tiles, 64-95 on the 64 x 32 tiles
+    g.ncf = 6;
+    go(wg64, g, nwg, 512, TSW_LDS);
+    g.cf_base = 4;
+    go(wg32, g, nwg, 512, TSW32_LDS);
+  } else if (p.product == SampPlan::TILES32) go(wg32, g, nwg, 512, TSW32_LDS);
+  // column groups of 64 preimages: one workgroup of 2 x 4 waves per CU, rounds of four k-steps; several groups: those of a tile group on one XCD
+  else if (p.product == SampPlan::TILES64) go(wg64, g, p.ncg > 1 ? 8 * ((nwg + 7) / 8) : nwg, 512, TSW_LDS);
+  else {
+    auto ts = [&](auto kern, int rt, int half) { const StreamGeom gt = geom(rt, p.ncg, p.bc); go(kern, gt, (unsigned)((gt.ntask + 2 * half - 1) / (2 * half)), 128 * half, 0); };
+#define TS_GO(rt, nb, pd, half) ts(cd(k_trmm_stream<rt, nb, pd, half, 0>, k_trmm_stream<rt, nb, pd, half, 1>), rt, half)
+    if (p.bc && p.RT == 2 && p.NB == 1) ts(k_trmm_stream<2, 1, 12, 2, 2>, 2, 2);
+    else if (p.bc && p.NB == 1) ts(k_trmm_stream<1, 1, 8, 4, 2>, 1, 4);
+    else if (p.RT == 2 && p.NB == 1) TS_GO(2, 1, 12, 2);
+    else if (p.RT == 2 && p.NB == 2 && B <= 32) TS_GO(2, 2, 8, 2);
+    else if (p.RT == 2 && p.NB == 2) TS_GO(2, 2, 16, 4);
+    else if (p.RT == 2 && p.NB == 4) TS_GO(2, 4, 8, 4);
+    else if (p.RT == 4 && p.NB == 2) TS_GO(4, 2, 10, 4);
+    else if (p.RT == 1 && p.NB == 8) TS_GO(1, 8, 8, 4);
+    else if (p.RT == 1 && p.NB == 4) TS_GO(1, 4, 8, 4);
+    else if (p.RT == 1 && p.NB == 2) TS_GO(1, 2, 8, 4);
+    else TS_GO(1, 1, 8, 4);
 #undef TS_GO
-    }
-    else {                   // k_trmm_f64_big: one workgroup per CU, accumulators in AccVGPRs
-      int GR = 8, GC = 4;                                     // super-tile of an XCD's 32 resident workgroups; PSF_TRMM_GR x PSF_TRMM_GC for experiments (product = 32)
-      // below 4096 preimages, or with a number of 128-column blocks that is not a multiple of four: 16 x 2 -- the grid is padded to whole super-columns, and 8 x 4 pays for up
-      // to three empty column blocks (round 6, tools/tail_ab.py: 34.9 -> 32.3 ms at 2176, 47.8 -> 44.1 at 3200, 27.2 -> 26.3 at 2048; 51.9 against 52.5 at 4096: 8 x 4 stays there)
-      if (B < 4096 || nbj % 4 != 0) { GR = 16; GC = 2; }
-      if (const char* e1 = psf_exp_env("PSF_TRMM_GR")) if (const char* e2 = psf_exp_env("PSF_TRMM_GC")) { GR = std::atoi(e1); GC = std::atoi(e2); }
-      if (GR < 1 || GC < 1 || GR * GC != 32) { GR = 8; GC = 4; }
-      hipLaunchKernelGGL(k_trmm_f64_big, dim3(tr_grid_size(((int)h->nbiL + 1) / 2, (int)nbj, GR, GC)), dim3(256), 0, st, h->dLt, h->dDt, h->dX, (int)h->nbiL, (int)nbj, h->nkb, ld, GR, GC, row_hi);
-    }
   }
-  if (h->structured) {  // x_top -= g R d_2 (exact integer sum on the int8 matrix cores)
-    ensure_R8(h, st);
-    ScopedTimer t(h, st, "k_rd2_mfma");
-    hipLaunchKernelGGL(k_rd2_mfma, dim3((unsigned)(ld / 64), (unsigned)(round_up(h->mb, 64) / 64)), dim3(256), 3 * (1 + kFixPlanes) * 4096, st, h->dR8, h->ldr, h->dD8, h->ldr * ld, ld,
-                       h->mb, h->g_const, h->dX);
+}
+
+// p_i <- D_{Z,r,x_i}
+static void round_stage(psfp_handle* h, hipStream_t st, const SampPlan& p, uint64_t seed, uint64_t first_index, size_t B) {
+  const size_t ld = h->ld, m = h->m;
+  if (p.tail) {      // and every 16-row tile's share of A p
+    ScopedTimer t(h, st, "k_round+A p");
+    StreamGeom g;
+    g.ntile = p.tail_ntask; g.ncg = 1; g.ntask = p.tail_ntask; g.bc = p.bc;
+    const StreamFuse fz{seed, first_index, m, h->szR, h->dP, ld, h->dA32T, h->n, h->q, h->dPartF, h->dFail};
+    hipLaunchKernelGGL(p.tail_rt == 1 ? k_round_syndrome_small<1> : k_round_syndrome_small<2>, dim3((unsigned)((g.ntask + 3) / 4)), dim3(256), 0, st, h->dX, ld,
+                       h->structured ? h->mb : h->M_pad, g, fz);
+    return;
   }
-  round_stage(h, st, seed, first_index, B, ft);
-  u_gate();                                                      // (host path: u reaches the device now)
-  syndrome_stage(h, st, B, d_u, ft);
-  gadget_stage(h, st, seed, first_index, B);
-  recombine_stage(h, st, B, d_e);
+  ScopedTimer t(h, st, "k_perturb_round");
+  const dim3 grid((unsigned)((p.rwaves + 3) / 4));
+  switch (p.round) {
+    case SampPlan::ROUND_TAB:
+    case SampPlan::ROUND_TAB_ROW:
+      hipLaunchKernelGGL(p.round == SampPlan::ROUND_TAB_ROW ? k_perturb_round_tab<true> : k_perturb_round_tab<false>, grid, dim3(256), (size_t)h->szR.n_int * h->szF * sizeof(uint32_t),
+                         st, seed, first_index, m, B, ld, h->dX, h->szR, h->dP, h->dFail, p.seg, SzTable{h->dSzTab, h->szF, h->szR.n_int});
+      break;
+    case SampPlan::ROUND_LEAN:
+      hipLaunchKernelGGL(k_perturb_round_lean, grid, dim3(256), 0, st, seed, first_index, m, B, ld, h->dX, h->szR, h->dP, h->dFail, p.seg);
+      break;
+    case SampPlan::ROUND_WAVE:
+      hipLaunchKernelGGL(k_perturb_round_wave, grid, dim3(256), 0, st, seed, first_index, m, B, ld, h->dX, h->szR, h->dP, h->dFail);
+      break;
+  }
+}
+
+// mp_perturbation.rs:318 -- v = u - A p
+static void syndrome_stage(psfp_handle* h, hipStream_t st, const SampPlan& p, size_t B, const uint64_t* d_u) {
+  ScopedTimer t(h, st, "k_zq_matmul(syndrome)");
+  if (p.tail)      // the tasks of the product left their shares of A p in dPartF: summed and taken from u, one wave per output
+    hipLaunchKernelGGL((k_zq_combine_wave<true>), dim3((unsigned)((h->n * B + 3) / 4)), dim3(256), 0, st, ZQ_SYNDROME, h->dPartF, p.tail_ntask, h->n, h->n, (size_t)p.bc, B, h->q, d_u, h->dV, h->ld, (size_t)0);
+  else launch_zq(h, st, p.syn, ZQ_SYNDROME, h->dP, h->dP8, B, d_u, h->dV, h->ld);
+}
+
+// mp_perturbation.rs:321-326 -- z <- D_{Lambda_v(G), r sqrt(b^2+1)}
+static void gadget_stage(psfp_handle* h, hipStream_t st, const SampPlan& p, uint64_t seed, uint64_t first_index, size_t B) {
+  const size_t ld = h->ld, nB = h->n * B;
+  ScopedTimer t(h, st, "k_gadget");
+  const GadgetTablesQ tq{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng};
+  auto go = [&](auto kern, dim3 grid, size_t lds, auto tables, auto... extra) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, h->q, h->prm.gp.base, B, ld, h->dV, tables, h->dZlo, h->dZhi, h->dFail, extra...);
+  };
+  switch (p.gadget) {
+    case SampPlan::G_WAVE: go(k_gadget_wave, dim3((unsigned)((nB + 3) / 4)), 0, tq); break;
+    case SampPlan::G_ROW: go(p.k32 ? k_gadget_quad<2, 16> : k_gadget_quad<4, 16>, dim3((unsigned)((nB + 15) / 16)), 0, tq); break;
+    case SampPlan::G_QUAD: go(p.k32 ? k_gadget_quad<8> : k_gadget_quad<16>, dim3((unsigned)((nB + 63) / 64)), 0, tq); break;
+    case SampPlan::G_QUEUE:      // GQ_WAVES * gq_p problems per workgroup
+      go(p.gq_p == 128 ? k_gadget_queue<true> : k_gadget_queue<false>, dim3((unsigned)((nB + (size_t)GQ_WAVES * p.gq_p - 1) / ((size_t)GQ_WAVES * p.gq_p))),
+         gadget_queue_lds_bytes(h->k, p.gq_p), tq, p.gq_p);
+      break;
+    case SampPlan::G_LOCKSTEP:
+      go(k_gadget, dim3((unsigned)((B + 255) / 256), (unsigned)h->n), gadget_lds_bytes(h->k), GadgetTables{h->dSk, h->dGso, h->dNorm2, h->dSz});
+      break;
+  }
+}
+
+// mp_perturbation.rs:328-335 -- e = p + [R; I] z
+static void recombine_stage(psfp_handle* h, hipStream_t st, const SampPlan& p, size_t B, int64_t* d_e) {
+  const size_t ld = h->ld, m = h->m;
+  ScopedTimer t(h, st, "k_recombine");
+  auto bottom = [&](size_t cols, int zero_top) {      // the rows from m_bar on (z itself); zero_top: also zero the top part for the split-K form
+    hipLaunchKernelGGL(k_recombine_bottom, dim3((unsigned)((B + 63) / 64), (unsigned)((cols + 63) / 64)), dim3(256), 0, st, h->mb, h->w, h->dZlo, h->dZhi, ld, h->dP, B, d_e, m, zero_top);
+  };
+  switch (p.recombine) {
+    case SampPlan::R_SMALL2:
+      hipLaunchKernelGGL(by_cols(B, k_recombine_small2<1>, k_recombine_small2<2>, k_recombine_small2<4>), dim3(p.rc_wgs), dim3(512), p.rc_lds, st, h->dR2, h->ldr, h->mb, h->w,
+                         h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
+      break;
+    case SampPlan::R_SMALL:
+      hipLaunchKernelGGL(by_cols(B, k_recombine_small<1>, k_recombine_small<2>, k_recombine_small<4>), dim3(p.rc_wgs), dim3(512), p.rc_lds, st, h->dR, h->ldr, h->mb, h->w,
+                         h->dZlo, h->dZhi, ld, h->dP, B, d_e, m);
+      break;
+    case SampPlan::R_WG: {
+      bottom(h->w, 0);
+      hipLaunchKernelGGL((p.nbf == 1 ? k_recombine_wg<1, 4> : p.nbf == 2 ? k_recombine_wg<2, 8> : p.nbf == 3 ? k_recombine_wg<3, 8> : k_recombine_wg<4, 8>),
+                         dim3((unsigned)((h->mb + 63) / 64), (unsigned)((B + 63) / 64)), dim3(64 * (p.nbf == 1 ? 4 : 8)), RW_LDS, st, h->dR, h->ldr, h->mb, (int)(h->ldr / 128),
+                         h->dZlo, h->dZhi, ld, h->dFail, h->dP, B, d_e, m);
+      break;
+    }
+    case SampPlan::R_TILES:
+      if (p.rc_big) {
+        const unsigned nbx = (unsigned)((B + 255) / 256), nby = (unsigned)(h->mb_pad / 256);
+        const unsigned nsup = ((nbx + 3) / 4) * ((nby + 7) / 8);                 // super-tiles of 4 x 8 tiles, dealt to the XCDs in rounds of eight
+        hipLaunchKernelGGL(k_recombine_mfma_big, dim3(((nsup + 7) / 8) * 8 * 32), dim3(512), RCB_LDS, st, h->dR8, 1, h->ldr, h->mb,
+                           (int)(h->ldr / 128), h->dZlo, ld, h->dFail, h->dP, B, d_e, m, nbx, nby);
+      }
+      bottom(p.rsplits > 1 && h->mb > h->w ? h->mb : h->w, p.rsplits > 1 ? 1 : 0);
+      hipLaunchKernelGGL(k_recombine_mfma, dim3((unsigned)((B + 127) / 128), (unsigned)((h->mb + 127) / 128), (unsigned)p.rsplits), dim3(256), RC_LDS, st, h->dR,
+                         h->ldr, h->mb, (int)(h->ldr / 64), h->dZlo, h->dZhi, ld, h->dFail, h->dP, B, d_e, m, p.rc_big ? 1 : 0, p.kps);
+      break;
+  }
+}
+
+// One samp_p pass over B rows (mp_perturbation.rs:304-336), everything in order on the caller's stream.
+static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_e, hipStream_t st) {
+  if (!h->keep_fail) hipMemsetAsync(h->dFail, 0, 4 * sizeof(int), st);      // [0] sampler failure, [1] some |z| > 127, [2] some |p| >= 2^15 (third digit plane of the syndrome product in use)
+  psf_status gate_rc = PSF_OK;
+  auto u_gate = [&]() { if (h->before_u) { auto f = std::move(h->before_u); h->before_u = nullptr; gate_rc = f(); } };
+  SampPlan p = plan_samp_p(h, B);
+  if (p.one_launch) {
+    u_gate();
+    if (gate_rc != PSF_OK) return gate_rc;
+    ScopedTimer t(h, st, "k_samp_p_small");
+    hipLaunchKernelGGL(k_samp_p_small, dim3((unsigned)B), dim3(FS_THREADS), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, (uint32_t)h->mb, h->q, h->two64,
+                       h->prm.gp.base, h->dLt, h->dA, h->dR, h->ldr, h->szR, GadgetTablesQ{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng}, d_u, d_e, h->dFail);
+  } else {
+    prepare_samp_p(h, st, p);
+    h->normals_ncf = p.ncf;
+    normals_stage(h, st, p, seed, first_index, B);
+    product_stage(h, st, p, B);
+    if (h->structured) {  // x_top -= g R d_2 (exact integer sum on the int8 matrix cores)
+      ScopedTimer t(h, st, "k_rd2_mfma");
+      hipLaunchKernelGGL(k_rd2_mfma, dim3((unsigned)(h->ld / 64), (unsigned)(round_up(h->mb, 64) / 64)), dim3(256), 3 * (1 + kFixPlanes) * 4096, st, h->dR8, h->ldr, h->dD8,
+                         h->ldr * h->ld, h->ld, h->mb, h->g_const, h->dX);
+    }
+    round_stage(h, st, p, seed, first_index, B);
+    u_gate();                                                      // (host path: u reaches the device now)
+    syndrome_stage(h, st, p, B, d_u);
+    gadget_stage(h, st, p, seed, first_index, B);
+    recombine_stage(h, st, p, B, d_e);
+  }
   HIP_TRY(hipGetLastError());
   if (gate_rc != PSF_OK) return gate_rc;
   h->last_stream = st;
@@ -2037,7 +2034,7 @@ psf_status psfp_f_a_dev(psfp_handle* h, size_t B, const int64_t* d_e, uint64_t* 
   const size_t m = h->m, ld = h->ld;
   hipLaunchKernelGGL(k_check_domain, dim3((unsigned)B), dim3(256), 0, st, d_e, m, m, domain_bound(h), d_ok);   // :367
   hipLaunchKernelGGL(k_narrow_transpose, dim3((unsigned)(ld / 64), (unsigned)((m + 63) / 64)), dim3(256), 0, st, d_e, m, B, ld, h->dPf, d_ok);
-  launch_zq_mfma(h, st, ZQ_FA, h->dPf, h->dP8f, B, nullptr, d_u, h->n);                                                    // :368
+  launch_zq(h, st, plan_zq(h, B, false), ZQ_FA, h->dPf, h->dP8f, B, nullptr, d_u, h->n);                                                  // :368
   HIP_TRY(hipGetLastError());
   h->last_stream = st;
   return PSF_OK;
