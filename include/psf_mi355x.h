@@ -168,6 +168,23 @@ psf_status psf_matpoly_mul_hat_dev(int device, uint64_t q, size_t n, size_t coun
                                    int trans_a, const void* d_b, void* d_c, int io_bits, void* stream);
 /* host buffers, one product C = A . B (rows x inner, inner x cols -> rows x cols); allocates per call, like psf_poly_mul_negacyclic */
 psf_status psf_matpoly_mul_negacyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, uint64_t* c);
+/* The cyclic ring R_q = Z_q[X]/(X^n - 1) (new_cyclic, common_moduli.rs:72-79): one twin per X^n + 1 entry point above, with the same arguments,
+ * layouts, word widths, limits, return codes and rules (every check before the first HIP call, nothing written on PSF_ERR_PARAM / PSF_ERR_UNSUPPORTED,
+ * PSF_ERR_HIP without a device, no CPU fallback).  out[c] = sum_i a_i b_{(c - i) mod n}.  A (q, n) has a cyclic NTT exactly when it has a negacyclic
+ * one: the same wave and LDS kernels run with a table of zetas for X^n - 1; every other q < 2^62 at 64-bit words runs an exact schoolbook kernel.
+ * Images from psf_ntt_forward_cyclic_dev are opaque and valid only for the *_hat_cyclic_dev products (not for psf_poly_mul_hat_dev /
+ * psf_matpoly_mul_hat_dev, and images from psf_ntt_forward_dev are not valid here). */
+psf_status psf_poly_mul_cyclic(int device, uint64_t q, size_t n, size_t count, const uint64_t* a, const int64_t* b, uint64_t* out);
+psf_status psf_poly_mul_cyclic_method(int device, uint64_t q, size_t n, size_t count, const uint64_t* a, const int64_t* b, uint64_t* out, int method);
+psf_status psf_poly_mul_cyclic_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, const void* d_b, void* d_out, int io_bits, void* stream);
+psf_status psf_ntt_forward_cyclic_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, int io_bits, uint32_t* d_hat, void* stream);
+psf_status psf_poly_mul_hat_cyclic_dev(int device, uint64_t q, size_t n, size_t count, const uint32_t* d_hat, size_t hat_stride, const void* d_b, void* d_out,
+                                       int io_bits, void* stream);
+psf_status psf_matpoly_mul_cyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
+                                      int trans_a, const void* d_b, void* d_c, int io_bits, void* stream);
+psf_status psf_matpoly_mul_hat_cyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint32_t* d_hat,
+                                          size_t hat_stride, int trans_a, const void* d_b, void* d_c, int io_bits, void* stream);
+psf_status psf_matpoly_mul_cyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, uint64_t* c);
 /* R_q coefficient maps of the ML-KEM-style schemes, on a flat array of `len` coefficients (any number of polynomials, or of the entries of a
  * MatPolynomialRingZq, n coefficients each, constant term first).  Exact integer arithmetic, bit for bit against the big-integer definitions:
  *   compress   (LossyCompressionFIPS203::lossy_compress, lossy_compression_fips203.rs:89-112):   y = floor((x 2^d + floor(q/2)) / q) mod 2^d,

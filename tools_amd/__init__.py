@@ -3,7 +3,7 @@
 Host-side mirror of the reference's interface for this path (src/primitive/psf.rs:39-81):
 GadgetParameters.init_default, PSFPerturbation / PSFGPV / PSFGPVRing with
 trap_gen / samp_d / samp_p / f_a / check_domain; compression (LossyCompressionFIPS203), encodings (utils::common_encodings) and
-rq (MatPolynomialRingZq matrix products).
+rq (MatPolynomialRingZq matrix products, and the products of the cyclic ring X^n - 1).
 Everything computes on the GPU through the C ABI.
 """
 from ._ffi import PsfError, LIB_PATH  # noqa: F401

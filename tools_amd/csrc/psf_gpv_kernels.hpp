@@ -193,6 +193,78 @@ __global__ __launch_bounds__(256) void k_matpoly_negacyclic(uint64_t q, uint64_t
   }
 }
 
-// The NTT forms of this product (one transform per wavefront, Montgomery arithmetic) are in psf_ntt_kernels.hpp / psf_ntt.hip.
+// ---- the cyclic ring Z_q[X]/(X^n - 1) (common_moduli.rs:72-79): the same two products for every q < 2^62 without an NTT ------------------------------
+// The layouts and the work split of k_polymul_negacyclic / k_matpoly_negacyclic; the wrapped terms are ADDED, so out[c] = sum_i a_i b_{(c - i) mod n}
+// is one non-negative sum: in 128 bits for q < 2^31 (at most 2^13 * 2^20 terms below 2^62; acc128_mod takes any high word), reduced term by term above.
+__global__ __launch_bounds__(256) void k_polymul_cyclic(uint64_t q, uint64_t two64, uint32_t n, size_t count, const uint64_t* __restrict__ A,
+                                                        const int64_t* __restrict__ Bp, uint64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) uint64_t pc_smem[];   // a[n] | b[n]
+  uint64_t* sa = pc_smem;
+  uint64_t* sb = pc_smem + n;
+  const bool small = q <= 0x7fffffffull;
+  for (size_t pair = blockIdx.x; pair < count; pair += gridDim.x) {
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n; i += 256) {
+      sa[i] = A[pair * n + i] % q;
+      const int64_t v = Bp[pair * n + i] % (int64_t)q;
+      sb[i] = (uint64_t)(v < 0 ? v + (int64_t)q : v);
+    }
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < n; c += 256) {
+      uint64_t sum = 0;
+      if (small) {
+        Acc128 S{0, 0};
+        for (uint32_t i = 0; i <= c; ++i) acc128_add(S, (int64_t)(sa[i] * sb[c - i]));
+        for (uint32_t i = c + 1; i < n; ++i) acc128_add(S, (int64_t)(sa[i] * sb[n + c - i]));
+        sum = acc128_mod(S, q, two64);
+      } else {
+        for (uint32_t i = 0; i <= c; ++i) { sum += mulmod_dev(sa[i], sb[c - i], q); if (sum >= q) sum -= q; }
+        for (uint32_t i = c + 1; i < n; ++i) { sum += mulmod_dev(sa[i], sb[n + c - i], q); if (sum >= q) sum -= q; }
+      }
+      out[pair * n + c] = sum;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_matpoly_cyclic(uint64_t q, uint64_t two64, uint32_t n, size_t count, size_t rows, size_t inner, size_t cols,
+                                                        const uint64_t* __restrict__ A, size_t a_stride, int trans_a, const int64_t* __restrict__ Bp,
+                                                        uint64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) uint64_t mc_smem[];   // a[n] | b[n]
+  uint64_t* sa = mc_smem;
+  uint64_t* sb = mc_smem + n;
+  const bool small = q <= 0x7fffffffull;
+  const size_t outs = count * rows * cols;
+  for (size_t o = blockIdx.x; o < outs; o += gridDim.x) {
+    const size_t j = o % cols, ci = o / cols, i = ci % rows, c = ci / rows;
+    for (uint32_t c0 = 0; c0 < n; c0 += 256) {
+      const uint32_t cc = c0 + threadIdx.x;
+      Acc128 S{0, 0};
+      uint64_t sum = 0;
+      for (size_t k = 0; k < inner; ++k) {
+        const uint64_t* pa = A + (c * a_stride + (trans_a ? k * rows + i : i * inner + k)) * n;
+        const int64_t* pb = Bp + ((c * inner + k) * cols + j) * n;
+        __syncthreads();
+        for (uint32_t t = threadIdx.x; t < n; t += 256) {
+          sa[t] = pa[t] % q;
+          const int64_t v = pb[t] % (int64_t)q;
+          sb[t] = (uint64_t)(v < 0 ? v + (int64_t)q : v);
+        }
+        __syncthreads();
+        if (cc >= n) continue;
+        if (small) {
+          for (uint32_t t = 0; t <= cc; ++t) acc128_add(S, (int64_t)(sa[t] * sb[cc - t]));
+          for (uint32_t t = cc + 1; t < n; ++t) acc128_add(S, (int64_t)(sa[t] * sb[n + cc - t]));
+        } else {
+          for (uint32_t t = 0; t <= cc; ++t) { sum += mulmod_dev(sa[t], sb[cc - t], q); if (sum >= q) sum -= q; }
+          for (uint32_t t = cc + 1; t < n; ++t) { sum += mulmod_dev(sa[t], sb[n + cc - t], q); if (sum >= q) sum -= q; }
+        }
+      }
+      if (cc >= n) continue;
+      out[o * n + cc] = small ? acc128_mod(S, q, two64) : sum;
+    }
+  }
+}
+
+// The NTT forms of these products (one transform per wavefront, Montgomery arithmetic) are in psf_ntt_kernels.hpp / psf_ntt.hip.
 
 }  // namespace psf

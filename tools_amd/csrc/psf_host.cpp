@@ -447,6 +447,29 @@ NttPlan make_ntt_plan(uint64_t q, uint32_t n) {
   return pl;
 }
 
+NttPlan make_ntt_plan_cyclic(uint64_t q, uint32_t n) {
+  NttPlan pl = make_ntt_plan(q, n);                                   // the same conditions, L, d and 2^-L
+  if (!pl.ok) return pl;
+  const uint32_t L = pl.L, cnt = 1u << L;
+  uint64_t omega = 0;                                                 // order exactly 2^L: x^((q-1)/2^L) for a quadratic non-residue x
+  for (uint64_t x = 2; x < q; ++x) {
+    if (powmod_u64(x, (q - 1) / 2, q) != q - 1) continue;
+    omega = powmod_u64(x, (q - 1) >> L, q);
+    break;
+  }
+  pl.zetas[0] = pl.zetas_inv[0] = 1;
+  for (uint32_t i = 1; i < cnt; ++i) {                                // i = 2^l + b
+    uint32_t l = 0;
+    while ((2u << l) <= i) ++l;
+    const uint32_t b = i - (1u << l);
+    uint32_t br = 0;
+    for (uint32_t k = 0; k + 1 < L; ++k) if (b & (1u << k)) br |= 1u << (L - 2 - k);
+    pl.zetas[i] = powmod_u64(omega, br, q);
+    pl.zetas_inv[i] = powmod_u64(pl.zetas[i], q - 2, q);
+  }
+  return pl;
+}
+
 static uint32_t ntt_form(uint64_t v, uint64_t q, int qb) {          // centred int32 bits for the 16-bit form, canonical otherwise
   if (qb == 0) return (uint32_t)v;
   const int64_t c = v > q / 2 ? (int64_t)v - (int64_t)q : (int64_t)v;

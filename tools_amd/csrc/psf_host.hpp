@@ -89,6 +89,10 @@ psf_status ring_short_basis_t(const psf_gadget_params& gp, const uint64_t* a, co
 // ok = false when q is not a prime with v2(q-1) >= 2, n is not a power of two, or q >= 2^31.
 struct NttPlan { bool ok = false; uint32_t n = 0, L = 0, d = 0; uint64_t q = 0, inv_scale = 0; std::vector<uint64_t> zetas, zetas_inv; };
 NttPlan make_ntt_plan(uint64_t q, uint32_t n);
+// The cyclic twin for Z_q[X]/(X^n - 1) (common_moduli.rs:72-79): the same L, d and inv_scale, and a plan exists exactly when make_ntt_plan has one.
+// zetas[2^l + b] = omega^bitrev_(L-1)(b) for omega of order 2^L (zetas[0] = 1, never read): node (l, b) splits X^(2m) - c^2 into X^m -+ c with
+// c = zetas[2^l + b], starting from the root constant 1, so leaf 2b is X^d - c and leaf 2b+1 is X^d + c -- the indexing the kernels already read.
+NttPlan make_ntt_plan_cyclic(uint64_t q, uint32_t n);
 // The same plan in the form the wave-level kernels of psf_ntt_core.hpp read: which arithmetic (qb = 12 / 14: signed 16-bit Montgomery form for
 // q < 2^12 / 2^14; qb = 0: 32-bit Montgomery form), the constants of the reduction, and the zetas (forward [2^L] | inverse [2^L]) multiplied by
 // R = 2^16 (centred, as int32 bits) or 2^32; qb = 12 appends the pairs of the dot-product form (psf_ntt_core.hpp, Mod16D).  wave = false when the shape has no wave kernel (n outside 128 ... 1024, leaf degree above 4 or wider than a lane).

@@ -1,5 +1,6 @@
-// psf_ntt.hip -- negacyclic NTT products over R_q = Z_q[X]/(X^n + 1): plan cache, shape dispatch and launches (psf_ntt_api.hpp).
-// PolynomialRingZq multiplication under gadget_ring.rs:78 and gpv_ring.rs:243-247; the kernels are in psf_ntt_kernels.hpp / psf_ntt_core.hpp.
+// psf_ntt.hip -- NTT products over R_q = Z_q[X]/(X^n + 1) and Z_q[X]/(X^n - 1): plan cache, shape dispatch and launches (psf_ntt_api.hpp).
+// PolynomialRingZq multiplication under gadget_ring.rs:78 and gpv_ring.rs:243-247; the kernels are in psf_ntt_kernels.hpp / psf_ntt_core.hpp.  They read
+// the ring from the table of zetas alone (NttDev::zetas), so the cyclic ring takes the same instantiations with the table of make_ntt_plan_cyclic.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -91,17 +92,17 @@ struct Plan {
   int route = 0;
 };
 std::mutex g_mu;
-std::map<std::tuple<int, uint64_t, size_t>, Plan*> g_plans;
+std::map<std::tuple<int, uint64_t, size_t, int>, Plan*> g_plans;
 
-// the plan of (device, q, n), built once; nullptr: no NTT for this (q, n)
-Plan* plan_for(int device, uint64_t q, size_t n, psf_status* st) {
+// the plan of (device, q, n, ring), built once; nullptr: no NTT for this (q, n)
+Plan* plan_for(int device, uint64_t q, size_t n, psf_status* st, NttRing ring = kNegacyclic) {
   *st = PSF_OK;
   std::lock_guard<std::mutex> lk(g_mu);
-  const auto key = std::make_tuple(device, q, n);
+  const auto key = std::make_tuple(device, q, n, (int)ring);
   auto it = g_plans.find(key);
   if (it != g_plans.end()) return it->second->route ? it->second : nullptr;
   Plan* P = new Plan();
-  if (q < (1ull << 31) && n >= 2 && n <= 8192) P->pl = make_ntt_plan(q, (uint32_t)n);
+  if (q < (1ull << 31) && n >= 2 && n <= 8192) P->pl = ring == kCyclic ? make_ntt_plan_cyclic(q, (uint32_t)n) : make_ntt_plan(q, (uint32_t)n);
   if (P->pl.ok) {
     P->tb = make_ntt_tables(P->pl);
     P->route = P->tb.wave ? 2 : 1;
@@ -149,17 +150,18 @@ unsigned wave_grid(size_t count) {                                       // four
 
 namespace psf {
 
-int ntt_route(uint64_t q, size_t n) {
+int ntt_route(uint64_t q, size_t n, NttRing ring) {
   psf_status st;
-  Plan* P = plan_for(-1, q, n, &st);
+  Plan* P = plan_for(-1, q, n, &st, ring);
   return P ? P->route : 0;
 }
 
-psf_status ntt_polymul_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, const void* d_b, void* d_out, int io_bits, hipStream_t st) {
+psf_status ntt_polymul_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, const void* d_b, void* d_out, int io_bits, hipStream_t st,
+                           NttRing ring) {
   if (io_bits != 16 && io_bits != 64) return PSF_ERR_PARAM;
   if (count && (!d_a || !d_b || !d_out)) return PSF_ERR_PARAM;
   psf_status rc;
-  Plan* P = plan_for(device, q, n, &rc);
+  Plan* P = plan_for(device, q, n, &rc, ring);
   if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
   if (count == 0) return PSF_OK;
   NTT_TRY(hipSetDevice(device));
@@ -195,11 +197,11 @@ psf_status ntt_polymul_dev(int device, uint64_t q, size_t n, size_t count, const
   return PSF_OK;
 }
 
-psf_status ntt_forward_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, int io_bits, uint32_t* d_hat, hipStream_t st) {
+psf_status ntt_forward_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, int io_bits, uint32_t* d_hat, hipStream_t st, NttRing ring) {
   if (io_bits != 16 && io_bits != 64) return PSF_ERR_PARAM;
   if (count && (!d_a || !d_hat)) return PSF_ERR_PARAM;
   psf_status rc;
-  Plan* P = plan_for(device, q, n, &rc);
+  Plan* P = plan_for(device, q, n, &rc, ring);
   if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
   if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
   if (count == 0) return PSF_OK;
@@ -217,11 +219,12 @@ psf_status ntt_forward_dev(int device, uint64_t q, size_t n, size_t count, const
   return PSF_OK;
 }
 
-psf_status ntt_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, const uint32_t* d_hat, size_t hat_stride, const void* d_b, void* d_out, int io_bits, hipStream_t st) {
+psf_status ntt_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, const uint32_t* d_hat, size_t hat_stride, const void* d_b, void* d_out, int io_bits, hipStream_t st,
+                           NttRing ring) {
   if (io_bits != 16 && io_bits != 64) return PSF_ERR_PARAM;
   if (count && (!d_hat || !d_b || !d_out)) return PSF_ERR_PARAM;
   psf_status rc;
-  Plan* P = plan_for(device, q, n, &rc);
+  Plan* P = plan_for(device, q, n, &rc, ring);
   if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
   if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
   if (count == 0) return PSF_OK;
@@ -260,9 +263,9 @@ psf_status ntt_ring_fa_dev(int device, uint64_t q, size_t n, uint32_t K, const u
 
 
 psf_status ntt_matmul_dev(int device, uint64_t q, size_t n, const NttMatShape& s, const void* d_a, size_t a_stride, bool hat, const void* d_b, void* d_c,
-                          int io_bits, hipStream_t st) {
+                          int io_bits, hipStream_t st, NttRing ring) {
   psf_status rc;
-  Plan* P = plan_for(device, q, n, &rc);
+  Plan* P = plan_for(device, q, n, &rc, ring);
   if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
   if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
   const size_t zn = (P->tb.qb == 12 ? 4u : 2u) << P->pl.L;

@@ -1041,16 +1041,37 @@ static psf_status ring_install(psfring_handle* h) {
   return PSF_OK;
 }
 
+// the dynamic LDS of a schoolbook kernel of the cyclic ring above the default 64 KiB (n > 4096): its limit is raised once per process, kernel and device
+static psf_status raise_lds_once(const void* kern, int device, size_t smem) {
+  if (smem <= 64 * 1024) return PSF_OK;
+  static std::mutex mu; static std::vector<std::pair<const void*, int>> raised;
+  std::lock_guard<std::mutex> lk(mu);
+  if (std::find(raised.begin(), raised.end(), std::make_pair(kern, device)) == raised.end()) {
+    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    raised.emplace_back(kern, device);
+  }
+  return PSF_OK;
+}
+
 // one R_q product kernel launch on device buffers: the NTT when (q, n) has one, the exact schoolbook kernel otherwise (64-bit layout only)
-static psf_status polymul_dev_any(int device, uint64_t q, size_t n, size_t count, const void* da, const void* db, void* dout, int io_bits, int method, hipStream_t st) {
+static psf_status polymul_dev_any(int device, uint64_t q, size_t n, size_t count, const void* da, const void* db, void* dout, int io_bits, int method, hipStream_t st,
+                                  NttRing ring = kNegacyclic) {
   if (method != 0) {
-    const psf_status rc = ntt_polymul_dev(device, q, n, count, da, db, dout, io_bits, st);
+    const psf_status rc = ntt_polymul_dev(device, q, n, count, da, db, dout, io_bits, st, ring);
     if (rc != PSF_ERR_UNSUPPORTED || method == 1) return rc;
   }
   if (io_bits != 64) return PSF_ERR_UNSUPPORTED;
   if (count == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(device));
   const uint64_t two64 = (uint64_t)((((u128)1) << 64) % q);
+  if (ring == kCyclic) {
+    const psf_status rl = raise_lds_once(reinterpret_cast<const void*>(k_polymul_cyclic), device, 2 * n * sizeof(uint64_t));
+    if (rl != PSF_OK) return rl;
+    hipLaunchKernelGGL(k_polymul_cyclic, dim3((unsigned)(count < 65536 ? count : 65536)), dim3(256), 2 * n * sizeof(uint64_t), st, q, two64, (uint32_t)n, count,
+                       (const uint64_t*)da, (const int64_t*)db, (uint64_t*)dout);
+    HIP_TRY(hipGetLastError());
+    return PSF_OK;
+  }
   hipLaunchKernelGGL(k_polymul_negacyclic, dim3((unsigned)count), dim3(256), 2 * n * sizeof(uint64_t), st, q, two64, (uint32_t)n, (const uint64_t*)da, n, (const int64_t*)db, n,
                      (uint64_t*)dout, n);
   HIP_TRY(hipGetLastError());
@@ -1083,9 +1104,9 @@ void psfring_destroy(psfring_handle* h) {
 }
 
 // method: 0 = schoolbook kernel, 1 = NTT (PSF_ERR_UNSUPPORTED without a plan), -1 = NTT when there is one
-psf_status psf_poly_mul_negacyclic_method(int device, uint64_t q, size_t n, size_t count, const uint64_t* a, const int64_t* b, uint64_t* out, int method) {
+static psf_status poly_mul_host(int device, uint64_t q, size_t n, size_t count, const uint64_t* a, const int64_t* b, uint64_t* out, int method, NttRing ring) {
   if (q <= 1 || q >= (1ull << 62) || n < 1 || n > 8192 || (count && (!a || !b || !out))) return PSF_ERR_PARAM;
-  if (method == 1 && ntt_route(q, n) == 0) return PSF_ERR_UNSUPPORTED;
+  if (method == 1 && ntt_route(q, n, ring) == 0) return PSF_ERR_UNSUPPORTED;
   if (count == 0) return PSF_OK;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
@@ -1096,10 +1117,13 @@ psf_status psf_poly_mul_negacyclic_method(int device, uint64_t q, size_t n, size
       hipMalloc(&dout, count * n * sizeof(uint64_t)) != hipSuccess) return done(PSF_ERR_HIP);
   if (hipMemcpy(da, a, count * n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(db, b, count * n * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) return done(PSF_ERR_HIP);
-  const psf_status rc = polymul_dev_any(device, q, n, count, da, db, dout, 64, method, nullptr);
+  const psf_status rc = polymul_dev_any(device, q, n, count, da, db, dout, 64, method, nullptr, ring);
   if (rc != PSF_OK) return done(rc);
   if (hipMemcpy(out, dout, count * n * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
   return done(PSF_OK);
+}
+psf_status psf_poly_mul_negacyclic_method(int device, uint64_t q, size_t n, size_t count, const uint64_t* a, const int64_t* b, uint64_t* out, int method) {
+  return poly_mul_host(device, q, n, count, a, b, out, method, kNegacyclic);
 }
 
 psf_status psf_poly_mul_negacyclic(int device, uint64_t q, size_t n, size_t count, const uint64_t* a, const int64_t* b, uint64_t* out) {
@@ -1118,13 +1142,32 @@ psf_status psf_poly_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, 
   return ntt_mul_hat_dev(device, q, n, count, d_hat, hat_stride, d_b, d_out, io_bits, (hipStream_t)stream);
 }
 
+// the cyclic ring Z_q[X]/(X^n - 1) (common_moduli.rs:72-79): the same checks, codes and routes with the cyclic tables or the cyclic schoolbook kernel
+psf_status psf_poly_mul_cyclic_method(int device, uint64_t q, size_t n, size_t count, const uint64_t* a, const int64_t* b, uint64_t* out, int method) {
+  return poly_mul_host(device, q, n, count, a, b, out, method, kCyclic);
+}
+psf_status psf_poly_mul_cyclic(int device, uint64_t q, size_t n, size_t count, const uint64_t* a, const int64_t* b, uint64_t* out) {
+  return poly_mul_host(device, q, n, count, a, b, out, -1, kCyclic);
+}
+psf_status psf_poly_mul_cyclic_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, const void* d_b, void* d_out, int io_bits, void* stream) {
+  if (q <= 1 || q >= (1ull << 62) || n < 1 || n > 8192 || (io_bits != 16 && io_bits != 64) || (count && (!d_a || !d_b || !d_out))) return PSF_ERR_PARAM;
+  return polymul_dev_any(device, q, n, count, d_a, d_b, d_out, io_bits, -1, (hipStream_t)stream, kCyclic);
+}
+psf_status psf_ntt_forward_cyclic_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, int io_bits, uint32_t* d_hat, void* stream) {
+  return ntt_forward_dev(device, q, n, count, d_a, io_bits, d_hat, (hipStream_t)stream, kCyclic);
+}
+psf_status psf_poly_mul_hat_cyclic_dev(int device, uint64_t q, size_t n, size_t count, const uint32_t* d_hat, size_t hat_stride, const void* d_b, void* d_out,
+                                       int io_bits, void* stream) {
+  return ntt_mul_hat_dev(device, q, n, count, d_hat, hat_stride, d_b, d_out, io_bits, (hipStream_t)stream, kCyclic);
+}
+
 }  // extern "C"
 
 // ---- R_q matrix products (MatPolynomialRingZq * MatPolynomialRingZq: gpv_ring.rs:245, gadget_ring.rs:78 and :190-202, short_basis_ring.rs:183-198) ----
 // Every argument is checked here, before the first HIP call (plan_for allocates on the device, so it comes after).  hat: A given by its images.
 static constexpr size_t kMatpolyMaxInner = (size_t)1 << 20;
 static psf_status matpoly_check(uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride, bool hat,
-                                int trans_a, const void* d_b, const void* d_c, int io_bits) {
+                                int trans_a, const void* d_b, const void* d_c, int io_bits, NttRing ring = kNegacyclic) {
   if (q <= 1 || q >= (1ull << 62) || n < 1 || n > 8192) return PSF_ERR_PARAM;
   if (rows == 0 || inner == 0 || cols == 0 || (trans_a != 0 && trans_a != 1) || (io_bits != 16 && io_bits != 64)) return PSF_ERR_PARAM;
   if (count && (!d_a || !d_b || !d_c)) return PSF_ERR_PARAM;
@@ -1146,22 +1189,31 @@ static psf_status matpoly_check(uint64_t q, size_t n, size_t count, size_t rows,
     if ((c0 < a0 + a_all && a0 < c0 + c_all) || (c0 < b0 + b_all && b0 < c0 + c_all)) return PSF_ERR_PARAM;   // the output overlaps an input
   }
   if (inner > kMatpolyMaxInner) return PSF_ERR_UNSUPPORTED;
-  const int route = ntt_route(q, n);                        // host tables only (device -1): no HIP call
+  const int route = ntt_route(q, n, ring);                  // host tables only (device -1): no HIP call
   if ((hat || io_bits == 16) && route != 2) return PSF_ERR_UNSUPPORTED;
   if (io_bits == 16 && q >= (1ull << 14)) return PSF_ERR_UNSUPPORTED;     // 16-bit words: the wave kernels of q < 2^14
   return PSF_OK;
 }
 
 static psf_status matpoly_dev_any(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
-                                  bool hat, int trans_a, const void* d_b, void* d_c, int io_bits, hipStream_t st) {
-  const psf_status chk = matpoly_check(q, n, count, rows, inner, cols, d_a, a_stride, hat, trans_a, d_b, d_c, io_bits);
+                                  bool hat, int trans_a, const void* d_b, void* d_c, int io_bits, hipStream_t st, NttRing ring = kNegacyclic) {
+  const psf_status chk = matpoly_check(q, n, count, rows, inner, cols, d_a, a_stride, hat, trans_a, d_b, d_c, io_bits, ring);
   if (chk != PSF_OK || count == 0) return chk;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
-  if (ntt_route(q, n) == 2) return ntt_matmul_dev(device, q, n, NttMatShape{count, rows, inner, cols, trans_a}, d_a, a_stride, hat, d_b, d_c, io_bits, st);
+  if (ntt_route(q, n, ring) == 2)
+    return ntt_matmul_dev(device, q, n, NttMatShape{count, rows, inner, cols, trans_a}, d_a, a_stride, hat, d_b, d_c, io_bits, st, ring);
   HIP_TRY(hipSetDevice(device));                            // every other q < 2^62 at 64-bit words: the exact schoolbook kernel
   const uint64_t two64 = (uint64_t)((((u128)1) << 64) % q);
   const size_t outs = count * rows * cols;
+  if (ring == kCyclic) {
+    const psf_status rl = raise_lds_once(reinterpret_cast<const void*>(k_matpoly_cyclic), device, 2 * n * sizeof(uint64_t));
+    if (rl != PSF_OK) return rl;
+    hipLaunchKernelGGL(k_matpoly_cyclic, dim3((unsigned)(outs < 16384 ? outs : 16384)), dim3(256), 2 * n * sizeof(uint64_t), st, q, two64, (uint32_t)n,
+                       count, rows, inner, cols, (const uint64_t*)d_a, a_stride, trans_a, (const int64_t*)d_b, (uint64_t*)d_c);
+    HIP_TRY(hipGetLastError());
+    return PSF_OK;
+  }
   if (2 * n * sizeof(uint64_t) > 64 * 1024) {               // n > 4096: above the default LDS limit, raised once per process and device
     static std::mutex mu; static std::vector<int> raised;
     std::lock_guard<std::mutex> lk(mu);
@@ -1186,9 +1238,10 @@ psf_status psf_matpoly_mul_hat_dev(int device, uint64_t q, size_t n, size_t coun
                                    int trans_a, const void* d_b, void* d_c, int io_bits, void* stream) {
   return matpoly_dev_any(device, q, n, count, rows, inner, cols, d_hat, hat_stride, true, trans_a, d_b, d_c, io_bits, (hipStream_t)stream);
 }
-psf_status psf_matpoly_mul_negacyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, uint64_t* c) {
+static psf_status matpoly_host(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, uint64_t* c,
+                               NttRing ring) {
   // the same checks on the host buffers (one batch), then device copies
-  const psf_status chk = matpoly_check(q, n, 1, rows, inner, cols, a, 0, false, 0, b, c, 64);
+  const psf_status chk = matpoly_check(q, n, 1, rows, inner, cols, a, 0, false, 0, b, c, 64, ring);
   if (chk != PSF_OK) return chk;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
@@ -1200,10 +1253,26 @@ psf_status psf_matpoly_mul_negacyclic(int device, uint64_t q, size_t n, size_t r
       hipMalloc(&dc, nc * sizeof(uint64_t)) != hipSuccess) return done(PSF_ERR_HIP);
   if (hipMemcpy(da, a, na * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(db, b, nb * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) return done(PSF_ERR_HIP);
-  const psf_status rc = matpoly_dev_any(device, q, n, 1, rows, inner, cols, da, 0, false, 0, db, dc, 64, nullptr);
+  const psf_status rc = matpoly_dev_any(device, q, n, 1, rows, inner, cols, da, 0, false, 0, db, dc, 64, nullptr, ring);
   if (rc != PSF_OK) return done(rc);
   if (hipMemcpy(c, dc, nc * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
   return done(PSF_OK);
+}
+psf_status psf_matpoly_mul_negacyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, uint64_t* c) {
+  return matpoly_host(device, q, n, rows, inner, cols, a, b, c, kNegacyclic);
+}
+
+// the cyclic ring Z_q[X]/(X^n - 1): the same checks, codes and routes
+psf_status psf_matpoly_mul_cyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
+                                      int trans_a, const void* d_b, void* d_c, int io_bits, void* stream) {
+  return matpoly_dev_any(device, q, n, count, rows, inner, cols, d_a, a_stride, false, trans_a, d_b, d_c, io_bits, (hipStream_t)stream, kCyclic);
+}
+psf_status psf_matpoly_mul_hat_cyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint32_t* d_hat,
+                                          size_t hat_stride, int trans_a, const void* d_b, void* d_c, int io_bits, void* stream) {
+  return matpoly_dev_any(device, q, n, count, rows, inner, cols, d_hat, hat_stride, true, trans_a, d_b, d_c, io_bits, (hipStream_t)stream, kCyclic);
+}
+psf_status psf_matpoly_mul_cyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, uint64_t* c) {
+  return matpoly_host(device, q, n, rows, inner, cols, a, b, c, kCyclic);
 }
 
 // MatQ::gso (gpv.rs:88-91) as a free function: rows of an integer matrix -> their Gram-Schmidt vectors

@@ -1,4 +1,5 @@
-"""MatPolynomialRingZq * MatPolynomialRingZq over R_q = Z_q[X]/(X^n + 1) through the C ABI (psf_matpoly_mul_*, include/psf_mi355x.h).
+"""MatPolynomialRingZq * MatPolynomialRingZq over R_q = Z_q[X]/(X^n + 1) through the C ABI (psf_matpoly_mul_*, include/psf_mi355x.h), and the
+products of the cyclic ring Z_q[X]/(X^n - 1) (new_cyclic, common_moduli.rs:72-79): the *_cyclic functions at the end, with the same conventions.
 
 The reference multiplies matrices of polynomials at gpv_ring.rs:245 (a * sigma), gadget_ring.rs:78 (a_bar * r), gadget_ring.rs:190-202 (is_trapdoor)
 and short_basis_ring.rs:183-198 (is_basis).  A matrix of polynomials is an array (rows, cols, n): row-major, constant term first."""
@@ -43,3 +44,66 @@ def matpoly_mul_hat_dev(d_hat, d_b, d_c, q, n, count, rows, inner, cols, hat_str
     check(lib().psf_matpoly_mul_hat_dev(C.c_int(device), C.c_uint64(q), C.c_size_t(n), C.c_size_t(count), C.c_size_t(rows), C.c_size_t(inner),
                                         C.c_size_t(cols), C.c_void_p(d_hat), C.c_size_t(hat_stride), C.c_int(trans_a), C.c_void_p(d_b), C.c_void_p(d_c),
                                         C.c_int(io_bits), C.c_void_p(stream or 0)), "matpoly_mul_hat_dev")
+
+
+# ---- the cyclic ring Z_q[X]/(X^n - 1) ------------------------------------------------------------------------------------------------------------------
+
+def poly_mul_cyclic(a, b, q, device=0, method=None):
+    """a * b in Z_q[X]/(X^n - 1) on the device (psf_poly_mul_cyclic).  a: residues (count x n or n), b: signed integers of the same shape.
+    method: None = automatic, 0 = schoolbook kernel, 1 = NTT kernel (PsfError(UNSUPPORTED) when q / n do not admit one)."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.int64)
+    if a.ndim not in (1, 2) or a.shape != b.shape or a.shape[-1] == 0:
+        raise ValueError(f"poly_mul_cyclic: shapes {a.shape} x {b.shape}")
+    a2, b2 = a.reshape(-1, a.shape[-1]), b.reshape(-1, b.shape[-1])
+    out = np.zeros_like(a2)
+    check(lib().psf_poly_mul_cyclic_method(C.c_int(device), C.c_uint64(q), C.c_size_t(a2.shape[1]), C.c_size_t(a2.shape[0]), _p(a2, C.c_uint64),
+                                           _p(b2, C.c_int64), _p(out, C.c_uint64), C.c_int(-1 if method is None else method)), "poly_mul_cyclic")
+    return out.reshape(a.shape)
+
+
+def poly_mul_cyclic_dev(d_a, d_b, d_out, q, n, count, io_bits=64, device=0, stream=None):
+    """psf_poly_mul_cyclic_dev on device buffers (raw pointers), in `stream`, nothing allocated; the layouts of gadget.poly_mul_negacyclic_dev."""
+    check(lib().psf_poly_mul_cyclic_dev(C.c_int(device), C.c_uint64(q), C.c_size_t(n), C.c_size_t(count), C.c_void_p(d_a), C.c_void_p(d_b),
+                                        C.c_void_p(d_out), C.c_int(io_bits), C.c_void_p(stream or 0)), "poly_mul_cyclic_dev")
+
+
+def ntt_forward_cyclic_dev(d_a, d_hat, q, n, count, io_bits=64, device=0, stream=None):
+    """psf_ntt_forward_cyclic_dev: count * n 32-bit words of opaque images, valid only for poly_mul_hat_cyclic_dev / matpoly_mul_hat_cyclic_dev."""
+    check(lib().psf_ntt_forward_cyclic_dev(C.c_int(device), C.c_uint64(q), C.c_size_t(n), C.c_size_t(count), C.c_void_p(d_a), C.c_int(io_bits),
+                                           C.c_void_p(d_hat), C.c_void_p(stream or 0)), "ntt_forward_cyclic_dev")
+
+
+def poly_mul_hat_cyclic_dev(d_hat, hat_stride, d_b, d_out, q, n, count, io_bits=64, device=0, stream=None):
+    """psf_poly_mul_hat_cyclic_dev: d_out[c] = image[c * hat_stride] * d_b[c]; hat_stride in words, 0 = one image for every product."""
+    check(lib().psf_poly_mul_hat_cyclic_dev(C.c_int(device), C.c_uint64(q), C.c_size_t(n), C.c_size_t(count), C.c_void_p(d_hat), C.c_size_t(hat_stride),
+                                            C.c_void_p(d_b), C.c_void_p(d_out), C.c_int(io_bits), C.c_void_p(stream or 0)), "poly_mul_hat_cyclic_dev")
+
+
+def matpoly_mul_cyclic(A, B, q, device=0):
+    """matpoly_mul over Z_q[X]/(X^n - 1): A (rows, inner, n) times B (inner, cols, n); returns (rows, cols, n) uint64 in [0, q)."""
+    A, B = np.asarray(A), np.asarray(B)
+    if A.ndim != 3 or B.ndim != 3 or A.shape[1] != B.shape[0] or A.shape[2] != B.shape[2]:
+        raise ValueError(f"matpoly_mul_cyclic: shapes {A.shape} x {B.shape}")
+    rows, inner, n = A.shape
+    cols = B.shape[1]
+    a = np.ascontiguousarray(np.mod(A.astype(np.int64), np.int64(q)).astype(np.uint64) if A.dtype.kind == "i" else A, dtype=np.uint64)
+    b = np.ascontiguousarray(np.mod(B, q).astype(np.int64) if B.dtype.kind == "u" else B, dtype=np.int64)
+    c = np.empty((rows, cols, n), dtype=np.uint64)
+    check(lib().psf_matpoly_mul_cyclic(C.c_int(device), C.c_uint64(q), C.c_size_t(n), C.c_size_t(rows), C.c_size_t(inner), C.c_size_t(cols),
+                                       _p(a, C.c_uint64), _p(b, C.c_int64), _p(c, C.c_uint64)), "matpoly_mul_cyclic")
+    return c
+
+
+def matpoly_mul_cyclic_dev(d_a, d_b, d_c, q, n, count, rows, inner, cols, a_stride=0, trans_a=0, io_bits=64, device=0, stream=None):
+    """psf_matpoly_mul_cyclic_dev: matpoly_mul_dev over Z_q[X]/(X^n - 1)."""
+    check(lib().psf_matpoly_mul_cyclic_dev(C.c_int(device), C.c_uint64(q), C.c_size_t(n), C.c_size_t(count), C.c_size_t(rows), C.c_size_t(inner),
+                                           C.c_size_t(cols), C.c_void_p(d_a), C.c_size_t(a_stride), C.c_int(trans_a), C.c_void_p(d_b), C.c_void_p(d_c),
+                                           C.c_int(io_bits), C.c_void_p(stream or 0)), "matpoly_mul_cyclic_dev")
+
+
+def matpoly_mul_hat_cyclic_dev(d_hat, d_b, d_c, q, n, count, rows, inner, cols, hat_stride=0, trans_a=0, io_bits=64, device=0, stream=None):
+    """psf_matpoly_mul_hat_cyclic_dev: A given by its images from ntt_forward_cyclic_dev (rows * inner per batch, in A's storage order)."""
+    check(lib().psf_matpoly_mul_hat_cyclic_dev(C.c_int(device), C.c_uint64(q), C.c_size_t(n), C.c_size_t(count), C.c_size_t(rows), C.c_size_t(inner),
+                                               C.c_size_t(cols), C.c_void_p(d_hat), C.c_size_t(hat_stride), C.c_int(trans_a), C.c_void_p(d_b), C.c_void_p(d_c),
+                                               C.c_int(io_bits), C.c_void_p(stream or 0)), "matpoly_mul_hat_cyclic_dev")
