@@ -360,6 +360,40 @@ psf_status psfp_samp_p_stages(psfp_handle*, uint64_t seed, uint64_t first_index,
  * launch stream when timing is enabled; names are ';'-separated in `names`. */
 psf_status psfp_enable_timing(psfp_handle*, int on);
 psf_status psfp_get_timing(psfp_handle*, char* names, size_t names_len, double* ms, size_t* count);
+/* which forms a samp_p pass takes (diagnostic, read-only).  One pass over B preimages picks a product form, a normals layout, a rounding kernel, a Z_q
+ * form, a gadget walk and a recombination from B, the key's shape and the buffers the handle holds; every form gives the same rows.
+ *   psfp_query_plan    : the plan a pass over B preimages would take on the handle as it stands -- nothing is launched, allocated or changed
+ *                        (what the call would derive from B for its buffers is computed for the query)
+ *   psfp_get_last_plan : the plan of the last pass that ran (PSF_ERR_NO_KEY before the first).  A device-pointer call is one pass; a host-pointer call
+ *                        of 2^20 coordinates or more runs in slices, each a pass of its own.
+ * Both fill fields[0 .. PSFP_PLAN_FIELDS) in the order of the PSFP_PLAN_* indices; count is the room in `fields`. */
+enum {
+  PSFP_PLAN_ONE_LAUNCH = 0,   /* 1: the whole call in one launch (small keys, up to 64 preimages); the other fields are then the defaults */
+  PSFP_PLAN_PRODUCT,          /* x = sqrt(Sigma_2) d: PSFP_PRODUCT_* */
+  PSFP_PLAN_RT, PSFP_PLAN_NB, PSFP_PLAN_NCG,   /* 16-row tiles x fragments of 16 preimages per wave; column groups of 16 NB preimages */
+  PSFP_PLAN_BC,               /* dense normals stream of bc = 1 ... 16 preimages (0: fragments or chunks) */
+  PSFP_PLAN_COMPACT,          /* 1: compact normals stream, 0: chunk stream */
+  PSFP_PLAN_GR, PSFP_PLAN_GC, /* PSFP_PRODUCT_BIG: super-tile of 8 x 4 or 16 x 2 workgroups */
+  PSFP_PLAN_TAIL,             /* 1: rounding and syndrome in one launch behind the product (one or two preimages, compact key copies present) */
+  PSFP_PLAN_ROUND,            /* PSFP_ROUND_* */
+  PSFP_PLAN_SYN_FORM,         /* v = u - A p: PSFP_ZQ_* */
+  PSFP_PLAN_SYN_SPLITS, PSFP_PLAN_SYN_FOLD128, PSFP_PLAN_SYN_POW2, PSFP_PLAN_SYN_WAVE_COMBINE,
+  PSFP_PLAN_GADGET,           /* PSFP_GADGET_* */
+  PSFP_PLAN_K32,              /* gadget kernels: the k <= 32 instantiation */
+  PSFP_PLAN_GQ_P,             /* PSFP_GADGET_QUEUE: problems per wave */
+  PSFP_PLAN_RECOMBINE,        /* e = p + [R; I] z: PSFP_RECOMBINE_* */
+  PSFP_PLAN_NBF,              /* PSFP_RECOMBINE_WG: fragments of 16 preimages per column group */
+  PSFP_PLAN_RC_BIG,           /* PSFP_RECOMBINE_TILES: the 256 x 256 tiles first */
+  PSFP_PLAN_RSPLITS,          /* PSFP_RECOMBINE_TILES: K splits of the 128 x 128 kernel */
+  PSFP_PLAN_FIELDS
+};
+enum { PSFP_PRODUCT_TASKS = 0, PSFP_PRODUCT_TILES64 = 1, PSFP_PRODUCT_TILES32 = 2, PSFP_PRODUCT_TILES96 = 3, PSFP_PRODUCT_BIG = 4 };
+enum { PSFP_ROUND_TAB = 0, PSFP_ROUND_TAB_ROW = 1, PSFP_ROUND_LEAN = 2, PSFP_ROUND_WAVE = 3 };
+enum { PSFP_ZQ_SMALL = 0, PSFP_ZQ_SMALL32 = 1, PSFP_ZQ_MFMA = 2 };
+enum { PSFP_GADGET_WAVE = 0, PSFP_GADGET_ROW = 1, PSFP_GADGET_QUAD = 2, PSFP_GADGET_QUEUE = 3, PSFP_GADGET_LOCKSTEP = 4 };
+enum { PSFP_RECOMBINE_SMALL = 0, PSFP_RECOMBINE_SMALL2 = 1, PSFP_RECOMBINE_WG = 2, PSFP_RECOMBINE_TILES = 3 };
+psf_status psfp_query_plan(const psfp_handle*, size_t B, int* fields, size_t count);
+psf_status psfp_get_last_plan(const psfp_handle*, int* fields, size_t count);
 
 /* ------------------------------------------------------------------------------------------------
  * PSFGPV (gpv.rs:53-57, impl PSF :59-225)

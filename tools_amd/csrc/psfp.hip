@@ -164,6 +164,7 @@ struct psfp_handle {
   // psfp_samp_p_multi: this handle's window inside the last call (host clock, ms since the call began)
   const std::chrono::steady_clock::time_point* multi_t0 = nullptr;
   double multi_launched_ms = -1.0, multi_done_ms = -1.0;
+  int last_plan[PSFP_PLAN_FIELDS] = {0}; bool has_last_plan = false;      // the forms of the last samp_p pass that ran (psfp_get_last_plan)
 };
 
 // The compact copies follow the key without ever blocking a call: the first small call after a key change launches the two packers on its stream and goes on with
@@ -231,6 +232,17 @@ static int zq_plan(const psfp_handle* h, size_t ncols, int cap) {
   return splits;
 }
 
+// the K splits the Z_q product may take with buffers of leading dimension ld: the partial residues of every split live in dPart, [split][n_pad][ld]
+static int zq_split_cap_for(const psfp_handle* h, size_t ld) {
+  const int nks = (int)(h->K_pad / 64);
+  const size_t per_split = h->n_pad * ld * sizeof(uint64_t);
+  int cap = (int)(((size_t)256 << 20) / per_split);                 // small batches take up to 64 splits, within 256 MB
+  if (cap > 64) cap = 64;
+  const int legacy = zq_plan(h, ld, 8);
+  if (cap < legacy) cap = legacy;
+  return cap > nks ? nks : cap;
+}
+
 static psf_status ensure_batch(psfp_handle* h, size_t B) {
   if (B <= h->Bcap) {
     h->nbj = round_up(B, TR_BN) / TR_BN;
@@ -259,16 +271,8 @@ static psf_status ensure_batch(psfp_handle* h, size_t B) {
   }
   HIP_TRY(hipMalloc(&h->dPf, h->M_pad * ld * sizeof(int32_t)));
   HIP_TRY(hipMalloc(&h->dP8f, 3 * h->K_pad * ld));
-  {  // K splits of the Z_q product (zq_plan): the partial residues of every split live in dPart, [split][n_pad][ld]
-    const int nks = (int)(h->K_pad / 64);
-    const size_t per_split = h->n_pad * ld * sizeof(uint64_t);
-    int cap = (int)(((size_t)256 << 20) / per_split);                 // small batches take up to 64 splits, within 256 MB
-    if (cap > 64) cap = 64;
-    const int legacy = zq_plan(h, ld, 8);
-    h->zq_split_cap = cap > legacy ? cap : legacy;
-    if (h->zq_split_cap > nks) h->zq_split_cap = nks;
-    HIP_TRY(hipMalloc(&h->dPart, (size_t)h->zq_split_cap * per_split));
-  }
+  h->zq_split_cap = zq_split_cap_for(h, ld);      // K splits of the Z_q product (zq_plan)
+  HIP_TRY(hipMalloc(&h->dPart, (size_t)h->zq_split_cap * h->n_pad * ld * sizeof(uint64_t)));
   HIP_TRY(hipMalloc(&h->dU, B * h->n * sizeof(uint64_t)));
   HIP_TRY(hipMalloc(&h->dE, B * h->m * sizeof(int64_t)));
   HIP_TRY(hipMalloc(&h->dOk, B));
@@ -1031,19 +1035,21 @@ struct ZqPlan {      // out = (syndrome) U - A P  or  (f_a) A P over ncols preim
   bool fold128 = false, pow2 = false, wave_combine = true;        // k_zq_mfma's template arguments; the splits summed by one wave per output (k_zq_combine_wave)
 };
 
-static ZqPlan plan_zq(const psfp_handle* h, size_t ncols, bool syndrome) {
+// (split_cap: h->zq_split_cap, or what ensure_batch would make it -- the plan query)
+static ZqPlan plan_zq(const psfp_handle* h, size_t ncols, bool syndrome, int split_cap = -1) {
   ZqPlan z;
+  if (split_cap < 0) split_cap = h->zq_split_cap;
   if (syndrome) {  // a handful of preimages: A streamed once as 64-bit words (k_syndrome_small; PSF_SYNDROME_SMALL = largest batch it serves, 0: never)
     size_t small_max = 1;                                             // measured at C3: 39 vs 48 us at one preimage, 52 vs 50 at two, 81 vs 50 at four (64-bit multiply-adds)
     if (const char* e = psf_exp_env("PSF_SYNDROME_SMALL")) small_max = std::min<size_t>((size_t)std::atol(e), 4);
     z.splits = (int)((h->m + SYN_KLEN - 1) / SYN_KLEN);
-    if (ncols <= small_max && z.splits <= h->zq_split_cap && z.splits <= 64) {
+    if (ncols <= small_max && z.splits <= split_cap && z.splits <= 64) {
       z.form = h->dA32 && small_usable(h) ? ZqPlan::SMALL32 : ZqPlan::SMALL;
       return z;
     }
   }
   const int nks = (int)(h->K_pad / 64);
-  z.splits = zq_plan(h, ncols, h->zq_split_cap);
+  z.splits = zq_plan(h, ncols, split_cap);
   z.ks = (nks + z.splits - 1) / z.splits;
   z.fold128 = z.ks <= 32;                                             // short splits (few preimages): one 128-bit fold per output; long ones: the per-class fold
   if (const char* e = psf_exp_env("PSF_ZQ_FOLD128")) z.fold128 = std::atoi(e) != 0;
@@ -1095,10 +1101,13 @@ struct SampPlan {      // every form choice of one samp_p call, with the launch 
   bool small_copies = false, r8 = false;                     // prepare_samp_p: ensure_small_copies, ensure_R8
 };
 
-// The forms of a call of B preimages, from the handle as it stands at the start of the call (after ensure_batch)
-static SampPlan plan_samp_p(const psfp_handle* h, size_t B) {
+struct BatchDims { size_t nbj; int zq_split_cap; };      // what ensure_batch derives from B and the plan reads
+
+// The forms of a call of B preimages, from the handle as it stands at the start of the call (after ensure_batch; psfp_query_plan hands in what ensure_batch would leave)
+static SampPlan plan_samp_p(const psfp_handle* h, size_t B, const BatchDims* bd = nullptr) {
   SampPlan p;
   const size_t m = h->m;
+  const size_t nbj = bd ? bd->nbj : h->nbj;
   // small parameter sets, few preimages (the reference's own benchmarks: n = 8, one call; benches/psf.rs:51-66): the whole call in ONE launch, one
   // workgroup per preimage (k_samp_p_small).  PSF_FUSED_MAX = largest batch it serves (0: never).  Stage exports need the intermediates: not here.
   size_t fused_max = 64;
@@ -1157,7 +1166,7 @@ static SampPlan plan_samp_p(const psfp_handle* h, size_t B) {
   // <= 16 preimages in one fragment: the dense stream of bc = 1, 2, 4, 8, 16 preimages (PSF_COMPACT_D=1 keeps the fragment stream)
   if (p.compact && p.NB == 1 && p.ncg == 1 && !(ecd && std::atoi(ecd) == 1)) { p.bc = 1; while ((size_t)p.bc < B) p.bc <<= 1; }
   p.ncf = p.bc ? 0x100u + (uint32_t)p.bc : p.compact ? (uint32_t)(p.ncg * p.NB) : 0u;
-  const size_t npos = p.bc ? h->nkb * 4 * 4 * (size_t)p.bc : p.ncf ? h->nkb * 4 * (size_t)p.ncf * 64 : h->nbj * h->nkb * TR_CHUNK;
+  const size_t npos = p.bc ? h->nkb * 4 * 4 * (size_t)p.bc : p.ncf ? h->nkb * 4 * (size_t)p.ncf * 64 : nbj * h->nkb * TR_CHUNK;
   p.nseg = nr_segment(npos);
   if (const char* e = psf_exp_env("PSF_NR_SEG")) { const long v = std::atol(e); if (v >= 64 && v <= NR_SEG && v % 64 == 0) p.nseg = (uint32_t)v; }      // positions per wave (experiments)
   p.nwaves = (npos + p.nseg - 1) / p.nseg;
@@ -1165,7 +1174,7 @@ static SampPlan plan_samp_p(const psfp_handle* h, size_t B) {
     p.product = SampPlan::BIG;   // super-tile of an XCD's 32 resident workgroups; PSF_TRMM_GR x PSF_TRMM_GC for experiments (product = 32)
     // below 4096 preimages, or with a number of 128-column blocks that is not a multiple of four: 16 x 2 -- the grid is padded to whole super-columns, and 8 x 4 pays for up
     // to three empty column blocks (round 6, tools/tail_ab.py: 34.9 -> 32.3 ms at 2176, 47.8 -> 44.1 at 3200, 27.2 -> 26.3 at 2048; 51.9 against 52.5 at 4096: 8 x 4 stays there)
-    if (B < 4096 || h->nbj % 4 != 0) { p.GR = 16; p.GC = 2; }
+    if (B < 4096 || nbj % 4 != 0) { p.GR = 16; p.GC = 2; }
     if (const char* e1 = psf_exp_env("PSF_TRMM_GR")) if (const char* e2 = psf_exp_env("PSF_TRMM_GC")) { p.GR = std::atoi(e1); p.GC = std::atoi(e2); }
     if (p.GR < 1 || p.GC < 1 || p.GR * p.GC != 32) { p.GR = 8; p.GC = 4; }
   } else p.product = wg96 ? SampPlan::TILES96 : wg32 ? SampPlan::TILES32 : wg ? SampPlan::TILES64 : SampPlan::TASKS;
@@ -1196,7 +1205,7 @@ static SampPlan plan_samp_p(const psfp_handle* h, size_t B) {
     p.rwaves = (m * B + p.seg - 1) / p.seg;
   } else p.rwaves = (m * B + PR_SEG - 1) / PR_SEG;
   // mp_perturbation.rs:318 -- v = u - A p (the Z_q product unless the fused tail left the shares of A p)
-  p.syn = plan_zq(h, B, true);
+  p.syn = plan_zq(h, B, true, bd ? bd->zq_split_cap : -1);
   p.small_copies |= p.syn.form != ZqPlan::MFMA;
   // mp_perturbation.rs:321-326 -- z <- D_{Lambda_v(G), r sqrt(b^2+1)}
   const size_t nB = h->n * B;
@@ -1254,6 +1263,17 @@ static SampPlan plan_samp_p(const psfp_handle* h, size_t B) {
     }
   }
   return p;
+}
+
+// psfp_query_plan / psfp_get_last_plan: the form choices in the order of include/psf_mi355x.h (PSFP_PLAN_*)
+static_assert(SampPlan::BIG == PSFP_PRODUCT_BIG && SampPlan::TILES96 == PSFP_PRODUCT_TILES96 && SampPlan::TILES64 == PSFP_PRODUCT_TILES64 && SampPlan::ROUND_WAVE == PSFP_ROUND_WAVE &&
+              SampPlan::ROUND_TAB_ROW == PSFP_ROUND_TAB_ROW && ZqPlan::MFMA == PSFP_ZQ_MFMA && ZqPlan::SMALL32 == PSFP_ZQ_SMALL32 && SampPlan::G_LOCKSTEP == PSFP_GADGET_LOCKSTEP &&
+              SampPlan::G_QUAD == PSFP_GADGET_QUAD && SampPlan::R_TILES == PSFP_RECOMBINE_TILES && SampPlan::R_SMALL2 == PSFP_RECOMBINE_SMALL2 && PSFP_PLAN_RSPLITS == 22,
+              "the enumerators of include/psf_mi355x.h follow SampPlan");
+static void plan_fields(const SampPlan& p, int* f) {
+  const int v[PSFP_PLAN_FIELDS] = {p.one_launch, p.product, p.RT, p.NB, p.ncg, p.bc, p.compact, p.GR, p.GC, p.tail, p.round, p.syn.form, p.syn.splits, p.syn.fold128, p.syn.pow2,
+                                   p.syn.wave_combine, p.gadget, p.k32, p.gq_p, p.recombine, p.nbf, p.rc_big, p.rsplits};
+  std::memcpy(f, v, sizeof(v));
 }
 
 // The side effects a plan names, each once per call: the compact copies (built beside the call; a later call's plan finds them usable), room for the fused
@@ -1422,6 +1442,9 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
   psf_status gate_rc = PSF_OK;
   auto u_gate = [&]() { if (h->before_u) { auto f = std::move(h->before_u); h->before_u = nullptr; gate_rc = f(); } };
   SampPlan p = plan_samp_p(h, B);
+  if (!p.one_launch) prepare_samp_p(h, st, p);
+  plan_fields(p, h->last_plan);      // as it runs: prepare_samp_p has had its say on the fused tail
+  h->has_last_plan = true;
   if (p.one_launch) {
     u_gate();
     if (gate_rc != PSF_OK) return gate_rc;
@@ -1429,7 +1452,6 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
     hipLaunchKernelGGL(k_samp_p_small, dim3((unsigned)B), dim3(FS_THREADS), 0, st, seed, first_index, (uint32_t)h->n, (uint32_t)h->k, (uint32_t)h->mb, h->q, h->two64,
                        h->prm.gp.base, h->dLt, h->dA, h->dR, h->ldr, h->szR, GadgetTablesQ{h->dSk, h->dGso, h->dNorm2, h->dSz, h->dRng}, d_u, d_e, h->dFail);
   } else {
-    prepare_samp_p(h, st, p);
     h->normals_ncf = p.ncf;
     normals_stage(h, st, p, seed, first_index, B);
     product_stage(h, st, p, B);
@@ -2075,6 +2097,26 @@ psf_status psf_narrow_rows_dev(const int64_t* d_src, int32_t* d_dst, size_t coun
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(k_narrow_rows, dim3(grid_for(count / 2 + 1, 256, 256 * 16)), dim3(256), 0, (hipStream_t)stream, d_src, d_dst, count, d_overflow);
   HIP_TRY(hipGetLastError());
+  return PSF_OK;
+}
+
+// The plan a samp_p pass over B preimages would take on this handle as it stands: plan_samp_p behind what ensure_batch would derive from B.  Nothing is
+// launched, allocated or changed; the compact key copies count as present only once a call has found them complete (small_state), as for the call itself.
+psf_status psfp_query_plan(const psfp_handle* h, size_t B, int* fields, size_t count) {
+  if (!h || !fields || B == 0 || count < PSFP_PLAN_FIELDS) return PSF_ERR_PARAM;
+  if (!h->has_key || !h->has_pub) return PSF_ERR_NO_KEY;
+  BatchDims bd;
+  bd.nbj = round_up(B, TR_BN) / TR_BN;
+  bd.zq_split_cap = B <= h->Bcap ? h->zq_split_cap : zq_split_cap_for(h, round_up(B, TR_BN));
+  plan_fields(plan_samp_p(h, B, &bd), fields);
+  return PSF_OK;
+}
+
+// The plan of the last samp_p pass this handle ran (a host-pointer call above 2^20 coordinates runs in slices: the last slice's)
+psf_status psfp_get_last_plan(const psfp_handle* h, int* fields, size_t count) {
+  if (!h || !fields || count < PSFP_PLAN_FIELDS) return PSF_ERR_PARAM;
+  if (!h->has_last_plan) return PSF_ERR_NO_KEY;
+  std::memcpy(fields, h->last_plan, sizeof(h->last_plan));
   return PSF_OK;
 }
 

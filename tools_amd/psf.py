@@ -264,6 +264,19 @@ class PSFPerturbation:
     def last_status(self):
         return lib().psfp_last_status(self._h)
 
+    def query_plan(self, B):
+        """The forms a samp_p pass over B preimages would take on this handle as it stands (psfp_query_plan: nothing runs, nothing changes): a dict over
+        PLAN_FIELDS, the form fields as the names of PLAN_ENUMS, the others as integers."""
+        f = (C.c_int * len(PLAN_FIELDS))()
+        check(lib().psfp_query_plan(self._h, C.c_size_t(B), f, C.c_size_t(len(PLAN_FIELDS))), "query_plan")
+        return _plan_dict(f)
+
+    def last_plan(self):
+        """The forms of the last samp_p pass this handle ran (psfp_get_last_plan), as query_plan returns them."""
+        f = (C.c_int * len(PLAN_FIELDS))()
+        check(lib().psfp_get_last_plan(self._h, f, C.c_size_t(len(PLAN_FIELDS))), "last_plan")
+        return _plan_dict(f)
+
     def enable_timing(self, on=True):
         check(lib().psfp_enable_timing(self._h, C.c_int(1 if on else 0)), "enable_timing")
 
@@ -274,6 +287,22 @@ class PSFPerturbation:
         check(lib().psfp_get_timing(self._h, names, C.c_size_t(4096), ms, C.byref(cnt)), "get_timing")
         nm = names.value.decode().split(";") if names.value else []
         return list(zip(nm, list(ms)[:cnt.value]))
+
+
+# psfp_query_plan / psfp_get_last_plan: the fields in the order of the PSFP_PLAN_* indices, and the enumerators of the form fields (include/psf_mi355x.h)
+PLAN_FIELDS = ("one_launch", "product", "RT", "NB", "ncg", "bc", "compact", "GR", "GC", "tail", "round", "syn.form", "syn.splits", "syn.fold128", "syn.pow2",
+               "syn.wave_combine", "gadget", "k32", "gq_p", "recombine", "nbf", "rc_big", "rsplits")
+PLAN_ENUMS = {
+    "product": ("TASKS", "TILES64", "TILES32", "TILES96", "BIG"),
+    "round": ("ROUND_TAB", "ROUND_TAB_ROW", "ROUND_LEAN", "ROUND_WAVE"),
+    "syn.form": ("SMALL", "SMALL32", "MFMA"),
+    "gadget": ("G_WAVE", "G_ROW", "G_QUAD", "G_QUEUE", "G_LOCKSTEP"),
+    "recombine": ("R_SMALL", "R_SMALL2", "R_WG", "R_TILES"),
+}
+
+
+def _plan_dict(fields):
+    return {name: PLAN_ENUMS[name][v] if name in PLAN_ENUMS else int(v) for name, v in zip(PLAN_FIELDS, fields)}
 
 
 def samp_p_multi(psfs, u, seed=0, first_index=0, out=None):
