@@ -209,6 +209,34 @@ psf_status psf_lossy_compress_dev(int device, uint64_t q, uint32_t d, size_t len
 psf_status psf_lossy_decompress_dev(int device, uint64_t q, uint32_t d, size_t len, const void* d_y, void* d_x, int io_bits, void* stream);
 psf_status psf_encode_digits_dev(int device, uint64_t q, uint64_t base, size_t len, const void* d_digits, void* d_out, int io_bits, void* stream);
 psf_status psf_decode_digits_dev(int device, uint64_t q, uint64_t base, size_t len, const void* d_coeffs, void* d_digits, int io_bits, void* stream);
+/* FIPS 203 byte encodings of a flat array of `len` d-bit values, and their fusions with the compression maps above:
+ *   byte_encode       (ByteEncode_d, Algorithm 5, for any len): nbytes = ceil(len d / 8) bytes, the little-endian encoding of
+ *                     sum_i (y_i mod 2^d) 2^(i d): bit j of value i is stream bit i d + j, byte b holds stream bits 8b ... 8b + 7, least significant
+ *                     first.  The unused high bits of a final partial byte are written as 0; no byte at or beyond nbytes is written.
+ *   byte_decode       (ByteDecode_d, Algorithm 6): y_i = stream bits [i d, i d + d).  q = 0: written as they are, in [0, 2^d); q >= 2: written as
+ *                     the least non-negative residue mod q (the m = q rule of ByteDecode_12), and *noncanonical is OR-ed with 1 if any value
+ *                     was >= q (the modulus check of ML-KEM's encapsulation-key validation).  The flag may be NULL, is never cleared by the
+ *                     call, and is never touched when q = 0.
+ *   compress_encode   ByteEncode_d(Compress_d(x)), x read as its residue mod q;
+ *   decode_decompress Decompress_d(ByteDecode_d(bytes)), the least non-negative residue.
+ * For n d a multiple of 8 a flat call over several polynomials is the concatenation of their encodings (32 d bytes each at n = 256).
+ * PSF_ERR_PARAM, in this order: d < 1; io_bits not 16 / 64; a NULL data pointer with len > 0; len d or a byte count that overflows size_t;
+ * an output range that overlaps an input range (no in-place form); q = 1 in byte_decode; q < 2 in the two fused forms.  Then
+ * PSF_ERR_UNSUPPORTED: d > 63; io_bits = 16 with d > 16 or q > 2^16; q >= 2^62.  len = 0 is PSF_OK.  Every check runs before the first HIP
+ * call; nothing is launched or written on an error.  A valid call without a device is PSF_ERR_HIP (no CPU fallback).
+ * Host forms: 64-bit words, allocate per call. */
+psf_status psf_byte_encode(int device, uint32_t d, size_t len, const int64_t* y, uint8_t* bytes);
+psf_status psf_byte_decode(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* bytes, int64_t* y, int* noncanonical);
+psf_status psf_compress_encode(int device, uint64_t q, uint32_t d, size_t len, const uint64_t* x, uint8_t* bytes);
+psf_status psf_decode_decompress(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* bytes, uint64_t* x);
+/* The same on DEVICE buffers, ordered on `stream`, nothing allocated, never synchronising.  io_bits = 64: y int64 (read mod 2^d; written in
+ * [0, 2^d) or [0, q)), x uint64; io_bits = 16: uint16 words, d <= 16, q <= 2^16.  d_noncanonical is a device int (or NULL).  Value buffers need
+ * the alignment of their word, the byte buffer none; whole tiles (8192 16-bit or 2048 64-bit values) move by 16-byte vectors when both
+ * pointers are 16-byte aligned, everything else byte by byte or value by value. */
+psf_status psf_byte_encode_dev(int device, uint32_t d, size_t len, const void* d_y, uint8_t* d_bytes, int io_bits, void* stream);
+psf_status psf_byte_decode_dev(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* d_bytes, void* d_y, int* d_noncanonical, int io_bits, void* stream);
+psf_status psf_compress_encode_dev(int device, uint64_t q, uint32_t d, size_t len, const void* d_x, uint8_t* d_bytes, int io_bits, void* stream);
+psf_status psf_decode_decompress_dev(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* d_bytes, void* d_x, int io_bits, void* stream);
 /* rot_minus_matrix (rotation_matrix.rs:85-96): mat[rows x cols] -> out[rows x rows*cols] */
 psf_status psf_rot_minus_matrix(const int64_t* mat, size_t rows, size_t cols, int64_t* out);
 

@@ -1,6 +1,7 @@
 // psf_compress.hip -- the two other R_q coefficient maps of the ML-KEM-style schemes next to the products of psf_ntt.hip:
 //   FIPS 203 Compress_d / Decompress_d (compression/lossy_compression_fips203.rs:89-112, :143-172) and the message layer
 //   out = digit * floor(q/base) mod q / digit = round(base * c / q) mod base (utils/common_encodings.rs:49-91, :125-151).
+// and the FIPS 203 byte encodings ByteEncode_d / ByteDecode_d (Algorithms 5 / 6) of the d-bit values, alone or fused with Compress_d / Decompress_d.
 // Every map is one pass over a flat array of coefficients: memory-bound streams, 16-byte non-temporal loads and stores per lane.
 // Exact integer arithmetic without a division on the device: the host precomputes the constants of each call (DESIGN.md "Compression and
 // message encodings").
@@ -268,6 +269,296 @@ psf_status map_host(int op, int device, uint64_t q, uint64_t d_or_base, size_t l
   return done(PSF_OK);
 }
 
+
+// ---- FIPS 203 ByteEncode_d / ByteDecode_d (Algorithms 5 / 6) and their fusions with Compress_d / Decompress_d --------------------------------
+// Value i of a flat array owns stream bits [i d, i d + d); byte b holds stream bits [8 b, 8 b + 8), least significant first.  A tile is
+// kTileVec 16-byte vectors of values (8192 16-bit words or 2048 64-bit words): a whole number of 16-byte vectors of packed bytes for every d.
+// Values and bytes move by coalesced 16-byte non-temporal vectors; the bit shuffle between the two layouts goes through LDS (DESIGN.md
+// "Compression and message encodings").  Everything outside whole tiles -- the ragged end, the final partial byte, buffers that are not both
+// 16-byte aligned -- runs byte by byte (pack) or value by value (unpack) from global memory.
+constexpr int kTileVec = 1024;                                          // 4 vectors per lane of a 256-lane workgroup: 16 KiB of values
+enum { UNPACK_RAW = 0, UNPACK_MODQ = 1, UNPACK_DECOMPRESS = 2 };
+
+template <int IO> struct LdsWord { typedef uint16_t type; };
+template <> struct LdsWord<64> { typedef uint64_t type; };
+
+// floor(s / d) without a division: m = floor((2^W - 1) / d) gives floor(s m / 2^W) in {floor(s/d) - 1, floor(s/d)} for every s < 2^W
+// (s/d - s m/2^W = s (2^W - m d) / (d 2^W) <= s / 2^W < 1), and one comparison settles it.
+__device__ __forceinline__ uint32_t div_d32(uint32_t s, uint32_t d, uint32_t m) {
+  const uint32_t t = __umulhi(s, m);
+  return t + ((t + 1) * d <= s);
+}
+__device__ __forceinline__ uint64_t div_d64(uint64_t s, uint32_t d, uint64_t m) {
+  const uint64_t t = __umul64hi(s, m);
+  return t + ((t + 1) * d <= s);
+}
+
+// the d-bit value of one word on its way into the stream: y mod 2^d, or Compress_d(x)
+template <int FUSED, int IO> __device__ __forceinline__ v4u pack_vec(const CmpArgs& a, v4u w) {
+  if constexpr (FUSED) return map_vec<OP_COMPRESS, IO>(a, w);
+  v4u r;
+  if constexpr (IO == 16) {
+    const uint32_t m2 = (uint32_t)a.mask * 0x10001u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = w[j] & m2;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      r[2 * j] = w[2 * j] & (uint32_t)a.mask;
+      r[2 * j + 1] = w[2 * j + 1] & (uint32_t)(a.mask >> 32);
+    }
+  }
+  return r;
+}
+template <int FUSED, int IO> __device__ __forceinline__ uint64_t pack_word(const CmpArgs& a, const void* in, size_t e) {
+  if constexpr (IO == 16) {
+    const uint32_t w = static_cast<const uint16_t*>(in)[e];
+    return FUSED ? map16<OP_COMPRESS>(a, w) : (w & (uint32_t)a.mask);
+  } else {
+    const uint64_t w = static_cast<const uint64_t*>(in)[e];
+    return FUSED ? map64<OP_COMPRESS>(a, w) : (w & a.mask);
+  }
+}
+
+// stream bits [s, s + 32) of a tile from its d-bit values in LDS: values floor(s / d) ... while they start below s + 32
+template <int IO> __device__ __forceinline__ uint32_t gather_dword(const typename LdsWord<IO>::type* vals, uint32_t s, uint32_t d, uint32_t md) {
+  uint32_t idx = div_d32(s, d, md);
+  int pos = (int)(idx * d) - (int)s;                                    // in (-d, 0]: where value idx starts, relative to s
+  uint32_t dw = 0;
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)    // either would divide by d for its trip count
+  for (; pos < 32; ++idx, pos += (int)d) {                              // idx d < s + 32 <= the tile's bits: idx stays inside the tile
+    const uint64_t v = vals[idx];
+    dw |= pos >= 0 ? (uint32_t)(v << pos) : (uint32_t)(v >> -pos);
+  }
+  return dw;
+}
+
+// ByteEncode_d (FUSED = 0) and ByteEncode_d(Compress_d(.)) (FUSED = 1).  Whole tiles: 4 coalesced 16-byte loads per lane, the d-bit values
+// parked in LDS, every lane gathers the tile's output dwords tid, tid + 256, ... (d or d / 4 of them: the same count in every lane), and
+// the staged dwords leave as coalesced 16-byte stores.  Then bytes [tail0, nbytes) one per lane from global memory: whole bytes only, each
+// written by exactly one lane, values at or beyond len read as absent (the unused high bits of the last byte are 0).
+template <int FUSED, int IO>
+__global__ __launch_bounds__(256) void k_pack(CmpArgs a, uint32_t md32, uint64_t md64, const void* __restrict__ in, uint8_t* __restrict__ out, size_t len,
+                                              size_t ntiles, size_t nbytes) {
+  typedef typename LdsWord<IO>::type word_t;
+  constexpr uint32_t TV = kTileVec * (IO == 16 ? 8 : 2);                // values per tile
+  __shared__ v4u s_val[kTileVec];
+  __shared__ v4u s_out[kTileVec];                                       // TV d / 128 vectors: at most 1024 (d = 16) or 1008 (d = 63)
+  const uint32_t tid = threadIdx.x;
+  const uint32_t ndw = TV / 32 * a.d;                                   // packed dwords per tile
+  for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const v4u* vin = static_cast<const v4u*>(in) + t * kTileVec;
+    v4u w[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) w[u] = __builtin_nontemporal_load(vin + tid + 256 * u);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s_val[tid + 256 * u] = pack_vec<FUSED, IO>(a, w[u]);
+    __syncthreads();
+    for (uint32_t k = tid; k < ndw; k += 256)
+      reinterpret_cast<uint32_t*>(s_out)[k] = gather_dword<IO>(reinterpret_cast<const word_t*>(s_val), 32 * k, a.d, md32);
+    __syncthreads();
+    v4u* vout = reinterpret_cast<v4u*>(out + t * (size_t)(TV / 8) * a.d);
+    for (uint32_t j = tid; j < ndw / 4; j += 256) __builtin_nontemporal_store(s_out[j], vout + j);
+  }
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t b = ntiles * (size_t)(TV / 8) * a.d + (size_t)blockIdx.x * blockDim.x + tid; b < nbytes; b += stride) {
+    const uint64_t s = (uint64_t)b * 8;
+    uint64_t idx = div_d64(s, a.d, md64);
+    int pos = (int)(int64_t)(idx * a.d - s);
+    uint32_t by = 0;
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (; pos < 8 && idx < len; ++idx, pos += (int)a.d) {
+      const uint64_t v = pack_word<FUSED, IO>(a, in, idx);
+      by |= pos >= 0 ? (uint32_t)(v << pos) : (uint32_t)(v >> -pos);
+    }
+    out[b] = (uint8_t)by;
+  }
+}
+
+// what ByteDecode_d does with a d-bit value v: nothing, its residue mod q (noting v >= q), or Decompress_d
+template <int MODE, int IO> __device__ __forceinline__ uint64_t unpack_value(const CmpArgs& a, uint64_t v, bool* bad) {
+  if constexpr (MODE == UNPACK_RAW) return v;
+  if constexpr (MODE == UNPACK_MODQ) {
+    *bad |= v >= a.q;
+    if constexpr (IO == 16) return (uint32_t)v - div32_q(a, (uint32_t)v) * (uint32_t)a.q;
+    else return reduce_q(a, v);
+  }
+  if constexpr (IO == 16) return map16<OP_DECOMPRESS>(a, (uint32_t)v);
+  else return map64<OP_DECOMPRESS>(a, v);
+}
+
+// value i of a tile from its packed dwords in LDS (two dwords past the tile may be read; their bits are masked off)
+template <int IO> __device__ __forceinline__ uint64_t extract(const uint32_t* s, uint32_t i, const CmpArgs& a) {
+  const uint32_t bit = i * a.d, wi = bit >> 5, sh = bit & 31;
+  const uint64_t lo = (uint64_t)s[wi] | ((uint64_t)s[wi + 1] << 32);
+  if constexpr (IO == 16) return (uint32_t)(lo >> sh) & (uint32_t)a.mask;                     // sh + d <= 47
+  else return ((lo >> sh) | (((uint64_t)s[wi + 2] << 32) << (32 - sh))) & a.mask;             // sh + d <= 94
+}
+
+// ByteDecode_d (UNPACK_RAW, UNPACK_MODQ) and Decompress_d(ByteDecode_d(.)) (UNPACK_DECOMPRESS): the reverse of k_pack.  Whole tiles: up to 4
+// coalesced 16-byte loads of packed bytes per lane into LDS, then every lane extracts the 8 (16-bit) or 2 (64-bit) values of each of its
+// 4 output vectors and stores them coalesced.  Then values [ntiles TV, len) one per lane from the bytes in global memory.
+template <int MODE, int IO>
+__global__ __launch_bounds__(256) void k_unpack(CmpArgs a, const uint8_t* __restrict__ in, void* __restrict__ out, int* __restrict__ flag, size_t len,
+                                                size_t ntiles) {
+  constexpr uint32_t EPV = IO == 16 ? 8 : 2, TV = kTileVec * EPV;
+  __shared__ v4u s_in[kTileVec + 1];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t nvin = TV / 128 * a.d;                                 // packed 16-byte vectors per tile: at most 1024
+  const uint32_t* sw = reinterpret_cast<const uint32_t*>(s_in);
+  bool bad = false;
+  for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const v4u* vin = reinterpret_cast<const v4u*>(in + t * (size_t)(TV / 8) * a.d);
+    v4u w[4] = {};
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (tid + 256 * u < nvin) w[u] = __builtin_nontemporal_load(vin + tid + 256 * u);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (tid + 256 * u < nvin) s_in[tid + 256 * u] = w[u];
+    __syncthreads();
+    v4u* vout = static_cast<v4u*>(out) + t * kTileVec;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint32_t i0 = (tid + 256 * u) * EPV;
+      v4u r;
+      if constexpr (IO == 16) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t x0 = (uint32_t)unpack_value<MODE, 16>(a, extract<16>(sw, i0 + 2 * j, a), &bad);
+          const uint32_t x1 = (uint32_t)unpack_value<MODE, 16>(a, extract<16>(sw, i0 + 2 * j + 1, a), &bad);
+          r[j] = x0 | (x1 << 16);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const uint64_t x = unpack_value<MODE, 64>(a, extract<64>(sw, i0 + j, a), &bad);
+          r[2 * j] = (uint32_t)x;
+          r[2 * j + 1] = (uint32_t)(x >> 32);
+        }
+      }
+      __builtin_nontemporal_store(r, vout + tid + 256 * u);
+    }
+    __syncthreads();
+  }
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = ntiles * (size_t)TV + (size_t)blockIdx.x * blockDim.x + tid; i < len; i += stride) {
+    const uint64_t bit = (uint64_t)i * a.d;
+    const uint8_t* p = in + (bit >> 3);
+    const int sh = (int)(bit & 7);
+    uint64_t v = 0;
+    for (int k = 0; 8 * k < sh + (int)a.d; ++k) {                       // at most 9 bytes, every one below ceil(len d / 8)
+      const uint64_t by = p[k];
+      const int off = 8 * k - sh;
+      v |= off >= 0 ? by << off : by >> -off;
+    }
+    const uint64_t x = unpack_value<MODE, IO>(a, v & a.mask, &bad);
+    if constexpr (IO == 16) static_cast<uint16_t*>(out)[i] = (uint16_t)x;
+    else static_cast<uint64_t*>(out)[i] = x;
+  }
+  if constexpr (MODE == UNPACK_MODQ) {
+    if (flag && bad) atomicOr(flag, 1);                                 // one vector atomic per lane that met a value >= q
+  }
+}
+
+enum { BY_ENCODE = 0, BY_DECODE = 1, BY_COMPRESS_ENCODE = 2, BY_DECODE_DECOMPRESS = 3 };
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return na && nb && pa < pb + nb && pb < pa + na;
+}
+
+// argument checks of the eight byte-encoding entry points, every PSF_ERR_PARAM before every PSF_ERR_UNSUPPORTED; *nbytes = ceil(len d / 8)
+psf_status check_bytes(int kind, uint64_t q, uint32_t d, size_t len, const void* vals, const void* bytes, int io_bits, size_t* nbytes) {
+  if (d < 1 || (io_bits != 16 && io_bits != 64)) return PSF_ERR_PARAM;
+  if (len && (!vals || !bytes)) return PSF_ERR_PARAM;
+  const size_t wb = (size_t)io_bits / 8;
+  if (len > SIZE_MAX / d || len > SIZE_MAX / wb) return PSF_ERR_PARAM;
+  *nbytes = len * d / 8 + (len * d % 8 != 0);
+  if (ranges_overlap(vals, len * wb, bytes, *nbytes)) return PSF_ERR_PARAM;
+  if (kind == BY_DECODE && q == 1) return PSF_ERR_PARAM;
+  if ((kind == BY_COMPRESS_ENCODE || kind == BY_DECODE_DECOMPRESS) && q < 2) return PSF_ERR_PARAM;
+  if (d > 63 || (io_bits == 16 && d > 16)) return PSF_ERR_UNSUPPORTED;
+  if (kind != BY_ENCODE && ((io_bits == 16 && q > (1ull << 16)) || q >= (1ull << 62))) return PSF_ERR_UNSUPPORTED;
+  return PSF_OK;
+}
+
+// the constants of a call: those of Compress_d / Decompress_d where q is used, d and its mask alone otherwise
+CmpArgs make_byte_args(int kind, uint64_t q, uint32_t d) {
+  if (q >= 2) return make_args(kind == BY_COMPRESS_ENCODE ? OP_COMPRESS : OP_DECOMPRESS, q, d);
+  CmpArgs a{};
+  a.d = d;
+  a.mask = (1ull << d) - 1;
+  return a;
+}
+
+template <int FUSED> void launch_pack(int io_bits, dim3 grid, hipStream_t st, const CmpArgs& a, const void* in, uint8_t* out, size_t len, size_t ntiles, size_t nbytes) {
+  const uint32_t md32 = 0xffffffffu / a.d;
+  const uint64_t md64 = ~0ull / a.d;
+  if (io_bits == 16) hipLaunchKernelGGL((k_pack<FUSED, 16>), grid, dim3(256), 0, st, a, md32, md64, in, out, len, ntiles, nbytes);
+  else hipLaunchKernelGGL((k_pack<FUSED, 64>), grid, dim3(256), 0, st, a, md32, md64, in, out, len, ntiles, nbytes);
+}
+template <int MODE> void launch_unpack(int io_bits, dim3 grid, hipStream_t st, const CmpArgs& a, const uint8_t* in, void* out, int* flag, size_t len, size_t ntiles) {
+  if (io_bits == 16) hipLaunchKernelGGL((k_unpack<MODE, 16>), grid, dim3(256), 0, st, a, in, out, flag, len, ntiles);
+  else hipLaunchKernelGGL((k_unpack<MODE, 64>), grid, dim3(256), 0, st, a, in, out, flag, len, ntiles);
+}
+
+// the launch of checked arguments on device buffers, in `stream`, nothing allocated.  `vals` is the value buffer (read by the two encodes,
+// written by the two decodes), `bytes` the packed one.
+psf_status bytes_dev(int kind, int device, uint64_t q, uint32_t d, size_t len, const void* vals, const void* bytes, size_t nbytes, int* flag, int io_bits,
+                     hipStream_t st) {
+  if (len == 0) return PSF_OK;
+  CMP_TRY(hipSetDevice(device));
+  const int cus = device_cus(device);
+  if (cus <= 0) return PSF_ERR_HIP;
+  const size_t tv = (size_t)kTileVec * (io_bits == 16 ? 8 : 2);
+  const bool pack = kind == BY_ENCODE || kind == BY_COMPRESS_ENCODE;
+  const size_t ntiles = ((uintptr_t)vals % 16 == 0 && (uintptr_t)bytes % 16 == 0) ? len / tv : 0;     // whole tiles need both pointers 16-byte aligned
+  const size_t tail = pack ? nbytes - ntiles * (tv / 8) * d : len - ntiles * tv;                          // bytes (pack) or values (unpack), one per lane
+  size_t blocks = (tail + 255) / 256;
+  if (blocks < ntiles) blocks = ntiles;
+  const size_t cap = (size_t)cus * (pack ? 4 : 8);                      // by LDS: 32 KiB (pack) or 16 KiB (unpack) per workgroup of 4 waves
+  blocks = blocks < 1 ? 1 : blocks > cap ? cap : blocks;
+  const CmpArgs a = make_byte_args(kind, q, d);
+  const dim3 grid((unsigned)blocks);
+  switch (kind) {
+    case BY_ENCODE: launch_pack<0>(io_bits, grid, st, a, vals, (uint8_t*)bytes, len, ntiles, nbytes); break;
+    case BY_COMPRESS_ENCODE: launch_pack<1>(io_bits, grid, st, a, vals, (uint8_t*)bytes, len, ntiles, nbytes); break;
+    case BY_DECODE:
+      if (q == 0) launch_unpack<UNPACK_RAW>(io_bits, grid, st, a, (const uint8_t*)bytes, (void*)vals, nullptr, len, ntiles);
+      else launch_unpack<UNPACK_MODQ>(io_bits, grid, st, a, (const uint8_t*)bytes, (void*)vals, flag, len, ntiles);
+      break;
+    default: launch_unpack<UNPACK_DECOMPRESS>(io_bits, grid, st, a, (const uint8_t*)bytes, (void*)vals, nullptr, len, ntiles); break;
+  }
+  CMP_TRY(hipGetLastError());
+  return PSF_OK;
+}
+
+// host-pointer form: copy in, run on the device (64-bit words), copy out.  No CPU fallback.
+psf_status bytes_host(int kind, int device, uint64_t q, uint32_t d, size_t len, const void* vals, const void* bytes, size_t nbytes, int* noncanonical) {
+  if (len == 0) return PSF_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
+  CMP_TRY(hipSetDevice(device));
+  const bool pack = kind == BY_ENCODE || kind == BY_COMPRESS_ENCODE;
+  const bool flagged = kind == BY_DECODE && q && noncanonical;
+  void *dvals = nullptr, *dbytes = nullptr, *dflag = nullptr;
+  auto done = [&](psf_status s) { (void)hipFree(dvals); (void)hipFree(dbytes); (void)hipFree(dflag); return s; };
+  const size_t vbytes = len * sizeof(uint64_t);
+  if (hipMalloc(&dvals, vbytes) != hipSuccess || hipMalloc(&dbytes, nbytes) != hipSuccess) return done(PSF_ERR_HIP);
+  if (flagged && (hipMalloc(&dflag, sizeof(int)) != hipSuccess || hipMemset(dflag, 0, sizeof(int)) != hipSuccess)) return done(PSF_ERR_HIP);
+  if (hipMemcpy(pack ? dvals : dbytes, pack ? vals : bytes, pack ? vbytes : nbytes, hipMemcpyHostToDevice) != hipSuccess) return done(PSF_ERR_HIP);
+  const psf_status rc = bytes_dev(kind, device, q, d, len, dvals, dbytes, nbytes, (int*)dflag, 64, nullptr);
+  if (rc != PSF_OK) return done(rc);
+  if (hipMemcpy(pack ? (void*)bytes : (void*)vals, pack ? dbytes : dvals, pack ? nbytes : vbytes, hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
+  if (flagged) {
+    int f = 0;
+    if (hipMemcpy(&f, dflag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
+    if (f) *noncanonical |= 1;
+  }
+  return done(PSF_OK);
+}
+
 }  // namespace cmp
 }  // namespace psf
 
@@ -319,6 +610,47 @@ psf_status psf_decode_digits_dev(int device, uint64_t q, uint64_t base, size_t l
   if (rc == PSF_OK) rc = check_common(q, len, d_coeffs, d_digits);
   if (rc == PSF_OK) rc = check_base(q, base, io_bits);
   return rc != PSF_OK ? rc : map_dev(OP_DECODE, device, q, base, len, d_coeffs, d_digits, io_bits, (hipStream_t)stream);
+}
+
+psf_status psf_byte_encode_dev(int device, uint32_t d, size_t len, const void* d_y, uint8_t* d_bytes, int io_bits, void* stream) {
+  size_t nbytes = 0;
+  const psf_status rc = check_bytes(BY_ENCODE, 0, d, len, d_y, d_bytes, io_bits, &nbytes);
+  return rc != PSF_OK ? rc : bytes_dev(BY_ENCODE, device, 0, d, len, d_y, d_bytes, nbytes, nullptr, io_bits, (hipStream_t)stream);
+}
+psf_status psf_byte_decode_dev(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* d_bytes, void* d_y, int* d_noncanonical, int io_bits, void* stream) {
+  size_t nbytes = 0;
+  const psf_status rc = check_bytes(BY_DECODE, q, d, len, d_y, d_bytes, io_bits, &nbytes);
+  return rc != PSF_OK ? rc : bytes_dev(BY_DECODE, device, q, d, len, d_y, d_bytes, nbytes, d_noncanonical, io_bits, (hipStream_t)stream);
+}
+psf_status psf_compress_encode_dev(int device, uint64_t q, uint32_t d, size_t len, const void* d_x, uint8_t* d_bytes, int io_bits, void* stream) {
+  size_t nbytes = 0;
+  const psf_status rc = check_bytes(BY_COMPRESS_ENCODE, q, d, len, d_x, d_bytes, io_bits, &nbytes);
+  return rc != PSF_OK ? rc : bytes_dev(BY_COMPRESS_ENCODE, device, q, d, len, d_x, d_bytes, nbytes, nullptr, io_bits, (hipStream_t)stream);
+}
+psf_status psf_decode_decompress_dev(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* d_bytes, void* d_x, int io_bits, void* stream) {
+  size_t nbytes = 0;
+  const psf_status rc = check_bytes(BY_DECODE_DECOMPRESS, q, d, len, d_x, d_bytes, io_bits, &nbytes);
+  return rc != PSF_OK ? rc : bytes_dev(BY_DECODE_DECOMPRESS, device, q, d, len, d_x, d_bytes, nbytes, nullptr, io_bits, (hipStream_t)stream);
+}
+psf_status psf_byte_encode(int device, uint32_t d, size_t len, const int64_t* y, uint8_t* bytes) {
+  size_t nbytes = 0;
+  const psf_status rc = check_bytes(BY_ENCODE, 0, d, len, y, bytes, 64, &nbytes);
+  return rc != PSF_OK ? rc : bytes_host(BY_ENCODE, device, 0, d, len, y, bytes, nbytes, nullptr);
+}
+psf_status psf_byte_decode(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* bytes, int64_t* y, int* noncanonical) {
+  size_t nbytes = 0;
+  const psf_status rc = check_bytes(BY_DECODE, q, d, len, y, bytes, 64, &nbytes);
+  return rc != PSF_OK ? rc : bytes_host(BY_DECODE, device, q, d, len, y, bytes, nbytes, noncanonical);
+}
+psf_status psf_compress_encode(int device, uint64_t q, uint32_t d, size_t len, const uint64_t* x, uint8_t* bytes) {
+  size_t nbytes = 0;
+  const psf_status rc = check_bytes(BY_COMPRESS_ENCODE, q, d, len, x, bytes, 64, &nbytes);
+  return rc != PSF_OK ? rc : bytes_host(BY_COMPRESS_ENCODE, device, q, d, len, x, bytes, nbytes, nullptr);
+}
+psf_status psf_decode_decompress(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* bytes, uint64_t* x) {
+  size_t nbytes = 0;
+  const psf_status rc = check_bytes(BY_DECODE_DECOMPRESS, q, d, len, x, bytes, 64, &nbytes);
+  return rc != PSF_OK ? rc : bytes_host(BY_DECODE_DECOMPRESS, device, q, d, len, x, bytes, nbytes, nullptr);
 }
 
 }  // extern "C"
