@@ -237,6 +237,42 @@ psf_status psf_byte_encode_dev(int device, uint32_t d, size_t len, const void* d
 psf_status psf_byte_decode_dev(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* d_bytes, void* d_y, int* d_noncanonical, int io_bits, void* stream);
 psf_status psf_compress_encode_dev(int device, uint64_t q, uint32_t d, size_t len, const void* d_x, uint8_t* d_bytes, int io_bits, void* stream);
 psf_status psf_decode_decompress_dev(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* d_bytes, void* d_x, int io_bits, void* stream);
+/* Fills of `count` polynomials of n coefficients with samples (sample_uniform / sample_binomial / sample_discrete_gauss of MatZq,
+ * PolynomialRingZq, MatPolynomialRingZq and MatZ: mp_perturbation.rs:222, trapdoor_distribution.rs, gadget_ring.rs), bound to no handle.
+ * Layout: row-major, polynomial first_index + c at offset c n, constant term first.  Every value is a pure function of (seed, tag, global
+ * polynomial index, coefficient), so filling [0, 8) equals filling [0, 3) and then [3, 8), bit for bit (DESIGN.md "Randomness contract").
+ * `tag` selects the stream: 64 ... 255 are the caller's, 0 ... 63 belong to the library (PSF_ERR_PARAM); two tags under one seed are independent.
+ * The tag word is tag | (index >> 32) << 8, so first_index + count <= 2^56, and the coefficient is a 32-bit counter word, so n < 2^32.
+ *   uniform         on [0, q): multiply-shift with Lemire's rejection, attempt t from Philox block (i, (uint32)index, t, tag word) -- the rule of the
+ *                   keys' a_bar.  Exact for 2 <= q < 2^62.  Words: uint64, or uint16 (io_bits = 16, q <= 2^16).
+ *   cbd             centred binomial, 2 eta trials at p = 1/2 shifted by -eta (the law of FIPS 203's SamplePolyCBD_eta), 1 <= eta <= 16: with
+ *                   s_w = floor(16 / eta), coefficient i is popcount(f & (2^eta - 1)) - popcount(f >> eta) of the 2 eta-bit field
+ *                   f = (word >> 2 eta (i mod s_w)) & (2^(2 eta) - 1), word floor(i / s_w) mod 4 (x, y, z, w) of Philox block
+ *                   (floor(i / (4 s_w)), (uint32)index, 0, tag word).  Words: int64 or int16 -- operand b of psf_matpoly_mul_*_dev.
+ *   discrete_gauss  D_{Z,s,c} by the library's SampleZ (rejection from [ceil(c) - ceil(6 s), floor(c) + floor(6 s)], narrow or wide words by s
+ *                   alone).  d_centers == NULL: the one centre `center` for the whole fill; otherwise count x n doubles, one centre per
+ *                   coefficient (randomised rounding), and `center` is ignored.  Words: int64; int16 with a shared centre and
+ *                   |center| + 6 s + 1 < 2^15.  A draw that ends at the cap of 65 536 attempts writes floor(c + 1/2), a centre with
+ *                   |c| >= 2^62 writes 0; either ORs 1 into *d_fail (a device int, may be NULL, never cleared by the call), and the host form
+ *                   returns PSF_ERR_SAMPLER.
+ * Not offered: binomials with p != 1/2, and the SHAKE-derived byte-exact SampleNTT / SamplePolyCBD of FIPS 203 (different contracts).
+ * PSF_ERR_PARAM, in this order: tag outside 64 ... 255; io_bits not 16 / 64; n = 0 or n >= 2^32; first_index + count > 2^56 or a byte count that
+ * overflows size_t; a NULL output pointer with count > 0; q < 2; eta = 0; s not finite or s <= 0; a shared centre that is not finite.  Then
+ * PSF_ERR_UNSUPPORTED: q >= 2^62; io_bits = 16 with q > 2^16; eta > 16; s > 2^28 (the candidate count must fit 32 bits); io_bits = 16 with
+ * per-element centres or a range that does not fit int16.  count = 0 is PSF_OK.  Every check runs before the first HIP call; nothing is launched
+ * or written on an error.  A valid call without a device is PSF_ERR_HIP (no CPU fallback).
+ * Device forms: ordered on `stream`, nothing allocated, never synchronising; the output needs the alignment of its word only. */
+psf_status psf_sample_uniform_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, uint64_t q, void* d_out, int io_bits,
+                                  void* stream);
+psf_status psf_sample_cbd_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, uint32_t eta, void* d_out, int io_bits,
+                              void* stream);
+psf_status psf_sample_discrete_gauss_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, double center,
+                                         const double* d_centers, double s, void* d_out, int* d_fail, int io_bits, void* stream);
+/* Host forms: 64-bit words, allocate per call, run on the device. */
+psf_status psf_sample_uniform(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, uint64_t q, uint64_t* out);
+psf_status psf_sample_cbd(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, uint32_t eta, int64_t* out);
+psf_status psf_sample_discrete_gauss(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, double center,
+                                     const double* centers, double s, int64_t* out);
 /* rot_minus_matrix (rotation_matrix.rs:85-96): mat[rows x cols] -> out[rows x rows*cols] */
 psf_status psf_rot_minus_matrix(const int64_t* mat, size_t rows, size_t cols, int64_t* out);
 
