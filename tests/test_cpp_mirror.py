@@ -51,6 +51,18 @@ def test_host_logic_under_address_and_ub_sanitizers():
     assert r.returncode == 0 and "HOST_SANITIZE_OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
 
 
+def test_stream_split_and_grid_under_address_and_ub_sanitizers():
+    """tools_amd/csrc/psf_stream_host.hpp (no HIP in it): the head / vector / tail split of a flat array and the workgroup count of a pass,
+    swept by tests/cpp/stream_host_check.cpp over every pair of addresses modulo 16, 2- and 8-byte words and every length 0..40."""
+    src = os.path.join(ROOT, "tests", "cpp", "stream_host_check.cpp")
+    exe = os.path.join(ROOT, "tests", "cpp", "stream_host_check")
+    b = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src],
+                       capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "STREAM_HOST_OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
 def test_oracle_under_address_and_ub_sanitizers():
     """The checker itself: oracle/*.c built with gcc -fsanitize=address,undefined and run through one small flow per scheme
     (tests/cpp/oracle_sanitize.c)."""

@@ -127,6 +127,8 @@ def test_every_shape_against_the_composed_route_and_the_model(T, torch):
                     Ac = A[0 if shared else c]
                     assert (M.matpoly_entry(Ac, B[c], q, i, j) == got[c, i, j]).all(), (q, n, rows, inner, cols, c, i, j)
             case += 1
+    A, B = _operands(rng, 3329, 128, 1, 1, 1, 1, 0, 64, wide=False)        # the host-pointer form at a single product of n = 128
+    assert (T.rq.matpoly_mul(A[0], B[0], 3329)[0, 0] == M.matpoly_entry(A[0], B[0], 3329, 0, 0)).all()
 
 
 @pytest.mark.parametrize("q,n,io", [(3329, 256, 64), (3329, 256, 16), (12289, 1024, 64), (12289, 1024, 16), (2013265921, 256, 64)])

@@ -66,6 +66,10 @@ def test_dev_products_equal_schoolbook_and_big_integers(T, torch):
             T.gadget.poly_mul_negacyclic_dev(a16.data_ptr(), b16.data_ptr(), o16.data_ptr(), q, n, count, 16)
             torch.cuda.synchronize()
             assert (o16.cpu().numpy().view(np.uint16).astype(np.uint64) == want).all(), (q, n, 16)
+    a = rng.integers(0, 3329, size=(1, 128), dtype=np.uint64)              # the host-pointer form at a single product
+    b = rng.integers(-3328, 3329, size=(1, 128), dtype=np.int64)
+    for method in (None, 0, 1):
+        assert T.gadget.poly_mul_negacyclic(a, b, 3329, method=method)[0].tolist() == big_product(a[0], b[0], 128, 3329), method
 
 
 def test_unreduced_64_bit_operands(T, torch):

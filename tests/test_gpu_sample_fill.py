@@ -310,6 +310,12 @@ def test_host_forms_equal_the_device_forms(T, torch):
     d_cen = torch.from_numpy(cen).cuda()
     dev = fill(T, torch, "gauss", count, n, 64, s=8.0, d_centers=d_cen.data_ptr(), seed=SEED, tag=130, first_index=first)
     assert np.array_equal(T.sample.sample_discrete_gauss(count, n, 8.0, SEED, centers=cen, tag=130, first_index=first), dev)
+    for n in (1, 7, 9):                                                 # below one 16-byte vector, and no whole number of them
+        u, c, g, gw = _three(T, torch, 1, n, first, 130)
+        assert np.array_equal(T.sample.sample_uniform(1, n, 3329, SEED, tag=130, first_index=first), u), n
+        assert np.array_equal(T.sample.sample_cbd(1, n, 3, SEED, tag=130, first_index=first), c), n
+        assert np.array_equal(T.sample.sample_discrete_gauss(1, n, 8.0, SEED, center=0.5, tag=130, first_index=first), g), n
+        assert np.array_equal(T.sample.sample_discrete_gauss(1, n, 400.0, SEED, center=0.5, tag=130, first_index=first), gw), n
 
 
 # ---- composition ------------------------------------------------------------------------------------------------------------------------------------

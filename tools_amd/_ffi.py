@@ -91,6 +91,11 @@ def lib():
     return _lib
 
 
+def _p(a, t):
+    """The data of a contiguous numpy array as a ctypes pointer to t."""
+    return a.ctypes.data_as(C.POINTER(t))
+
+
 def check(status, where=""):
     if status != OK:
         raise PsfError(status, where)

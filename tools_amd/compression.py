@@ -7,11 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import check, lib
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+from ._ffi import _p, check, lib
 
 
 def _residues(x, q):

@@ -5,25 +5,13 @@
 // Every map is one pass over a flat array of coefficients: memory-bound streams, 16-byte non-temporal loads and stores per lane.
 // Exact integer arithmetic without a division on the device: the host precomputes the constants of each call (DESIGN.md "Compression and
 // message encodings").
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include <mutex>
-#include "../../include/psf_mi355x.h"
-
-#define CMP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e__ = (expr);                                                           \
-    if (e__ != hipSuccess) {                                                           \
-      std::fprintf(stderr, "[psf_mi355x] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return PSF_ERR_HIP;                                                              \
-    }                                                                                  \
-  } while (0)
+#include "psf_hip_util.hpp"
+#include "psf_stream_host.hpp"
 
 namespace psf {
 namespace cmp {
 
 typedef unsigned __int128 u128;
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
 enum { OP_COMPRESS = 0, OP_DECOMPRESS = 1, OP_ENCODE = 2, OP_DECODE = 3 };
 
@@ -207,68 +195,51 @@ CmpArgs make_args(int op, uint64_t q, uint64_t d_or_base) {
   return a;
 }
 
-// compute units of a device, queried once
-int device_cus(int device) {
-  static std::mutex mu;
-  static int cus[64] = {0};
-  if (device < 0 || device >= 64) return 0;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!cus[device] && hipDeviceGetAttribute(&cus[device], hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus[device] = 0;
-  return cus[device];
-}
-
-template <int OP> void launch_op(int io_bits, dim3 grid, hipStream_t st, const CmpArgs& a, const void* in, void* out, size_t len, size_t head, size_t nvec) {
-  if (io_bits == 16) hipLaunchKernelGGL((k_coeff_map<OP, 16>), grid, dim3(256), 0, st, a, in, out, len, head, nvec);
-  else hipLaunchKernelGGL((k_coeff_map<OP, 64>), grid, dim3(256), 0, st, a, in, out, len, head, nvec);
-}
-
 // the launch of checked arguments on device buffers, in `stream`, nothing allocated
 psf_status map_dev(int op, int device, uint64_t q, uint64_t d_or_base, size_t len, const void* in, void* out, int io_bits, hipStream_t st) {
   if (len == 0) return PSF_OK;
-  CMP_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   const int cus = device_cus(device);
   if (cus <= 0) return PSF_ERR_HIP;
   const size_t wb = (size_t)io_bits / 8, epv = 16 / wb;
-  const uintptr_t pi = (uintptr_t)in, po = (uintptr_t)out;
-  size_t head = len, nvec = 0;
-  if (pi % wb == 0 && pi % 16 == po % 16) {                             // both reach a 16-byte boundary after the same number of words
-    head = ((16 - pi % 16) % 16) / wb;
-    if (head > len) head = len;
-    nvec = (len - head) / epv;
-  }
-  const size_t vwork = (nvec + kUnroll - 1) / kUnroll, swork = len - nvec * epv, work = vwork > swork ? vwork : swork;
-  size_t blocks = (work + 255) / 256;
-  const size_t cap = (size_t)cus * 8;                                   // 8 workgroups of 256 lanes per CU: 8 waves per SIMD
-  blocks = blocks < 1 ? 1 : blocks > cap ? cap : blocks;
+  const StreamSplit sp = split_stream_pair((uintptr_t)in, (uintptr_t)out, wb, len, epv);
+  const size_t head = sp.head, nvec = sp.nvec;
+  const size_t vwork = (nvec + kUnroll - 1) / kUnroll, swork = len - nvec * epv;
+  const dim3 grid(grid_blocks(vwork > swork ? vwork : swork, 0, cus, 8));      // 8 workgroups of 256 lanes per CU: 8 waves per SIMD
   const CmpArgs a = make_args(op, q, d_or_base);
-  const dim3 grid((unsigned)blocks);
-  switch (op) {
-    case OP_COMPRESS: launch_op<OP_COMPRESS>(io_bits, grid, st, a, in, out, len, head, nvec); break;
-    case OP_DECOMPRESS: launch_op<OP_DECOMPRESS>(io_bits, grid, st, a, in, out, len, head, nvec); break;
-    case OP_ENCODE: launch_op<OP_ENCODE>(io_bits, grid, st, a, in, out, len, head, nvec); break;
-    default: launch_op<OP_DECODE>(io_bits, grid, st, a, in, out, len, head, nvec); break;
-  }
-  CMP_TRY(hipGetLastError());
+  for_int<16, 64>(io_bits, [&](auto io) {
+    for_int<OP_COMPRESS, OP_DECOMPRESS, OP_ENCODE, OP_DECODE>(op, [&](auto o) {
+      hipLaunchKernelGGL((k_coeff_map<decltype(o)::value, decltype(io)::value>), grid, dim3(256), 0, st, a, in, out, len, head, nvec);
+    });
+  });
+  HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
 
 // host-pointer form: copy in, run on the device (64-bit words), copy out.  No CPU fallback.
 psf_status map_host(int op, int device, uint64_t q, uint64_t d_or_base, size_t len, const void* in, void* out) {
   if (len == 0) return PSF_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
-  CMP_TRY(hipSetDevice(device));
-  void *din = nullptr, *dout = nullptr;
-  auto done = [&](psf_status s) { (void)hipFree(din); (void)hipFree(dout); return s; };
+  const psf_status ud = use_device(device);
+  if (ud != PSF_OK) return ud;
   const size_t bytes = len * sizeof(uint64_t);
-  if (hipMalloc(&din, bytes) != hipSuccess || hipMalloc(&dout, bytes) != hipSuccess) return done(PSF_ERR_HIP);
-  if (hipMemcpy(din, in, bytes, hipMemcpyHostToDevice) != hipSuccess) return done(PSF_ERR_HIP);
-  const psf_status rc = map_dev(op, device, q, d_or_base, len, din, dout, 64, nullptr);
-  if (rc != PSF_OK) return done(rc);
-  if (hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
-  return done(PSF_OK);
+  DevBuf din, dout;
+  HIP_TRY(din.alloc(bytes));
+  HIP_TRY(dout.alloc(bytes));
+  HIP_TRY(din.upload(in, bytes));
+  const psf_status rc = map_dev(op, device, q, d_or_base, len, din.as<void>(), dout.as<void>(), 64, nullptr);
+  if (rc != PSF_OK) return rc;
+  HIP_TRY(dout.download(out, bytes));
+  return PSF_OK;
 }
 
+// the four maps behind their entry points: the checks in the header's order, then the device form in `st` or (host) the host-pointer form
+psf_status map_call(int op, int device, uint64_t q, uint64_t d_or_base, size_t len, const void* in, void* out, int io_bits, void* st, bool host = false) {
+  psf_status rc = check_io(io_bits);
+  if (rc == PSF_OK) rc = check_common(q, len, in, out);
+  if (rc == PSF_OK) rc = op == OP_COMPRESS || op == OP_DECOMPRESS ? check_d(q, (uint32_t)d_or_base, io_bits) : check_base(q, d_or_base, io_bits);
+  if (rc != PSF_OK) return rc;
+  return host ? map_host(op, device, q, d_or_base, len, in, out) : map_dev(op, device, q, d_or_base, len, in, out, io_bits, (hipStream_t)st);
+}
 
 // ---- FIPS 203 ByteEncode_d / ByteDecode_d (Algorithms 5 / 6) and their fusions with Compress_d / Decompress_d --------------------------------
 // Value i of a flat array owns stream bits [i d, i d + d); byte b holds stream bits [8 b, 8 b + 8), least significant first.  A tile is
@@ -492,71 +463,77 @@ CmpArgs make_byte_args(int kind, uint64_t q, uint32_t d) {
   return a;
 }
 
-template <int FUSED> void launch_pack(int io_bits, dim3 grid, hipStream_t st, const CmpArgs& a, const void* in, uint8_t* out, size_t len, size_t ntiles, size_t nbytes) {
-  const uint32_t md32 = 0xffffffffu / a.d;
-  const uint64_t md64 = ~0ull / a.d;
-  if (io_bits == 16) hipLaunchKernelGGL((k_pack<FUSED, 16>), grid, dim3(256), 0, st, a, md32, md64, in, out, len, ntiles, nbytes);
-  else hipLaunchKernelGGL((k_pack<FUSED, 64>), grid, dim3(256), 0, st, a, md32, md64, in, out, len, ntiles, nbytes);
-}
-template <int MODE> void launch_unpack(int io_bits, dim3 grid, hipStream_t st, const CmpArgs& a, const uint8_t* in, void* out, int* flag, size_t len, size_t ntiles) {
-  if (io_bits == 16) hipLaunchKernelGGL((k_unpack<MODE, 16>), grid, dim3(256), 0, st, a, in, out, flag, len, ntiles);
-  else hipLaunchKernelGGL((k_unpack<MODE, 64>), grid, dim3(256), 0, st, a, in, out, flag, len, ntiles);
-}
-
 // the launch of checked arguments on device buffers, in `stream`, nothing allocated.  `vals` is the value buffer (read by the two encodes,
 // written by the two decodes), `bytes` the packed one.
 psf_status bytes_dev(int kind, int device, uint64_t q, uint32_t d, size_t len, const void* vals, const void* bytes, size_t nbytes, int* flag, int io_bits,
                      hipStream_t st) {
   if (len == 0) return PSF_OK;
-  CMP_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   const int cus = device_cus(device);
   if (cus <= 0) return PSF_ERR_HIP;
   const size_t tv = (size_t)kTileVec * (io_bits == 16 ? 8 : 2);
   const bool pack = kind == BY_ENCODE || kind == BY_COMPRESS_ENCODE;
   const size_t ntiles = ((uintptr_t)vals % 16 == 0 && (uintptr_t)bytes % 16 == 0) ? len / tv : 0;     // whole tiles need both pointers 16-byte aligned
   const size_t tail = pack ? nbytes - ntiles * (tv / 8) * d : len - ntiles * tv;                          // bytes (pack) or values (unpack), one per lane
-  size_t blocks = (tail + 255) / 256;
-  if (blocks < ntiles) blocks = ntiles;
-  const size_t cap = (size_t)cus * (pack ? 4 : 8);                      // by LDS: 32 KiB (pack) or 16 KiB (unpack) per workgroup of 4 waves
-  blocks = blocks < 1 ? 1 : blocks > cap ? cap : blocks;
+  const dim3 grid(grid_blocks(tail, ntiles, cus, pack ? 4 : 8));        // by LDS: 32 KiB (pack) or 16 KiB (unpack) per workgroup of 4 waves
   const CmpArgs a = make_byte_args(kind, q, d);
-  const dim3 grid((unsigned)blocks);
-  switch (kind) {
-    case BY_ENCODE: launch_pack<0>(io_bits, grid, st, a, vals, (uint8_t*)bytes, len, ntiles, nbytes); break;
-    case BY_COMPRESS_ENCODE: launch_pack<1>(io_bits, grid, st, a, vals, (uint8_t*)bytes, len, ntiles, nbytes); break;
-    case BY_DECODE:
-      if (q == 0) launch_unpack<UNPACK_RAW>(io_bits, grid, st, a, (const uint8_t*)bytes, (void*)vals, nullptr, len, ntiles);
-      else launch_unpack<UNPACK_MODQ>(io_bits, grid, st, a, (const uint8_t*)bytes, (void*)vals, flag, len, ntiles);
-      break;
-    default: launch_unpack<UNPACK_DECOMPRESS>(io_bits, grid, st, a, (const uint8_t*)bytes, (void*)vals, nullptr, len, ntiles); break;
-  }
-  CMP_TRY(hipGetLastError());
+  const uint32_t md32 = 0xffffffffu / a.d;
+  const uint64_t md64 = ~0ull / a.d;
+  const int mode = kind == BY_DECODE_DECOMPRESS ? UNPACK_DECOMPRESS : q == 0 ? UNPACK_RAW : UNPACK_MODQ;
+  if (mode != UNPACK_MODQ) flag = nullptr;
+  for_int<16, 64>(io_bits, [&](auto io) {
+    constexpr int IO = decltype(io)::value;
+    if (pack) {
+      for_int<0, 1>(kind == BY_COMPRESS_ENCODE, [&](auto fused) {
+        hipLaunchKernelGGL((k_pack<decltype(fused)::value, IO>), grid, dim3(256), 0, st, a, md32, md64, vals, (uint8_t*)bytes, len, ntiles, nbytes);
+      });
+    } else {
+      for_int<UNPACK_RAW, UNPACK_MODQ, UNPACK_DECOMPRESS>(mode, [&](auto m) {
+        hipLaunchKernelGGL((k_unpack<decltype(m)::value, IO>), grid, dim3(256), 0, st, a, (const uint8_t*)bytes, (void*)vals, flag, len, ntiles);
+      });
+    }
+  });
+  HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
 
 // host-pointer form: copy in, run on the device (64-bit words), copy out.  No CPU fallback.
 psf_status bytes_host(int kind, int device, uint64_t q, uint32_t d, size_t len, const void* vals, const void* bytes, size_t nbytes, int* noncanonical) {
   if (len == 0) return PSF_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
-  CMP_TRY(hipSetDevice(device));
+  const psf_status ud = use_device(device);
+  if (ud != PSF_OK) return ud;
   const bool pack = kind == BY_ENCODE || kind == BY_COMPRESS_ENCODE;
   const bool flagged = kind == BY_DECODE && q && noncanonical;
-  void *dvals = nullptr, *dbytes = nullptr, *dflag = nullptr;
-  auto done = [&](psf_status s) { (void)hipFree(dvals); (void)hipFree(dbytes); (void)hipFree(dflag); return s; };
   const size_t vbytes = len * sizeof(uint64_t);
-  if (hipMalloc(&dvals, vbytes) != hipSuccess || hipMalloc(&dbytes, nbytes) != hipSuccess) return done(PSF_ERR_HIP);
-  if (flagged && (hipMalloc(&dflag, sizeof(int)) != hipSuccess || hipMemset(dflag, 0, sizeof(int)) != hipSuccess)) return done(PSF_ERR_HIP);
-  if (hipMemcpy(pack ? dvals : dbytes, pack ? vals : bytes, pack ? vbytes : nbytes, hipMemcpyHostToDevice) != hipSuccess) return done(PSF_ERR_HIP);
-  const psf_status rc = bytes_dev(kind, device, q, d, len, dvals, dbytes, nbytes, (int*)dflag, 64, nullptr);
-  if (rc != PSF_OK) return done(rc);
-  if (hipMemcpy(pack ? (void*)bytes : (void*)vals, pack ? dbytes : dvals, pack ? nbytes : vbytes, hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
+  DevBuf dvals, dbytes, dflag;
+  HIP_TRY(dvals.alloc(vbytes));
+  HIP_TRY(dbytes.alloc(nbytes));
+  if (flagged) {
+    HIP_TRY(dflag.alloc(sizeof(int)));
+    HIP_TRY(dflag.zero(sizeof(int)));
+  }
+  if (pack) HIP_TRY(dvals.upload(vals, vbytes));
+  else HIP_TRY(dbytes.upload(bytes, nbytes));
+  const psf_status rc = bytes_dev(kind, device, q, d, len, dvals.as<void>(), dbytes.as<void>(), nbytes, dflag.as<int>(), 64, nullptr);
+  if (rc != PSF_OK) return rc;
+  if (pack) HIP_TRY(dbytes.download((void*)bytes, nbytes));
+  else HIP_TRY(dvals.download((void*)vals, vbytes));
   if (flagged) {
     int f = 0;
-    if (hipMemcpy(&f, dflag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
+    HIP_TRY(dflag.download(&f, sizeof(int)));
     if (f) *noncanonical |= 1;
   }
-  return done(PSF_OK);
+  return PSF_OK;
+}
+
+// the four byte forms behind their entry points: the checks, then the device form in `st` or (host) the host-pointer form
+psf_status bytes_call(int kind, int device, uint64_t q, uint32_t d, size_t len, const void* vals, const void* bytes, int* flag, int io_bits, void* st,
+                      bool host = false) {
+  size_t nbytes = 0;
+  const psf_status rc = check_bytes(kind, q, d, len, vals, bytes, io_bits, &nbytes);
+  if (rc != PSF_OK) return rc;
+  return host ? bytes_host(kind, device, q, d, len, vals, bytes, nbytes, flag)
+              : bytes_dev(kind, device, q, d, len, vals, bytes, nbytes, flag, io_bits, (hipStream_t)st);
 }
 
 }  // namespace cmp
@@ -567,90 +544,53 @@ using namespace psf::cmp;
 extern "C" {
 
 psf_status psf_lossy_compress(int device, uint64_t q, uint32_t d, size_t len, const uint64_t* x, int64_t* y) {
-  psf_status rc = check_common(q, len, x, y);
-  if (rc == PSF_OK) rc = check_d(q, d, 64);
-  return rc != PSF_OK ? rc : map_host(OP_COMPRESS, device, q, d, len, x, y);
+  return map_call(OP_COMPRESS, device, q, d, len, x, y, 64, nullptr, true);
 }
 psf_status psf_lossy_decompress(int device, uint64_t q, uint32_t d, size_t len, const int64_t* y, uint64_t* x) {
-  psf_status rc = check_common(q, len, y, x);
-  if (rc == PSF_OK) rc = check_d(q, d, 64);
-  return rc != PSF_OK ? rc : map_host(OP_DECOMPRESS, device, q, d, len, y, x);
+  return map_call(OP_DECOMPRESS, device, q, d, len, y, x, 64, nullptr, true);
 }
 psf_status psf_encode_digits(int device, uint64_t q, uint64_t base, size_t len, const uint64_t* digits, uint64_t* out) {
-  psf_status rc = check_common(q, len, digits, out);
-  if (rc == PSF_OK) rc = check_base(q, base, 64);
-  return rc != PSF_OK ? rc : map_host(OP_ENCODE, device, q, base, len, digits, out);
+  return map_call(OP_ENCODE, device, q, base, len, digits, out, 64, nullptr, true);
 }
 psf_status psf_decode_digits(int device, uint64_t q, uint64_t base, size_t len, const uint64_t* coeffs, uint64_t* digits) {
-  psf_status rc = check_common(q, len, coeffs, digits);
-  if (rc == PSF_OK) rc = check_base(q, base, 64);
-  return rc != PSF_OK ? rc : map_host(OP_DECODE, device, q, base, len, coeffs, digits);
+  return map_call(OP_DECODE, device, q, base, len, coeffs, digits, 64, nullptr, true);
 }
-
 psf_status psf_lossy_compress_dev(int device, uint64_t q, uint32_t d, size_t len, const void* d_x, void* d_y, int io_bits, void* stream) {
-  psf_status rc = check_io(io_bits);
-  if (rc == PSF_OK) rc = check_common(q, len, d_x, d_y);
-  if (rc == PSF_OK) rc = check_d(q, d, io_bits);
-  return rc != PSF_OK ? rc : map_dev(OP_COMPRESS, device, q, d, len, d_x, d_y, io_bits, (hipStream_t)stream);
+  return map_call(OP_COMPRESS, device, q, d, len, d_x, d_y, io_bits, stream);
 }
 psf_status psf_lossy_decompress_dev(int device, uint64_t q, uint32_t d, size_t len, const void* d_y, void* d_x, int io_bits, void* stream) {
-  psf_status rc = check_io(io_bits);
-  if (rc == PSF_OK) rc = check_common(q, len, d_y, d_x);
-  if (rc == PSF_OK) rc = check_d(q, d, io_bits);
-  return rc != PSF_OK ? rc : map_dev(OP_DECOMPRESS, device, q, d, len, d_y, d_x, io_bits, (hipStream_t)stream);
+  return map_call(OP_DECOMPRESS, device, q, d, len, d_y, d_x, io_bits, stream);
 }
 psf_status psf_encode_digits_dev(int device, uint64_t q, uint64_t base, size_t len, const void* d_digits, void* d_out, int io_bits, void* stream) {
-  psf_status rc = check_io(io_bits);
-  if (rc == PSF_OK) rc = check_common(q, len, d_digits, d_out);
-  if (rc == PSF_OK) rc = check_base(q, base, io_bits);
-  return rc != PSF_OK ? rc : map_dev(OP_ENCODE, device, q, base, len, d_digits, d_out, io_bits, (hipStream_t)stream);
+  return map_call(OP_ENCODE, device, q, base, len, d_digits, d_out, io_bits, stream);
 }
 psf_status psf_decode_digits_dev(int device, uint64_t q, uint64_t base, size_t len, const void* d_coeffs, void* d_digits, int io_bits, void* stream) {
-  psf_status rc = check_io(io_bits);
-  if (rc == PSF_OK) rc = check_common(q, len, d_coeffs, d_digits);
-  if (rc == PSF_OK) rc = check_base(q, base, io_bits);
-  return rc != PSF_OK ? rc : map_dev(OP_DECODE, device, q, base, len, d_coeffs, d_digits, io_bits, (hipStream_t)stream);
+  return map_call(OP_DECODE, device, q, base, len, d_coeffs, d_digits, io_bits, stream);
 }
 
 psf_status psf_byte_encode_dev(int device, uint32_t d, size_t len, const void* d_y, uint8_t* d_bytes, int io_bits, void* stream) {
-  size_t nbytes = 0;
-  const psf_status rc = check_bytes(BY_ENCODE, 0, d, len, d_y, d_bytes, io_bits, &nbytes);
-  return rc != PSF_OK ? rc : bytes_dev(BY_ENCODE, device, 0, d, len, d_y, d_bytes, nbytes, nullptr, io_bits, (hipStream_t)stream);
+  return bytes_call(BY_ENCODE, device, 0, d, len, d_y, d_bytes, nullptr, io_bits, stream);
 }
 psf_status psf_byte_decode_dev(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* d_bytes, void* d_y, int* d_noncanonical, int io_bits, void* stream) {
-  size_t nbytes = 0;
-  const psf_status rc = check_bytes(BY_DECODE, q, d, len, d_y, d_bytes, io_bits, &nbytes);
-  return rc != PSF_OK ? rc : bytes_dev(BY_DECODE, device, q, d, len, d_y, d_bytes, nbytes, d_noncanonical, io_bits, (hipStream_t)stream);
+  return bytes_call(BY_DECODE, device, q, d, len, d_y, d_bytes, d_noncanonical, io_bits, stream);
 }
 psf_status psf_compress_encode_dev(int device, uint64_t q, uint32_t d, size_t len, const void* d_x, uint8_t* d_bytes, int io_bits, void* stream) {
-  size_t nbytes = 0;
-  const psf_status rc = check_bytes(BY_COMPRESS_ENCODE, q, d, len, d_x, d_bytes, io_bits, &nbytes);
-  return rc != PSF_OK ? rc : bytes_dev(BY_COMPRESS_ENCODE, device, q, d, len, d_x, d_bytes, nbytes, nullptr, io_bits, (hipStream_t)stream);
+  return bytes_call(BY_COMPRESS_ENCODE, device, q, d, len, d_x, d_bytes, nullptr, io_bits, stream);
 }
 psf_status psf_decode_decompress_dev(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* d_bytes, void* d_x, int io_bits, void* stream) {
-  size_t nbytes = 0;
-  const psf_status rc = check_bytes(BY_DECODE_DECOMPRESS, q, d, len, d_x, d_bytes, io_bits, &nbytes);
-  return rc != PSF_OK ? rc : bytes_dev(BY_DECODE_DECOMPRESS, device, q, d, len, d_x, d_bytes, nbytes, nullptr, io_bits, (hipStream_t)stream);
+  return bytes_call(BY_DECODE_DECOMPRESS, device, q, d, len, d_x, d_bytes, nullptr, io_bits, stream);
 }
 psf_status psf_byte_encode(int device, uint32_t d, size_t len, const int64_t* y, uint8_t* bytes) {
-  size_t nbytes = 0;
-  const psf_status rc = check_bytes(BY_ENCODE, 0, d, len, y, bytes, 64, &nbytes);
-  return rc != PSF_OK ? rc : bytes_host(BY_ENCODE, device, 0, d, len, y, bytes, nbytes, nullptr);
+  return bytes_call(BY_ENCODE, device, 0, d, len, y, bytes, nullptr, 64, nullptr, true);
 }
 psf_status psf_byte_decode(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* bytes, int64_t* y, int* noncanonical) {
-  size_t nbytes = 0;
-  const psf_status rc = check_bytes(BY_DECODE, q, d, len, y, bytes, 64, &nbytes);
-  return rc != PSF_OK ? rc : bytes_host(BY_DECODE, device, q, d, len, y, bytes, nbytes, noncanonical);
+  return bytes_call(BY_DECODE, device, q, d, len, y, bytes, noncanonical, 64, nullptr, true);
 }
 psf_status psf_compress_encode(int device, uint64_t q, uint32_t d, size_t len, const uint64_t* x, uint8_t* bytes) {
-  size_t nbytes = 0;
-  const psf_status rc = check_bytes(BY_COMPRESS_ENCODE, q, d, len, x, bytes, 64, &nbytes);
-  return rc != PSF_OK ? rc : bytes_host(BY_COMPRESS_ENCODE, device, q, d, len, x, bytes, nbytes, nullptr);
+  return bytes_call(BY_COMPRESS_ENCODE, device, q, d, len, x, bytes, nullptr, 64, nullptr, true);
 }
 psf_status psf_decode_decompress(int device, uint64_t q, uint32_t d, size_t len, const uint8_t* bytes, uint64_t* x) {
-  size_t nbytes = 0;
-  const psf_status rc = check_bytes(BY_DECODE_DECOMPRESS, q, d, len, x, bytes, 64, &nbytes);
-  return rc != PSF_OK ? rc : bytes_host(BY_DECODE_DECOMPRESS, device, q, d, len, x, bytes, nbytes, nullptr);
+  return bytes_call(BY_DECODE_DECOMPRESS, device, q, d, len, x, bytes, nullptr, 64, nullptr, true);
 }
 
 }  // extern "C"

@@ -1,0 +1,64 @@
+// psf_hip_util.hpp -- what the host side of every HIP translation unit shares: the error macro, the device check, the compute-unit count, an
+// owning device buffer for allocations that live for one call, and the dispatch of a runtime integer to a template argument.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <mutex>
+#include <type_traits>
+#include "../../include/psf_mi355x.h"
+
+#define HIP_TRY(expr)                                                                  \
+  do {                                                                                 \
+    hipError_t e__ = (expr);                                                           \
+    if (e__ != hipSuccess) {                                                           \
+      std::fprintf(stderr, "[psf_mi355x] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+      return PSF_ERR_HIP;                                                              \
+    }                                                                                  \
+  } while (0)
+
+namespace psf {
+
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));              // one 16-byte load or store of a lane
+
+// compute units of a device, queried once
+inline int device_cus(int device) {
+  static std::mutex mu;
+  static int cus[64] = {0};
+  if (device < 0 || device >= 64) return 0;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!cus[device] && hipDeviceGetAttribute(&cus[device], hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus[device] = 0;
+  return cus[device];
+}
+
+// makes `device` current; PSF_ERR_HIP when there is no such device (no CPU fallback)
+inline psf_status use_device(int device) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return PSF_ERR_HIP;
+  HIP_TRY(hipSetDevice(device));
+  return PSF_OK;
+}
+
+// device memory that lives for one call: freed on every exit of the scope.  The operations return the runtime's code, for HIP_TRY.
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { (void)hipFree(p_); p_ = o.p_; o.p_ = nullptr; } return *this; }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { (void)hipFree(p_); }
+  hipError_t alloc(size_t bytes) { (void)hipFree(p_); p_ = nullptr; return hipMalloc(&p_, bytes); }
+  hipError_t upload(const void* src, size_t bytes) { return hipMemcpy(p_, src, bytes, hipMemcpyHostToDevice); }
+  hipError_t download(void* dst, size_t bytes) const { return hipMemcpy(dst, p_, bytes, hipMemcpyDeviceToHost); }
+  hipError_t zero(size_t bytes) { return hipMemset(p_, 0, bytes); }
+  template <class T> T* as() const { return static_cast<T*>(p_); }
+
+ private:
+  void* p_ = nullptr;
+};
+
+// a runtime integer as a template argument: f(ic<V>{}) for the V of the list that equals v; false when none does
+template <int V> using ic = std::integral_constant<int, V>;
+template <int... Vs, class F> bool for_int(int v, F&& f) { return ((v == Vs && (f(ic<Vs>{}), true)) || ...); }
+
+}  // namespace psf

@@ -1,29 +1,18 @@
 // psf_ntt.hip -- NTT products over R_q = Z_q[X]/(X^n + 1) and Z_q[X]/(X^n - 1): plan cache, shape dispatch and launches (psf_ntt_api.hpp).
 // PolynomialRingZq multiplication under gadget_ring.rs:78 and gpv_ring.rs:243-247; the kernels are in psf_ntt_kernels.hpp / psf_ntt_core.hpp.  They read
 // the ring from the table of zetas alone (NttDev::zetas), so the cyclic ring takes the same instantiations with the table of make_ntt_plan_cyclic.
-#include <hip/hip_runtime.h>
-#include <cstdio>
 #include <cstdlib>
 #include <map>
 #include <set>
 #include <mutex>
 #include <tuple>
-#include <type_traits>
+#include "psf_hip_util.hpp"
 #include "psf_host.hpp"
 #include "psf_ntt_api.hpp"
 #include "psf_ntt_kernels.hpp"
 
 using namespace psf;
 using namespace psf::ntt;
-
-#define NTT_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e__ = (expr);                                                           \
-    if (e__ != hipSuccess) {                                                           \
-      std::fprintf(stderr, "[psf_mi355x] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return PSF_ERR_HIP;                                                              \
-    }                                                                                  \
-  } while (0)
 
 namespace {
 
@@ -119,7 +108,6 @@ Plan* plan_for(int device, uint64_t q, size_t n, psf_status* st, NttRing ring = 
   return P->route ? P : nullptr;
 }
 
-template <int V> using ic = std::integral_constant<int, V>;
 // the shapes that have a wave kernel (make_ntt_tables decides logn, ld, qb)
 template <class F> bool for_shape(int logn, int ld, int qb, F&& f) {
 #define PSF_SHAPE(LN, LDV, QBV) if (logn == LN && ld == LDV && qb == QBV) { f(ic<LN>{}, ic<LDV>{}, ic<QBV>{}); return true; }
@@ -164,7 +152,7 @@ psf_status ntt_polymul_dev(int device, uint64_t q, size_t n, size_t count, const
   Plan* P = plan_for(device, q, n, &rc, ring);
   if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
   if (count == 0) return PSF_OK;
-  NTT_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   if (P->route == 1) {
     if (io_bits != 64) return PSF_ERR_UNSUPPORTED;
     const NttDev a = dev_args(P, 1, 1);
@@ -174,13 +162,13 @@ psf_status ntt_polymul_dev(int device, uint64_t q, size_t n, size_t count, const
       static std::mutex mu; static std::set<int> raised;
       std::lock_guard<std::mutex> lk(mu);
       if (!raised.count(device)) {
-        NTT_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_polymul_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_polymul_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         raised.insert(device);
       }
     }
     hipLaunchKernelGGL(k_ntt_polymul_lds, dim3((unsigned)(count > 4096 ? 4096 : count)), dim3(256), smem, st, a, (uint32_t)n, P->pl.L, P->pl.d,
                        (const uint64_t*)d_a, (const int64_t*)d_b, (uint64_t*)d_out, count);
-    NTT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return PSF_OK;
   }
   if (io_bits == 16 && P->tb.qb == 0) return PSF_ERR_UNSUPPORTED;
@@ -193,7 +181,7 @@ psf_status ntt_polymul_dev(int device, uint64_t q, size_t n, size_t count, const
     hipLaunchKernelGGL((k_ntt_polymul<LN, LDV, QBV, 64>), dim3(wave_grid(count)), dim3(256), 0, st, a, d_a, d_b, d_out, count);
   });
   if (!ok) return PSF_ERR_UNSUPPORTED;
-  NTT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
 
@@ -205,7 +193,7 @@ psf_status ntt_forward_dev(int device, uint64_t q, size_t n, size_t count, const
   if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
   if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
   if (count == 0) return PSF_OK;
-  NTT_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
     constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
     const NttDev a = dev_args(P, 1, 1);
@@ -215,7 +203,7 @@ psf_status ntt_forward_dev(int device, uint64_t q, size_t n, size_t count, const
     hipLaunchKernelGGL((k_ntt_forward<LN, LDV, QBV, 64, false>), dim3(wave_grid(count)), dim3(256), 0, st, a, d_a, d_hat, count);
   });
   if (!ok) return PSF_ERR_UNSUPPORTED;                      // route 2 without an instantiated shape: nothing was launched
-  NTT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
 
@@ -228,7 +216,7 @@ psf_status ntt_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, const
   if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
   if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
   if (count == 0) return PSF_OK;
-  NTT_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
     constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
     const NttDev a = dev_args(P, Kern<LN, LDV, QBV>::E, Kern<LN, LDV, QBV>::E + 1);
@@ -238,7 +226,7 @@ psf_status ntt_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, const
     hipLaunchKernelGGL((k_ntt_mul_hat<LN, LDV, QBV, 64>), dim3(wave_grid(count)), dim3(256), 0, st, a, d_hat, hat_stride, d_b, d_out, count);
   });
   if (!ok) return PSF_ERR_UNSUPPORTED;                      // route 2 without an instantiated shape: nothing was launched
-  NTT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
 
@@ -250,14 +238,14 @@ psf_status ntt_ring_fa_dev(int device, uint64_t q, size_t n, uint32_t K, const u
   const size_t smem = (((P->tb.qb == 12 ? 4u : 2u) << P->pl.L) + (size_t)K * n) * sizeof(uint32_t);
   if (P->route != 2 || smem > 64 * 1024) return PSF_ERR_UNSUPPORTED;
   if (B == 0) return PSF_OK;
-  NTT_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
     constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
     const NttDev a = dev_args(P, Kern<LN, LDV, QBV>::E, Kern<LN, LDV, QBV>::E + 1);
     hipLaunchKernelGGL((k_ring_fa<LN, LDV, QBV>), dim3(wave_grid(B)), dim3(256), smem, st, a, d_hat, K, d_sigma, d_u, B);
   });
   if (!ok) return PSF_ERR_UNSUPPORTED;                      // route 2 without an instantiated shape: nothing was launched
-  NTT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
 
@@ -271,7 +259,7 @@ psf_status ntt_matmul_dev(int device, uint64_t q, size_t n, const NttMatShape& s
   const size_t zn = (P->tb.qb == 12 ? 4u : 2u) << P->pl.L;
   const bool stage = hat && a_stride == 0 && (zn + s.rows * s.inner * n) * sizeof(uint32_t) <= 64 * 1024;   // one A for all: its images in LDS
   if (s.count == 0) return PSF_OK;
-  NTT_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
     constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
     const NttDev a = dev_args(P, Kern<LN, LDV, QBV>::E, Kern<LN, LDV, QBV>::E + 1);
@@ -295,7 +283,7 @@ psf_status ntt_matmul_dev(int device, uint64_t q, size_t n, const NttMatShape& s
     go(ic<64>{});
   });
   if (!ok) return PSF_ERR_UNSUPPORTED;                      // route 2 without an instantiated shape: nothing was launched
-  NTT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
 

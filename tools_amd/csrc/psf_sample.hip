@@ -5,27 +5,14 @@
 // (seed, tag, global polynomial index, coefficient) through the randomness contract of psf_rng.hpp (DESIGN.md "Randomness contract"), so a
 // fill of [0, 8) is the fill of [0, 3) followed by the fill of [3, 8).  No division by a runtime value on the device: the host passes
 // multipliers (div_u64 / div_u32 below), the Lemire thresholds and the constants of SampleZ.
-#include <hip/hip_runtime.h>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <mutex>
-#include "../../include/psf_mi355x.h"
+#include "psf_hip_util.hpp"
+#include "psf_stream_host.hpp"
 #include "psf_rng.hpp"
-
-#define SMP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e__ = (expr);                                                           \
-    if (e__ != hipSuccess) {                                                           \
-      std::fprintf(stderr, "[psf_mi355x] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return PSF_ERR_HIP;                                                              \
-    }                                                                                  \
-  } while (0)
 
 namespace psf {
 namespace smp {
-
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
 // floor(s / d) without a division: m = floor((2^W - 1) / d) gives floor(s m / 2^W) in {floor(s/d) - 1, floor(s/d)} for every s < 2^W
 // (s/d - s m/2^W = s (2^W - m d) / (d 2^W) <= s / 2^W < 1), and one comparison settles it.
@@ -381,16 +368,6 @@ __global__ __launch_bounds__(256) void k_fill_gauss(FillArgs a, SampleZParams sp
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
 
-// compute units of a device, queried once
-int device_cus(int device) {
-  static std::mutex mu;
-  static int cus[64] = {0};
-  if (device < 0 || device >= 64) return 0;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!cus[device] && hipDeviceGetAttribute(&cus[device], hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus[device] = 0;
-  return cus[device];
-}
-
 // the checks every fill shares, in the order of the header; *total = count n
 psf_status check_fill(uint32_t tag, int io_bits, uint64_t first_index, size_t count, size_t n, const void* out, size_t* total) {
   if (tag < 64 || tag > 255) return PSF_ERR_PARAM;
@@ -408,47 +385,33 @@ FillArgs fill_args(uint64_t seed, uint32_t tag, uint64_t first_index, size_t n) 
   return FillArgs{seed, first_index, tag, Shape{(uint64_t)n, ~0ull / (uint64_t)n}};
 }
 
-// words before the first 16-byte boundary of `out` (at most `total`)
-size_t head_words(const void* out, size_t wb, size_t total) {
-  const size_t h = ((16 - (uintptr_t)out % 16) % 16) / wb;
-  return h < total ? h : total;
-}
-
-unsigned grid_blocks(size_t work, int cus) {
-  size_t blocks = (work + 255) / 256;
-  const size_t cap = (size_t)cus * 8;                                   // 8 workgroups of 256 lanes per CU: 8 waves per SIMD
-  return (unsigned)(blocks < 1 ? 1 : blocks > cap ? cap : blocks);
-}
-
 psf_status uniform_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t n, size_t total, uint64_t q, void* out, int io_bits, hipStream_t st) {
   if (total == 0) return PSF_OK;
-  SMP_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   const int cus = device_cus(device);
   if (cus <= 0) return PSF_ERR_HIP;
   const size_t wb = (size_t)io_bits / 8, epv = 16 / wb;
-  const size_t head = head_words(out, wb, total), nvec = (total - head) / epv;
-  const size_t swork = total - nvec * epv;
-  const dim3 grid(grid_blocks(nvec > swork ? nvec : swork, cus));
+  const StreamSplit sp = split_stream((uintptr_t)out, wb, total, epv);
+  const size_t head = sp.head, nvec = sp.nvec, swork = total - nvec * epv;
+  const dim3 grid(grid_blocks(nvec > swork ? nvec : swork, 0, cus, 8));      // 8 workgroups of 256 lanes per CU: 8 waves per SIMD
   const FillArgs a = fill_args(seed, tag, first_index, n);
   const uint64_t thr = (0 - q) % q;
-  if (io_bits == 16) hipLaunchKernelGGL((k_fill_uniform<16>), grid, dim3(256), 0, st, a, q, thr, out, total, head, nvec);
-  else hipLaunchKernelGGL((k_fill_uniform<64>), grid, dim3(256), 0, st, a, q, thr, out, total, head, nvec);
-  SMP_TRY(hipGetLastError());
+  for_int<16, 64>(io_bits, [&](auto io) {
+    hipLaunchKernelGGL((k_fill_uniform<decltype(io)::value>), grid, dim3(256), 0, st, a, q, thr, out, total, head, nvec);
+  });
+  HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
 
 psf_status cbd_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t n, size_t total, uint32_t eta, void* out, int io_bits, hipStream_t st) {
   if (total == 0) return PSF_OK;
-  SMP_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   const int cus = device_cus(device);
   if (cus <= 0) return PSF_ERR_HIP;
   const size_t wb = (size_t)io_bits / 8, tv = (size_t)kTileVec * (16 / wb);
-  const size_t head = head_words(out, wb, total), ntiles = (total - head) / tv;
-  const size_t rest = total - ntiles * tv;
-  size_t blocks = (rest + 255) / 256;
-  if (blocks < ntiles) blocks = ntiles;
-  const size_t cap = (size_t)cus * 8;                                   // 16 KiB of LDS per workgroup of 4 waves
-  blocks = blocks < 1 ? 1 : blocks > cap ? cap : blocks;
+  const StreamSplit sp = split_stream((uintptr_t)out, wb, total, tv);      // head words first, then whole tiles
+  const size_t head = sp.head, ntiles = sp.nvec;
+  const dim3 grid(grid_blocks(total - ntiles * tv, ntiles, cus, 8));      // 16 KiB of LDS per workgroup of 4 waves
   CbdArgs b{};
   b.eta = eta;
   b.sw = 16 / eta;
@@ -461,10 +424,10 @@ psf_status cbd_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_index
   b.nblk = ((uint64_t)n + b.bw - 1) / b.bw;
   b.mnblk = ~0ull / b.nblk;
   const FillArgs a = fill_args(seed, tag, first_index, n);
-  const dim3 grid((unsigned)blocks);
-  if (io_bits == 16) hipLaunchKernelGGL((k_fill_cbd<16>), grid, dim3(256), 0, st, a, b, out, total, head, ntiles);
-  else hipLaunchKernelGGL((k_fill_cbd<64>), grid, dim3(256), 0, st, a, b, out, total, head, ntiles);
-  SMP_TRY(hipGetLastError());
+  for_int<16, 64>(io_bits, [&](auto io) {
+    hipLaunchKernelGGL((k_fill_cbd<decltype(io)::value>), grid, dim3(256), 0, st, a, b, out, total, head, ntiles);
+  });
+  HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
 
@@ -480,14 +443,14 @@ uint32_t gauss_segment(size_t total, int cus) {
 psf_status gauss_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t n, size_t total, double center, const double* centers, double s,
                      void* out, int* fail, int io_bits, hipStream_t st) {
   if (total == 0) return PSF_OK;
-  SMP_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   const int cus = device_cus(device);
   if (cus <= 0) return PSF_ERR_HIP;
   const size_t wb = (size_t)io_bits / 8;
   const SampleZParams sp = make_sample_z_params(s);
   SegArgs sg;
   sg.seg = gauss_segment(total, cus);
-  const size_t head = head_words(out, wb, total);
+  const size_t head = head_words((uintptr_t)out, wb, total);
   sg.pad = head ? sg.seg - (uint32_t)head : 0;
   const size_t waves = (total + sg.pad + sg.seg - 1) / sg.seg;
   const dim3 grid((unsigned)((waves + 3) / 4));
@@ -506,13 +469,15 @@ psf_status gauss_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_ind
     tb.N = rg.N;
     tb.thr = rg.thr;
     const size_t lds = (size_t)2 * tb.N * sizeof(uint32_t) + (size_t)4 * sg.seg * sizeof(uint16_t);      // at most 32 + 16 KiB
-    if (io_bits == 16) hipLaunchKernelGGL((k_fill_gauss_tab<16>), grid, dim3(256), lds, st, a, tb, sg, out, fail, total);
-    else hipLaunchKernelGGL((k_fill_gauss_tab<64>), grid, dim3(256), lds, st, a, tb, sg, out, fail, total);
+    for_int<16, 64>(io_bits, [&](auto io) {
+      hipLaunchKernelGGL((k_fill_gauss_tab<decltype(io)::value>), grid, dim3(256), lds, st, a, tb, sg, out, fail, total);
+    });
   } else {
-    if (io_bits == 16) hipLaunchKernelGGL((k_fill_gauss<16>), grid, dim3(256), 0, st, a, sp, center, centers, sg, out, fail, total);
-    else hipLaunchKernelGGL((k_fill_gauss<64>), grid, dim3(256), 0, st, a, sp, center, centers, sg, out, fail, total);
+    for_int<16, 64>(io_bits, [&](auto io) {
+      hipLaunchKernelGGL((k_fill_gauss<decltype(io)::value>), grid, dim3(256), 0, st, a, sp, center, centers, sg, out, fail, total);
+    });
   }
-  SMP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
 
@@ -532,34 +497,56 @@ psf_status check_gauss_support(double center, const double* centers, double s, i
   return PSF_OK;
 }
 
-// host-pointer forms: allocate, run on the device (64-bit words), copy out.  No CPU fallback.
+// The three fills behind their entry points: the checks in the header's order (every PSF_ERR_PARAM before every PSF_ERR_UNSUPPORTED), then the
+// device form in `st`, or (host) the host-pointer form: allocate, run on the device (64-bit words), copy out.  No CPU fallback.
 enum { K_UNIFORM = 0, K_CBD = 1, K_GAUSS = 2 };
-psf_status fill_host(int kind, int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t n, size_t total, uint64_t q, uint32_t eta, double center,
-                     const double* centers, double s, void* out) {
+struct FillSpec { int kind; uint64_t q; uint32_t eta; double center; const double* centers; double s; };
+
+psf_status fill_dev(const FillSpec& f, int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t n, size_t total, void* out, int* fail, int io_bits,
+                    hipStream_t st) {
+  if (f.kind == K_UNIFORM) return uniform_dev(device, seed, tag, first_index, n, total, f.q, out, io_bits, st);
+  if (f.kind == K_CBD) return cbd_dev(device, seed, tag, first_index, n, total, f.eta, out, io_bits, st);
+  return gauss_dev(device, seed, tag, first_index, n, total, f.center, f.centers, f.s, out, fail, io_bits, st);
+}
+
+psf_status fill_host(FillSpec f, int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t n, size_t total, void* out) {
   if (total == 0) return PSF_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
-  SMP_TRY(hipSetDevice(device));
-  void *dout = nullptr, *dcen = nullptr, *dflag = nullptr;
-  auto done = [&](psf_status st) { (void)hipFree(dout); (void)hipFree(dcen); (void)hipFree(dflag); return st; };
+  const psf_status ud = use_device(device);
+  if (ud != PSF_OK) return ud;
   const size_t bytes = total * sizeof(uint64_t);
-  if (hipMalloc(&dout, bytes) != hipSuccess) return done(PSF_ERR_HIP);
-  psf_status rc;
-  if (kind == K_UNIFORM) rc = uniform_dev(device, seed, tag, first_index, n, total, q, dout, 64, nullptr);
-  else if (kind == K_CBD) rc = cbd_dev(device, seed, tag, first_index, n, total, eta, dout, 64, nullptr);
-  else {
-    if (hipMalloc(&dflag, sizeof(int)) != hipSuccess || hipMemset(dflag, 0, sizeof(int)) != hipSuccess) return done(PSF_ERR_HIP);
-    if (centers && (hipMalloc(&dcen, bytes) != hipSuccess || hipMemcpy(dcen, centers, bytes, hipMemcpyHostToDevice) != hipSuccess)) return done(PSF_ERR_HIP);
-    rc = gauss_dev(device, seed, tag, first_index, n, total, center, (const double*)dcen, s, dout, (int*)dflag, 64, nullptr);
+  DevBuf dout, dcen, dflag;
+  HIP_TRY(dout.alloc(bytes));
+  if (f.kind == K_GAUSS) {
+    HIP_TRY(dflag.alloc(sizeof(int)));
+    HIP_TRY(dflag.zero(sizeof(int)));
+    if (f.centers) {
+      HIP_TRY(dcen.alloc(bytes));
+      HIP_TRY(dcen.upload(f.centers, bytes));
+      f.centers = dcen.as<double>();
+    }
   }
-  if (rc != PSF_OK) return done(rc);
-  if (hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
-  if (kind == K_GAUSS) {
-    int f = 0;
-    if (hipMemcpy(&f, dflag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
-    if (f) return done(PSF_ERR_SAMPLER);
+  const psf_status rc = fill_dev(f, device, seed, tag, first_index, n, total, dout.as<void>(), dflag.as<int>(), 64, nullptr);
+  if (rc != PSF_OK) return rc;
+  HIP_TRY(dout.download(out, bytes));
+  if (f.kind == K_GAUSS) {
+    int fl = 0;
+    HIP_TRY(dflag.download(&fl, sizeof(int)));
+    if (fl) return PSF_ERR_SAMPLER;
   }
-  return done(PSF_OK);
+  return PSF_OK;
+}
+
+psf_status fill_call(const FillSpec& f, int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, void* out, int* fail, int io_bits,
+                     void* st, bool host = false) {
+  size_t total = 0;
+  psf_status rc = check_fill(tag, io_bits, first_index, count, n, out, &total);
+  if (rc == PSF_OK && f.kind == K_UNIFORM) rc = f.q < 2 ? PSF_ERR_PARAM : check_uniform(f.q, io_bits);
+  if (rc == PSF_OK && f.kind == K_CBD) rc = f.eta == 0 ? PSF_ERR_PARAM : f.eta > 16 ? PSF_ERR_UNSUPPORTED : PSF_OK;
+  if (rc == PSF_OK && f.kind == K_GAUSS) rc = check_gauss_param(f.center, f.centers, f.s);
+  if (rc == PSF_OK && f.kind == K_GAUSS) rc = check_gauss_support(f.center, f.centers, f.s, io_bits);
+  if (rc != PSF_OK) return rc;
+  return host ? fill_host(f, device, seed, tag, first_index, n, total, out)
+              : fill_dev(f, device, seed, tag, first_index, n, total, out, fail, io_bits, (hipStream_t)st);
 }
 
 }  // namespace smp
@@ -571,50 +558,25 @@ extern "C" {
 
 psf_status psf_sample_uniform_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, uint64_t q, void* d_out, int io_bits,
                                   void* stream) {
-  size_t total = 0;
-  psf_status rc = check_fill(tag, io_bits, first_index, count, n, d_out, &total);
-  if (rc == PSF_OK && q < 2) rc = PSF_ERR_PARAM;
-  if (rc == PSF_OK) rc = check_uniform(q, io_bits);
-  return rc != PSF_OK ? rc : uniform_dev(device, seed, tag, first_index, n, total, q, d_out, io_bits, (hipStream_t)stream);
+  return fill_call({K_UNIFORM, q, 0, 0.0, nullptr, 0.0}, device, seed, tag, first_index, count, n, d_out, nullptr, io_bits, stream);
 }
 psf_status psf_sample_cbd_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, uint32_t eta, void* d_out, int io_bits,
                               void* stream) {
-  size_t total = 0;
-  psf_status rc = check_fill(tag, io_bits, first_index, count, n, d_out, &total);
-  if (rc == PSF_OK && eta == 0) rc = PSF_ERR_PARAM;
-  if (rc == PSF_OK && eta > 16) rc = PSF_ERR_UNSUPPORTED;
-  return rc != PSF_OK ? rc : cbd_dev(device, seed, tag, first_index, n, total, eta, d_out, io_bits, (hipStream_t)stream);
+  return fill_call({K_CBD, 0, eta, 0.0, nullptr, 0.0}, device, seed, tag, first_index, count, n, d_out, nullptr, io_bits, stream);
 }
 psf_status psf_sample_discrete_gauss_dev(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, double center,
                                          const double* d_centers, double s, void* d_out, int* d_fail, int io_bits, void* stream) {
-  size_t total = 0;
-  psf_status rc = check_fill(tag, io_bits, first_index, count, n, d_out, &total);
-  if (rc == PSF_OK) rc = check_gauss_param(center, d_centers, s);
-  if (rc == PSF_OK) rc = check_gauss_support(center, d_centers, s, io_bits);
-  return rc != PSF_OK ? rc : gauss_dev(device, seed, tag, first_index, n, total, center, d_centers, s, d_out, d_fail, io_bits, (hipStream_t)stream);
+  return fill_call({K_GAUSS, 0, 0, center, d_centers, s}, device, seed, tag, first_index, count, n, d_out, d_fail, io_bits, stream);
 }
-
 psf_status psf_sample_uniform(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, uint64_t q, uint64_t* out) {
-  size_t total = 0;
-  psf_status rc = check_fill(tag, 64, first_index, count, n, out, &total);
-  if (rc == PSF_OK && q < 2) rc = PSF_ERR_PARAM;
-  if (rc == PSF_OK) rc = check_uniform(q, 64);
-  return rc != PSF_OK ? rc : fill_host(K_UNIFORM, device, seed, tag, first_index, n, total, q, 0, 0.0, nullptr, 0.0, out);
+  return fill_call({K_UNIFORM, q, 0, 0.0, nullptr, 0.0}, device, seed, tag, first_index, count, n, out, nullptr, 64, nullptr, true);
 }
 psf_status psf_sample_cbd(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, uint32_t eta, int64_t* out) {
-  size_t total = 0;
-  psf_status rc = check_fill(tag, 64, first_index, count, n, out, &total);
-  if (rc == PSF_OK && eta == 0) rc = PSF_ERR_PARAM;
-  if (rc == PSF_OK && eta > 16) rc = PSF_ERR_UNSUPPORTED;
-  return rc != PSF_OK ? rc : fill_host(K_CBD, device, seed, tag, first_index, n, total, 0, eta, 0.0, nullptr, 0.0, out);
+  return fill_call({K_CBD, 0, eta, 0.0, nullptr, 0.0}, device, seed, tag, first_index, count, n, out, nullptr, 64, nullptr, true);
 }
 psf_status psf_sample_discrete_gauss(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, double center,
                                      const double* centers, double s, int64_t* out) {
-  size_t total = 0;
-  psf_status rc = check_fill(tag, 64, first_index, count, n, out, &total);
-  if (rc == PSF_OK) rc = check_gauss_param(center, centers, s);
-  if (rc == PSF_OK) rc = check_gauss_support(center, centers, s, 64);
-  return rc != PSF_OK ? rc : fill_host(K_GAUSS, device, seed, tag, first_index, n, total, 0, 0, center, centers, s, out);
+  return fill_call({K_GAUSS, 0, 0, center, centers, s}, device, seed, tag, first_index, count, n, out, nullptr, 64, nullptr, true);
 }
 
 }  // extern "C"

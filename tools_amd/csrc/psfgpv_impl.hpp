@@ -3,6 +3,7 @@
 // psfp_handle created with r = 1 (then s*r = s and the domain bound s^2 m r^2 = s^2 m, gpv.rs:113-116, :219-224).
 
 #include <algorithm>
+#include "psf_hip_util.hpp"
 // Everything one batch of the nearest plane writes: a lane.  Lane 0 serves every call; samp_p_dev_many runs the odd batches of a launch-per-block walk on lane 1
 // (allocated by the first such many-call of two or more batches), so that one batch's solve, projection and recombination overlap the other lane's walk.
 struct NpLane {
@@ -79,14 +80,12 @@ static psf_status gpv_finish_basis(psfgpv_handle* g, bool compute_gso) {
   if (compute_gso) {
     hipLaunchKernelGGL(k_i32_to_f64, dim3(grid_for(d * d)), dim3(256), 0, 0, g->dSt, g->dGt, d * d);
     // blocked Gram-Schmidt with re-orthogonalisation on the FP64 matrix cores (psf_gemm_kernels.hpp)
-    int* dinfo = nullptr;
-    HIP_TRY(hipMalloc(&dinfo, sizeof(int)));
-    HIP_TRY(hipMemset(dinfo, 0, sizeof(int)));
-    const hipError_t ge = gso_blocked(nullptr, g->dGt, d, d, dinfo);
+    DevBuf dinfo;
+    HIP_TRY(dinfo.alloc(sizeof(int)));
+    HIP_TRY(dinfo.zero(sizeof(int)));
+    if (gso_blocked(nullptr, g->dGt, d, d, dinfo.as<int>()) != hipSuccess) return PSF_ERR_HIP;
     int info = 0;
-    if (ge == hipSuccess) hipMemcpy(&info, dinfo, sizeof(int), hipMemcpyDeviceToHost);
-    hipFree(dinfo);
-    if (ge != hipSuccess) return PSF_ERR_HIP;
+    dinfo.download(&info, sizeof(int));
     if (info != 0) return PSF_ERR_PARAM;                                 // linearly dependent "basis"
     kc.mark("  gso_blocked");
   }
@@ -111,8 +110,9 @@ static psf_status gpv_finish_basis(psfgpv_handle* g, bool compute_gso) {
   }
   kc.mark("  norms, SampleZ rows");
   {  // g[j][i] = <b_j, b~_i>, then its two packed forms
-    double* dGd = nullptr;
-    HIP_TRY(hipMalloc(&dGd, d * d * sizeof(double)));
+    DevBuf gram;
+    HIP_TRY(gram.alloc(d * d * sizeof(double)));
+    double* dGd = gram.as<double>();
     const unsigned tiles = (unsigned)((d + 63) / 64);
     hipLaunchKernelGGL(k_np_gram, dim3(tiles, tiles), dim3(256), 0, 0, g->dSt, g->dGt, d, dGd);
     if (np_panel_base(g->nblk))
@@ -121,17 +121,15 @@ static psf_status gpv_finish_basis(psfgpv_handle* g, bool compute_gso) {
     hipLaunchKernelGGL(k_np_pack_next, dim3(grid_for(g->nblk * NP_NB * NP_NB)), dim3(256), 0, 0, dGd, d, g->nblk, g->dGnx);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    hipFree(dGd);
   }
   kc.mark("  gram + packing");
   {
-    int* dinfo = nullptr;
-    HIP_TRY(hipMalloc(&dinfo, 2 * sizeof(int)));
-    HIP_TRY(hipMemset(dinfo, 0, 2 * sizeof(int)));
-    hipLaunchKernelGGL(k_np_pack_basis8, dim3(grid_for(g->dpad * g->dpad, 256, 256 * 64)), dim3(256), 0, 0, g->dSt, d, g->dpad, g->dB8, dinfo);
+    DevBuf dinfo;
+    HIP_TRY(dinfo.alloc(2 * sizeof(int)));
+    HIP_TRY(dinfo.zero(2 * sizeof(int)));
+    hipLaunchKernelGGL(k_np_pack_basis8, dim3(grid_for(g->dpad * g->dpad, 256, 256 * 64)), dim3(256), 0, 0, g->dSt, d, g->dpad, g->dB8, dinfo.as<int>());
     int info[2] = {0, 0};
-    HIP_TRY(hipMemcpy(info, dinfo, sizeof(info), hipMemcpyDeviceToHost));
-    hipFree(dinfo);
+    HIP_TRY(dinfo.download(info, sizeof(info)));
     g->basis_generic = info[0] != 0;
     g->basis_hi = info[1] != 0;
     hipLaunchKernelGGL(k_np_occ_basis, dim3((unsigned)(g->nrb * g->nrb), 2), dim3(256), 0, 0, g->dB8, g->dpad, (int)g->nrb, g->dBocc);
@@ -544,9 +542,10 @@ psf_status psfgpv_trap_gen(psfgpv_handle* g, uint64_t seed) {
   if (rc != PSF_OK) return rc;
   kc.mark("A, R");
   // gen_short_basis_for_trapdoor (:90, short_basis_classical.rs:54-110), assembled transposed on the device
-  int8_t* dBT = nullptr;
+  DevBuf bt;
   const size_t ldw = b->ldr;
-  HIP_TRY(hipMalloc(&dBT, b->m * ldw));
+  HIP_TRY(bt.alloc(b->m * ldw));
+  int8_t* dBT = bt.as<int8_t>();
   const int reversed = is_power_of_base(b->prm.gp.base, b->k, b->q) ? 1 : 0;
   hipLaunchKernelGGL(k_gpv_bottom_t, dim3(grid_for(b->m * ldw, 256, 256 * 64)), dim3(256), 0, 0, b->dA, b->m, (uint32_t)b->n, (uint32_t)b->k, b->mb, b->w,
                      b->q, b->prm.gp.base, b->dSk, reversed, dBT, ldw);
@@ -555,7 +554,6 @@ psf_status psfgpv_trap_gen(psfgpv_handle* g, uint64_t seed) {
   hipLaunchKernelGGL(k_gpv_basis_t_tail, dim3(grid_for(b->m * b->w, 256, 256 * 64)), dim3(256), 0, 0, dBT, ldw, b->m, b->mb, b->w, g->dSt);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  hipFree(dBT);
   kc.mark("short basis");
   rc = gpv_finish_basis(g, true);                                             // :91 gso
   if (rc != PSF_OK) return rc;
@@ -792,14 +790,13 @@ psf_status psfgpv_samp_p(psfgpv_handle* g, uint64_t seed, uint64_t first_index, 
     return (fl[1 + 0] || fl[1 + 4]) ? PSF_ERR_SAMPLER : PSF_OK;
   }
   if (psf_exp_env("PSF_HOST_STRAIGHT")) {                      // the form of rounds 1-3 (comparison arm of the tests)
-    uint64_t* du = nullptr; int64_t* de = nullptr;
-    HIP_TRY(hipMalloc(&du, B * g->n * sizeof(uint64_t)));
-    if (hipMalloc(&de, B * g->m * sizeof(int64_t)) != hipSuccess) { hipFree(du); return PSF_ERR_HIP; }
-    psf_status rcs = hipMemcpy(du, u, B * g->n * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess ? PSF_OK : PSF_ERR_HIP;
-    if (rcs == PSF_OK) rcs = psfgpv_samp_p_dev(g, seed, first_index, B, du, de, nullptr);
+    DevBuf du, de;
+    HIP_TRY(du.alloc(B * g->n * sizeof(uint64_t)));
+    HIP_TRY(de.alloc(B * g->m * sizeof(int64_t)));
+    psf_status rcs = du.upload(u, B * g->n * sizeof(uint64_t)) == hipSuccess ? PSF_OK : PSF_ERR_HIP;
+    if (rcs == PSF_OK) rcs = psfgpv_samp_p_dev(g, seed, first_index, B, du.as<uint64_t>(), de.as<int64_t>(), nullptr);
     if (rcs == PSF_OK) rcs = psfgpv_last_status(g);
-    if (hipMemcpy(e, de, B * g->m * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess && rcs == PSF_OK) rcs = PSF_ERR_HIP;
-    hipFree(du); hipFree(de);
+    if (de.download(e, B * g->m * sizeof(int64_t)) != hipSuccess && rcs == PSF_OK) rcs = PSF_ERR_HIP;
     return rcs;
   }
   // A batch: cached device buffers (no hipMalloc / hipFree per call), u through the pinned buffer, the rows narrowed to int32 on the device (every entry of a preimage
@@ -1028,13 +1025,11 @@ static psf_status ring_install(psfring_handle* h) {
   h->fa_ntt = false;
   if (ntt_route(h->gp.q, n) == 2 && ((size_t)K * n + 4 * n) * sizeof(uint32_t) <= 64 * 1024) {
     // (the key is installed and usable at this point: a failure below only means that f_a keeps the matrix-product route, it is not an error of the call)
-    uint64_t* da = nullptr;
+    DevBuf da;
     psf_status rf = (h->dHat || hipMalloc(&h->dHat, K * n * sizeof(uint32_t)) == hipSuccess) ? PSF_OK : PSF_ERR_HIP;
-    if (rf == PSF_OK && hipMalloc(&da, K * n * sizeof(uint64_t)) != hipSuccess) rf = PSF_ERR_HIP;
-    if (rf == PSF_OK && hipMemcpy(da, h->a.data(), K * n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) rf = PSF_ERR_HIP;
-    if (rf == PSF_OK) rf = ntt_forward_dev(b->prm.device, h->gp.q, n, K, da, 64, h->dHat, nullptr);
+    if (rf == PSF_OK && (da.alloc(K * n * sizeof(uint64_t)) != hipSuccess || da.upload(h->a.data(), K * n * sizeof(uint64_t)) != hipSuccess)) rf = PSF_ERR_HIP;
+    if (rf == PSF_OK) rf = ntt_forward_dev(b->prm.device, h->gp.q, n, K, da.as<uint64_t>(), 64, h->dHat, nullptr);
     if (rf == PSF_OK && hipDeviceSynchronize() != hipSuccess) rf = PSF_ERR_HIP;
-    hipFree(da);
     if (rf != PSF_OK) (void)hipGetLastError();
     h->fa_ntt = rf == PSF_OK;
   }
@@ -1108,19 +1103,19 @@ static psf_status poly_mul_host(int device, uint64_t q, size_t n, size_t count, 
   if (q <= 1 || q >= (1ull << 62) || n < 1 || n > 8192 || (count && (!a || !b || !out))) return PSF_ERR_PARAM;
   if (method == 1 && ntt_route(q, n, ring) == 0) return PSF_ERR_UNSUPPORTED;
   if (count == 0) return PSF_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
-  HIP_TRY(hipSetDevice(device));
-  uint64_t *da = nullptr, *dout = nullptr; int64_t* db = nullptr;
-  auto done = [&](psf_status st) { hipFree(da); hipFree(db); hipFree(dout); return st; };
-  if (hipMalloc(&da, count * n * sizeof(uint64_t)) != hipSuccess || hipMalloc(&db, count * n * sizeof(int64_t)) != hipSuccess ||
-      hipMalloc(&dout, count * n * sizeof(uint64_t)) != hipSuccess) return done(PSF_ERR_HIP);
-  if (hipMemcpy(da, a, count * n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(db, b, count * n * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) return done(PSF_ERR_HIP);
-  const psf_status rc = polymul_dev_any(device, q, n, count, da, db, dout, 64, method, nullptr, ring);
-  if (rc != PSF_OK) return done(rc);
-  if (hipMemcpy(out, dout, count * n * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
-  return done(PSF_OK);
+  const psf_status ud = use_device(device);
+  if (ud != PSF_OK) return ud;
+  const size_t bytes = count * n * sizeof(uint64_t);                 // of a, of b and of the product alike
+  DevBuf da, db, dout;
+  HIP_TRY(da.alloc(bytes));
+  HIP_TRY(db.alloc(bytes));
+  HIP_TRY(dout.alloc(bytes));
+  HIP_TRY(da.upload(a, bytes));
+  HIP_TRY(db.upload(b, bytes));
+  const psf_status rc = polymul_dev_any(device, q, n, count, da.as<void>(), db.as<void>(), dout.as<void>(), 64, method, nullptr, ring);
+  if (rc != PSF_OK) return rc;
+  HIP_TRY(dout.download(out, bytes));
+  return PSF_OK;
 }
 psf_status psf_poly_mul_negacyclic_method(int device, uint64_t q, size_t n, size_t count, const uint64_t* a, const int64_t* b, uint64_t* out, int method) {
   return poly_mul_host(device, q, n, count, a, b, out, method, kNegacyclic);
@@ -1199,11 +1194,11 @@ static psf_status matpoly_dev_any(int device, uint64_t q, size_t n, size_t count
                                   bool hat, int trans_a, const void* d_b, void* d_c, int io_bits, hipStream_t st, NttRing ring = kNegacyclic) {
   const psf_status chk = matpoly_check(q, n, count, rows, inner, cols, d_a, a_stride, hat, trans_a, d_b, d_c, io_bits, ring);
   if (chk != PSF_OK || count == 0) return chk;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
+  const psf_status ud = use_device(device);
+  if (ud != PSF_OK) return ud;
   if (ntt_route(q, n, ring) == 2)
     return ntt_matmul_dev(device, q, n, NttMatShape{count, rows, inner, cols, trans_a}, d_a, a_stride, hat, d_b, d_c, io_bits, st, ring);
-  HIP_TRY(hipSetDevice(device));                            // every other q < 2^62 at 64-bit words: the exact schoolbook kernel
+  // every other q < 2^62 at 64-bit words: the exact schoolbook kernel
   const uint64_t two64 = (uint64_t)((((u128)1) << 64) % q);
   const size_t outs = count * rows * cols;
   if (ring == kCyclic) {
@@ -1243,20 +1238,19 @@ static psf_status matpoly_host(int device, uint64_t q, size_t n, size_t rows, si
   // the same checks on the host buffers (one batch), then device copies
   const psf_status chk = matpoly_check(q, n, 1, rows, inner, cols, a, 0, false, 0, b, c, 64, ring);
   if (chk != PSF_OK) return chk;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
-  HIP_TRY(hipSetDevice(device));
-  const size_t na = rows * inner * n, nb = inner * cols * n, nc = rows * cols * n;
-  uint64_t *da = nullptr, *dc = nullptr; int64_t* db = nullptr;
-  auto done = [&](psf_status st) { hipFree(da); hipFree(db); hipFree(dc); return st; };
-  if (hipMalloc(&da, na * sizeof(uint64_t)) != hipSuccess || hipMalloc(&db, nb * sizeof(int64_t)) != hipSuccess ||
-      hipMalloc(&dc, nc * sizeof(uint64_t)) != hipSuccess) return done(PSF_ERR_HIP);
-  if (hipMemcpy(da, a, na * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(db, b, nb * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) return done(PSF_ERR_HIP);
-  const psf_status rc = matpoly_dev_any(device, q, n, 1, rows, inner, cols, da, 0, false, 0, db, dc, 64, nullptr, ring);
-  if (rc != PSF_OK) return done(rc);
-  if (hipMemcpy(c, dc, nc * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
-  return done(PSF_OK);
+  const psf_status ud = use_device(device);
+  if (ud != PSF_OK) return ud;
+  const size_t na = rows * inner * n * sizeof(uint64_t), nb = inner * cols * n * sizeof(int64_t), nc = rows * cols * n * sizeof(uint64_t);
+  DevBuf da, db, dc;
+  HIP_TRY(da.alloc(na));
+  HIP_TRY(db.alloc(nb));
+  HIP_TRY(dc.alloc(nc));
+  HIP_TRY(da.upload(a, na));
+  HIP_TRY(db.upload(b, nb));
+  const psf_status rc = matpoly_dev_any(device, q, n, 1, rows, inner, cols, da.as<void>(), 0, false, 0, db.as<void>(), dc.as<void>(), 64, nullptr, ring);
+  if (rc != PSF_OK) return rc;
+  HIP_TRY(dc.download(c, nc));
+  return PSF_OK;
 }
 psf_status psf_matpoly_mul_negacyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, uint64_t* c) {
   return matpoly_host(device, q, n, rows, inner, cols, a, b, c, kNegacyclic);
@@ -1278,21 +1272,21 @@ psf_status psf_matpoly_mul_cyclic(int device, uint64_t q, size_t n, size_t rows,
 // MatQ::gso (gpv.rs:88-91) as a free function: rows of an integer matrix -> their Gram-Schmidt vectors
 psf_status psf_gso_rows(int device, const int32_t* basis_t, size_t rows, size_t width, double* out) {
   if (!basis_t || !out || rows < 1 || width < 1) return PSF_ERR_PARAM;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
-  HIP_TRY(hipSetDevice(device));
-  int32_t* dS = nullptr; double* dG = nullptr; int* dinfo = nullptr;
-  auto done = [&](psf_status st) { hipFree(dS); hipFree(dG); hipFree(dinfo); return st; };
-  if (hipMalloc(&dS, rows * width * sizeof(int32_t)) != hipSuccess || hipMalloc(&dG, rows * width * sizeof(double)) != hipSuccess ||
-      hipMalloc(&dinfo, sizeof(int)) != hipSuccess) return done(PSF_ERR_HIP);
-  if (hipMemcpy(dS, basis_t, rows * width * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess || hipMemset(dinfo, 0, sizeof(int)) != hipSuccess) return done(PSF_ERR_HIP);
-  hipLaunchKernelGGL(k_i32_to_f64, dim3(grid_for(rows * width)), dim3(256), 0, 0, dS, dG, rows * width);
-  if (gso_blocked(nullptr, dG, rows, width, dinfo) != hipSuccess) return done(PSF_ERR_HIP);
+  const psf_status ud = use_device(device);
+  if (ud != PSF_OK) return ud;
+  DevBuf dS, dG, dinfo;
+  HIP_TRY(dS.alloc(rows * width * sizeof(int32_t)));
+  HIP_TRY(dG.alloc(rows * width * sizeof(double)));
+  HIP_TRY(dinfo.alloc(sizeof(int)));
+  HIP_TRY(dS.upload(basis_t, rows * width * sizeof(int32_t)));
+  HIP_TRY(dinfo.zero(sizeof(int)));
+  hipLaunchKernelGGL(k_i32_to_f64, dim3(grid_for(rows * width)), dim3(256), 0, 0, dS.as<int32_t>(), dG.as<double>(), rows * width);
+  HIP_TRY(gso_blocked(nullptr, dG.as<double>(), rows, width, dinfo.as<int>()));
   int info = 0;
-  if (hipMemcpy(&info, dinfo, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
-  if (info != 0) return done(PSF_ERR_PARAM);
-  if (hipMemcpy(out, dG, rows * width * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(PSF_ERR_HIP);
-  return done(PSF_OK);
+  HIP_TRY(dinfo.download(&info, sizeof(int)));
+  if (info != 0) return PSF_ERR_PARAM;
+  HIP_TRY(dG.download(out, rows * width * sizeof(double)));
+  return PSF_OK;
 }
 
 // gen_trapdoor_ring_lwe (gadget_ring.rs:62-81): A = [1 | a_bar | g_j - (a_bar r_j + e_j)] mod (X^n + 1, q); the k products a_bar * r_j run on the
@@ -1304,19 +1298,19 @@ static psf_status ring_lwe_assemble(int device, const psf_gadget_params* gp, con
   std::vector<uint64_t> prod(k * n);
   psf_status rc;
   if (ntt_route(q, n) == 2) {                                            // a_bar is transformed ONCE, then k products image x r_j
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSF_ERR_HIP;
-    HIP_TRY(hipSetDevice(device));
-    uint64_t *da = nullptr, *dout = nullptr; int64_t* dr = nullptr; uint32_t* dhat = nullptr;
-    auto done = [&](psf_status st) { hipFree(da); hipFree(dr); hipFree(dout); hipFree(dhat); return st; };
-    if (hipMalloc(&da, n * sizeof(uint64_t)) != hipSuccess || hipMalloc(&dr, k * n * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc(&dout, k * n * sizeof(uint64_t)) != hipSuccess || hipMalloc(&dhat, n * sizeof(uint32_t)) != hipSuccess) return done(PSF_ERR_HIP);
-    if (hipMemcpy(da, a_bar, n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dr, r, k * n * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) return done(PSF_ERR_HIP);
-    rc = ntt_forward_dev(device, q, n, 1, da, 64, dhat, nullptr);
-    if (rc == PSF_OK) rc = ntt_mul_hat_dev(device, q, n, k, dhat, 0, dr, dout, 64, nullptr);                 // a_bar * r (:78)
-    if (rc == PSF_OK && hipMemcpy(prod.data(), dout, k * n * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) rc = PSF_ERR_HIP;
-    if (done(rc) != PSF_OK) return rc;
+    rc = use_device(device);
+    if (rc != PSF_OK) return rc;
+    DevBuf da, dr, dout, dhat;
+    HIP_TRY(da.alloc(n * sizeof(uint64_t)));
+    HIP_TRY(dr.alloc(k * n * sizeof(int64_t)));
+    HIP_TRY(dout.alloc(k * n * sizeof(uint64_t)));
+    HIP_TRY(dhat.alloc(n * sizeof(uint32_t)));
+    HIP_TRY(da.upload(a_bar, n * sizeof(uint64_t)));
+    HIP_TRY(dr.upload(r, k * n * sizeof(int64_t)));
+    rc = ntt_forward_dev(device, q, n, 1, da.as<void>(), 64, dhat.as<uint32_t>(), nullptr);
+    if (rc == PSF_OK) rc = ntt_mul_hat_dev(device, q, n, k, dhat.as<uint32_t>(), 0, dr.as<void>(), dout.as<void>(), 64, nullptr);   // a_bar * r (:78)
+    if (rc != PSF_OK) return rc;
+    HIP_TRY(dout.download(prod.data(), k * n * sizeof(uint64_t)));
   } else {
     std::vector<uint64_t> abar_rep(k * n);
     for (size_t j = 0; j < k; ++j)

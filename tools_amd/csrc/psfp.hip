@@ -11,7 +11,7 @@
 #include <mutex>
 #include <functional>
 #include <vector>
-#include "../../include/psf_mi355x.h"
+#include "psf_hip_util.hpp"
 #include "psf_host.hpp"
 #include "psf_kernels.hpp"
 #include "psf_stream_kernels.hpp"
@@ -39,15 +39,6 @@ struct KeygenClock {
 // PSFP_FLAG_STRUCTURED_SQRT (2u) is public: include/psf_mi355x.h
 
 using namespace psf;
-
-#define HIP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e__ = (expr);                                                           \
-    if (e__ != hipSuccess) {                                                           \
-      std::fprintf(stderr, "[psf_mi355x] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return PSF_ERR_HIP;                                                              \
-    }                                                                                  \
-  } while (0)
 
 static inline unsigned grid_for(size_t total, unsigned block = 256, unsigned cap = 256 * 16) {
   size_t g = (total + block - 1) / block;
@@ -327,8 +318,8 @@ const char* psf_status_string(psf_status s) {
 }
 
 psf_status psf_device_info(int device, char* name, size_t name_len, int* compute_units) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return PSF_ERR_HIP;
+  const psf_status ud = use_device(device);
+  if (ud != PSF_OK) return ud;
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   if (name && name_len) { std::strncpy(name, prop.gcnArchName, name_len - 1); name[name_len - 1] = 0; }
@@ -377,14 +368,13 @@ psf_status psf_find_solution_gadget_mat(int device, const uint64_t* value, size_
   if (gadget_too_short(base, k, q)) return PSF_ERR_MODULUS;   // gadget_classical.rs:170-172
   if (rows * cols == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(device));
-  uint64_t* dv = nullptr; int64_t* dout = nullptr;
-  HIP_TRY(hipMalloc(&dv, rows * cols * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc(&dout, k * rows * cols * sizeof(int64_t)));
-  HIP_TRY(hipMemcpy(dv, value, rows * cols * sizeof(uint64_t), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_digits, dim3(grid_for(rows * cols)), dim3(256), 0, 0, dv, rows, cols, q, (uint32_t)k, base, dout);
+  DevBuf dv, dout;
+  HIP_TRY(dv.alloc(rows * cols * sizeof(uint64_t)));
+  HIP_TRY(dout.alloc(k * rows * cols * sizeof(int64_t)));
+  HIP_TRY(dv.upload(value, rows * cols * sizeof(uint64_t)));
+  hipLaunchKernelGGL(k_digits, dim3(grid_for(rows * cols)), dim3(256), 0, 0, dv.as<uint64_t>(), rows, cols, q, (uint32_t)k, base, dout.as<int64_t>());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, dout, k * rows * cols * sizeof(int64_t), hipMemcpyDeviceToHost));
-  hipFree(dv); hipFree(dout);
+  HIP_TRY(dout.download(out, k * rows * cols * sizeof(int64_t)));
   return PSF_OK;
 }
 
@@ -762,10 +752,10 @@ static psf_status build_sqrt_sigma2(psfp_handle* h, double s_cov, const double* 
   const char* ce = psf_exp_env("PSF_CHOL");
   const bool stream = ce ? !std::strcmp(ce, "stream") : m * m * sizeof(double) > (16ull << 30);
   if (stream) return build_sqrt_sigma2_stream(h, nf_r2, s2, b2p1, d_sigma_packed);
-  struct DenseGuard { double* dS = nullptr; ~DenseGuard() { hipFree(dS); } } dg;      // every exit releases it
-  double*& dS = dg.dS;
-  HIP_TRY(hipMalloc(&dS, m * m * sizeof(double)));
-  HIP_TRY(hipMemset(dS, 0, m * m * sizeof(double)));
+  DevBuf dense;
+  HIP_TRY(dense.alloc(m * m * sizeof(double)));
+  HIP_TRY(dense.zero(m * m * sizeof(double)));
+  double* dS = dense.as<double>();
   const unsigned tiles = (unsigned)((m + 63) / 64);
   // the R R^t block on the int8 matrix cores, everything else (the rows from m_bar on) in k_sigma2
   hipLaunchKernelGGL(k_sigma2_rrt, dim3(tiles, tiles), dim3(256), 3 * 2 * 4096, 0, h->dR, h->ldr, h->mb, m, nf_r2, s2, b2p1, d_sigma_packed, dS, m, (size_t)0, (size_t)0);
@@ -821,12 +811,11 @@ static psf_status gen_trapdoor_core(int device, const psf_gadget_params* gp, con
   psf_status rc = psfp_create(&prm, &h);
   if (rc != PSF_OK) return rc;
   if (gadget_too_short(gp->base, h->k, h->q)) { psfp_destroy(h); return PSF_ERR_MODULUS; }
-  uint64_t* dtag = nullptr;
-  auto fail = [&](psf_status st) { hipFree(dtag); psfp_destroy(h); return st; };
+  DevBuf dtag;
+  auto fail = [&](psf_status st) { psfp_destroy(h); return st; };
   if (hipMemcpy2D(h->dA, h->m * sizeof(uint64_t), a_bar, h->mb * sizeof(uint64_t), h->mb * sizeof(uint64_t), h->n, hipMemcpyHostToDevice) != hipSuccess) return fail(PSF_ERR_HIP);
   if (tag) {
-    if (hipMalloc(&dtag, h->n * h->n * sizeof(uint64_t)) != hipSuccess) return fail(PSF_ERR_HIP);
-    if (hipMemcpy(dtag, tag, h->n * h->n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) return fail(PSF_ERR_HIP);
+    if (dtag.alloc(h->n * h->n * sizeof(uint64_t)) != hipSuccess || dtag.upload(tag, h->n * h->n * sizeof(uint64_t)) != hipSuccess) return fail(PSF_ERR_HIP);
   }
   if (R_in) {
     // the trapdoor lives in int8 on the device (operand of the int8 matrix cores in e = p + [R; I] z and of the dot4 assembly of Sigma_2)
@@ -842,7 +831,7 @@ static psf_status gen_trapdoor_core(int device, const psf_gadget_params* gp, con
     h->r8_valid = false; h->small_state = 0;
     hipLaunchKernelGGL(k_sample_R, dim3(grid_for(h->mb * h->ldr)), dim3(256), 0, 0, seed, h->mb, h->w, h->ldr, h->dR);    // gadget_classical.rs:62-64
   }
-  launch_zq_trapdoor(h, dtag);                                                                                            // :66
+  launch_zq_trapdoor(h, dtag.as<uint64_t>());                                                                                            // :66
   if (hipGetLastError() != hipSuccess) return fail(PSF_ERR_HIP);
   if (hipMemcpy(A, h->dA, h->n * h->m * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return fail(PSF_ERR_HIP);
   if (R_out && hipMemcpy2D(R_out, h->w, h->dR, h->ldr, h->w, h->mb, hipMemcpyDeviceToHost) != hipSuccess) return fail(PSF_ERR_HIP);
@@ -907,12 +896,11 @@ psf_status psfp_compute_sqrt_sigma_2_dense(psfp_handle* h, const double* sigma_l
   if (h->structured) return PSF_ERR_UNSUPPORTED;           // the structured factor exists for Sigma = s^2 I only
   HIP_TRY(hipSetDevice(h->prm.device));
   PSFP_QUIESCE(h);
-  double* dsg = nullptr;
+  DevBuf dsg;
   const size_t np = h->m * (h->m + 1) / 2;
-  HIP_TRY(hipMalloc(&dsg, np * sizeof(double)));
-  if (hipMemcpy(dsg, sigma_lower_packed, np * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { hipFree(dsg); return PSF_ERR_HIP; }
-  const psf_status rc = build_sqrt_sigma2(h, 0.0, dsg);
-  hipFree(dsg);
+  HIP_TRY(dsg.alloc(np * sizeof(double)));
+  HIP_TRY(dsg.upload(sigma_lower_packed, np * sizeof(double)));
+  const psf_status rc = build_sqrt_sigma2(h, 0.0, dsg.as<double>());
   h->has_key = rc == PSF_OK;
   return rc;
 }
@@ -938,22 +926,21 @@ psf_status psfp_load_key(psfp_handle* h, const uint64_t* A, const int8_t* R, con
     h->has_key = rc == PSF_OK;
     return rc;
   }
-  double* dp = nullptr;
+  DevBuf dp;
   const size_t np = h->mL * (h->mL + 1) / 2;
-  HIP_TRY(hipMalloc(&dp, np * sizeof(double)));
-  HIP_TRY(hipMemcpy(dp, Lp, np * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_repack_L<true>, dim3(grid_for(tr_total_chunks(h->nbiL) * TR_CHUNK)), dim3(256), 0, 0, dp, (size_t)0, h->mL, h->dLt, h->nbiL);
+  HIP_TRY(dp.alloc(np * sizeof(double)));
+  HIP_TRY(dp.upload(Lp, np * sizeof(double)));
+  hipLaunchKernelGGL(k_repack_L<true>, dim3(grid_for(tr_total_chunks(h->nbiL) * TR_CHUNK)), dim3(256), 0, 0, dp.as<double>(), (size_t)0, h->mL, h->dLt, h->nbiL);
   if (h->structured) {      // the constants of the structured factor follow from (r, s): the same expressions as build_sqrt_sigma2
     const double nf_r2 = (1.0 / 6.283185307179586476925) * (h->prm.r * h->prm.r), kappa = (double)(h->prm.gp.base * h->prm.gp.base + 1);
     const double alpha = h->prm.s * h->prm.s - 1.0, beta = alpha - kappa;
-    if (!(beta > 0.0)) { hipFree(dp); return PSF_ERR_NOT_PD; }
+    if (!(beta > 0.0)) return PSF_ERR_NOT_PD;
     h->g_const = (std::sqrt(nf_r2) * kappa) / std::sqrt(beta);
     h->h_const = std::sqrt(nf_r2 * beta);
     ensure_R8(h, nullptr);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  hipFree(dp);
   h->has_key = true;
   hp_prewarm(h);
   return PSF_OK;
@@ -989,13 +976,12 @@ psf_status psfp_export_key(const psfp_handle* h, uint64_t* A, int8_t* R, double*
   if (A) HIP_TRY(hipMemcpy(A, h->dA, h->n * h->m * sizeof(uint64_t), hipMemcpyDeviceToHost));
   if (R) HIP_TRY(hipMemcpy2D(R, h->w, h->dR, h->ldr, h->w, h->mb, hipMemcpyDeviceToHost));
   if (Lp) {
-    double* dp = nullptr;
+    DevBuf dp;
     const size_t np = h->mL * (h->mL + 1) / 2;
-    HIP_TRY(hipMalloc(&dp, np * sizeof(double)));
-    hipLaunchKernelGGL(k_unpack_L, dim3(grid_for(np)), dim3(256), 0, 0, h->dLt, (size_t)0, np, dp);
+    HIP_TRY(dp.alloc(np * sizeof(double)));
+    hipLaunchKernelGGL(k_unpack_L, dim3(grid_for(np)), dim3(256), 0, 0, h->dLt, (size_t)0, np, dp.as<double>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(Lp, dp, np * sizeof(double), hipMemcpyDeviceToHost));
-    hipFree(dp);
+    HIP_TRY(dp.download(Lp, np * sizeof(double)));
   }
   return PSF_OK;
 }
@@ -1007,12 +993,11 @@ psf_status psfp_export_sqrt_sigma2_rows(const psfp_handle* h, size_t row0, size_
   if (nrows == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(h->prm.device));
   const size_t first = row0 * (row0 + 1) / 2, total = (row0 + nrows) * (row0 + nrows + 1) / 2 - first;
-  double* dp = nullptr;
-  HIP_TRY(hipMalloc(&dp, total * sizeof(double)));
-  hipLaunchKernelGGL(k_unpack_L, dim3(grid_for(total)), dim3(256), 0, 0, h->dLt, first, total, dp);
+  DevBuf dp;
+  HIP_TRY(dp.alloc(total * sizeof(double)));
+  hipLaunchKernelGGL(k_unpack_L, dim3(grid_for(total)), dim3(256), 0, 0, h->dLt, first, total, dp.as<double>());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, dp, total * sizeof(double), hipMemcpyDeviceToHost));
-  hipFree(dp);
+  HIP_TRY(dp.download(out, total * sizeof(double)));
   return PSF_OK;
 }
 
@@ -1970,8 +1955,9 @@ psf_status psfp_samp_p_stages(psfp_handle* h, uint64_t seed, uint64_t first_inde
   if (rc != PSF_OK && rc != PSF_ERR_SAMPLER) return rc;
   const size_t m = h->m, ld = h->ld;
   if (e) std::memcpy(e, etmp.data(), etmp.size() * sizeof(int64_t));
-  void* tmp = nullptr;
-  HIP_TRY(hipMalloc(&tmp, B * m * sizeof(double)));
+  DevBuf tbuf;
+  HIP_TRY(tbuf.alloc(B * m * sizeof(double)));
+  void* tmp = tbuf.as<void>();
   if (d) {
     hipLaunchKernelGGL(k_export_normals, dim3(grid_for(B * m)), dim3(256), 0, 0, h->dDt, m, B, h->nkb, (double*)tmp, h->normals_ncf);
     HIP_TRY(hipMemcpy(d, tmp, B * m * sizeof(double), hipMemcpyDeviceToHost));
@@ -1994,7 +1980,6 @@ psf_status psfp_samp_p_stages(psfp_handle* h, uint64_t seed, uint64_t first_inde
   if (z)  // e_bottom = p_bottom + z  (mp_perturbation.rs:335 with the identity block of [R; I])
     for (size_t b = 0; b < B; ++b)
       for (size_t c = 0; c < h->w; ++c) z[b * h->w + c] = etmp[b * m + h->mb + c] - ptmp[b * m + h->mb + c];
-  hipFree(tmp);
   return rc;
 }
 
@@ -2015,12 +2000,11 @@ psf_status psfp_samp_d(psfp_handle* h, uint64_t seed, uint64_t first_index, size
   if (!h || (B && !e)) return PSF_ERR_PARAM;
   if (B == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(h->prm.device));
-  int64_t* de = nullptr;
-  HIP_TRY(hipMalloc(&de, B * h->m * sizeof(int64_t)));
-  psf_status rc = psfp_samp_d_dev(h, seed, first_index, B, de, nullptr);
+  DevBuf de;
+  HIP_TRY(de.alloc(B * h->m * sizeof(int64_t)));
+  psf_status rc = psfp_samp_d_dev(h, seed, first_index, B, de.as<int64_t>(), nullptr);
   if (rc == PSF_OK) rc = psfp_last_status(h);
-  HIP_TRY(hipMemcpy(e, de, B * h->m * sizeof(int64_t), hipMemcpyDeviceToHost));
-  hipFree(de);
+  HIP_TRY(de.download(e, B * h->m * sizeof(int64_t)));
   return rc;
 }
 
@@ -2033,14 +2017,13 @@ psf_status psfp_check_domain(psfp_handle* h, size_t B, const int64_t* e, size_t 
   if (B == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(h->prm.device));
   if (len == 0) { std::memset(ok, 0, B); return PSF_OK; }
-  int64_t* de = nullptr; uint8_t* dok = nullptr;
-  HIP_TRY(hipMalloc(&de, B * len * sizeof(int64_t)));
-  HIP_TRY(hipMalloc(&dok, B));
-  HIP_TRY(hipMemcpy(de, e, B * len * sizeof(int64_t), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_check_domain, dim3((unsigned)B), dim3(256), 0, 0, de, len, h->m, domain_bound(h), dok);
+  DevBuf de, dok;
+  HIP_TRY(de.alloc(B * len * sizeof(int64_t)));
+  HIP_TRY(dok.alloc(B));
+  HIP_TRY(de.upload(e, B * len * sizeof(int64_t)));
+  hipLaunchKernelGGL(k_check_domain, dim3((unsigned)B), dim3(256), 0, 0, de.as<int64_t>(), len, h->m, domain_bound(h), dok.as<uint8_t>());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(ok, dok, B, hipMemcpyDeviceToHost));
-  hipFree(de); hipFree(dok);
+  HIP_TRY(dok.download(ok, B));
   return PSF_OK;
 }
 

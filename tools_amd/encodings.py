@@ -7,8 +7,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import ERR_PARAM, ERR_UNSUPPORTED, PsfError, check, lib
-from .compression import _p, _residues
+from ._ffi import ERR_PARAM, ERR_UNSUPPORTED, PsfError, _p, check, lib
+from .compression import _residues
 
 
 def _check_base(base, where):

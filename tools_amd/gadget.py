@@ -5,11 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import GadgetParams, check, lib
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+from ._ffi import GadgetParams, _p, check, lib
 
 
 def gen_gadget_vec(k, base):

@@ -8,11 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import GadgetParams, GpvParams, PsfpParams, RingParams, PsfError, check, lib
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+from ._ffi import GadgetParams, GpvParams, PsfpParams, RingParams, PsfError, _p, check, lib
 
 
 def _many(fn, h, d_u_ptr, d_e_ptr, B, seeds, first_indices, stream):

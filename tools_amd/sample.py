@@ -8,13 +8,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import check, lib
+from ._ffi import _p, check, lib
 
 TAG_MIN, TAG_MAX = 64, 255
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
 
 
 def _head(device, seed, tag, first_index, count, n):
