@@ -185,6 +185,27 @@ psf_status psf_matpoly_mul_cyclic_dev(int device, uint64_t q, size_t n, size_t c
 psf_status psf_matpoly_mul_hat_cyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint32_t* d_hat,
                                           size_t hat_stride, int trans_a, const void* d_b, void* d_c, int io_bits, void* stream);
 psf_status psf_matpoly_mul_cyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, uint64_t* c);
+/* Fused multiply-add over R_q: C[c] = E[c] + sign * op(A[c]) B[c] for c < count -- t = A s + e, u = A^T r + e1, v = t^T r + e2, w = v - s^T u in one
+ * launch each, and the checks a S (gadget_ring.rs:190-202) and A e - u with their subtraction.  One twin per matrix-product entry point above, with two
+ * more arguments in front of the output: E[c] is rows x cols polynomials laid out like C[c], in B's word type and value contract (int64 of any value at
+ * 64-bit words, int16 in (-q, q) at 16-bit words: signed noise and residues in [0, q) both fit); sign is +1 or -1, anything else PSF_ERR_PARAM.  C is
+ * canonical, in [0, q).  The word of E is added in the kernel that finishes the output polynomial, by the thread that writes that word of C, so
+ * d_e == d_c (exact in-place accumulation) is allowed; any other overlap of C with E is PSF_ERR_PARAM, like C overlapping A or B.  A NULL d_e with
+ * count > 0 is PSF_ERR_PARAM.  Every other rule of psf_matpoly_mul_negacyclic_dev carries over: limits, codes, PSF_ERR_PARAM before
+ * PSF_ERR_UNSUPPORTED, every check before the first HIP call, nothing written on error, no allocation, no synchronisation, count = 0 is PSF_OK.
+ * The host-buffer forms take one batch and allow c == e. */
+psf_status psf_matpoly_mul_add_negacyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
+                                              int trans_a, const void* d_b, const void* d_e, int sign, void* d_c, int io_bits, void* stream);
+psf_status psf_matpoly_mul_add_hat_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint32_t* d_hat, size_t hat_stride,
+                                       int trans_a, const void* d_b, const void* d_e, int sign, void* d_c, int io_bits, void* stream);
+psf_status psf_matpoly_mul_add_negacyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, const int64_t* e,
+                                          int sign, uint64_t* c);
+psf_status psf_matpoly_mul_add_cyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
+                                          int trans_a, const void* d_b, const void* d_e, int sign, void* d_c, int io_bits, void* stream);
+psf_status psf_matpoly_mul_add_hat_cyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint32_t* d_hat,
+                                              size_t hat_stride, int trans_a, const void* d_b, const void* d_e, int sign, void* d_c, int io_bits, void* stream);
+psf_status psf_matpoly_mul_add_cyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, const int64_t* e,
+                                      int sign, uint64_t* c);
 /* R_q coefficient maps of the ML-KEM-style schemes, on a flat array of `len` coefficients (any number of polynomials, or of the entries of a
  * MatPolynomialRingZq, n coefficients each, constant term first).  Exact integer arithmetic, bit for bit against the big-integer definitions:
  *   compress   (LossyCompressionFIPS203::lossy_compress, lossy_compression_fips203.rs:89-112):   y = floor((x 2^d + floor(q/2)) / q) mod 2^d,

@@ -43,6 +43,29 @@ inline psf_gadget_params gadget_parameters_ring_default(uint64_t n, uint64_t q) 
 using MatZq = std::vector<uint64_t>;   // least non-negative residues, row-major
 using MatZ = std::vector<int64_t>;
 
+// ---- fused R_q matrix products C[c] = E[c] + sign * op(A[c]) B[c] on device buffers (psf_matpoly_mul_add_*_dev; layouts and rules in psf_mi355x.h) ----
+// d_e == d_c accumulates in place.  `cyclic`: Z_q[X]/(X^n - 1) instead of Z_q[X]/(X^n + 1).
+struct MatPolyShape { size_t count, rows, inner, cols; int trans_a = 0; };
+inline void matpoly_mul_add_dev(int device, uint64_t q, size_t n, const MatPolyShape& s, const void* d_a, size_t a_stride, const void* d_b, const void* d_e, int sign,
+                                void* d_c, int io_bits = 64, void* stream = nullptr, bool cyclic = false) {
+  check((cyclic ? psf_matpoly_mul_add_cyclic_dev : psf_matpoly_mul_add_negacyclic_dev)(device, q, n, s.count, s.rows, s.inner, s.cols, d_a, a_stride, s.trans_a, d_b,
+                                                                                      d_e, sign, d_c, io_bits, stream), "matpoly_mul_add_dev");
+}
+inline void matpoly_mul_add_hat_dev(int device, uint64_t q, size_t n, const MatPolyShape& s, const uint32_t* d_hat, size_t hat_stride, const void* d_b, const void* d_e,
+                                    int sign, void* d_c, int io_bits = 64, void* stream = nullptr, bool cyclic = false) {
+  check((cyclic ? psf_matpoly_mul_add_hat_cyclic_dev : psf_matpoly_mul_add_hat_dev)(device, q, n, s.count, s.rows, s.inner, s.cols, d_hat, hat_stride, s.trans_a, d_b,
+                                                                                   d_e, sign, d_c, io_bits, stream), "matpoly_mul_add_hat_dev");
+}
+// host buffers, one batch: a rows x inner, b inner x cols, e rows x cols polynomials of n coefficients; returns e + sign * a b in [0, q)
+inline MatZq matpoly_mul_add(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const MatZq& a, const MatZ& b, const MatZ& e, int sign = 1,
+                             bool cyclic = false) {
+  if (a.size() != rows * inner * n || b.size() != inner * cols * n || e.size() != rows * cols * n) throw PsfError(PSF_ERR_PARAM, "matpoly_mul_add");
+  MatZq c(rows * cols * n);
+  check((cyclic ? psf_matpoly_mul_add_cyclic : psf_matpoly_mul_add_negacyclic)(device, q, n, rows, inner, cols, a.data(), b.data(), e.data(), sign, c.data()),
+        "matpoly_mul_add");
+  return c;
+}
+
 // ---- PSFPerturbation (mp_perturbation.rs:57-62, :193-403) -------------------------------------------------------------
 class PSFPerturbation {
  public:

@@ -39,6 +39,9 @@ class RingParams(C.Structure):
     _fields_ = [("gp", GadgetParams), ("s", C.c_double), ("s_td", C.c_double), ("device", C.c_int32), ("flags", C.c_uint32)]
 
 
+MATPOLY_MUL_ADD_DEV = ("psf_matpoly_mul_add_negacyclic_dev", "psf_matpoly_mul_add_hat_dev", "psf_matpoly_mul_add_cyclic_dev", "psf_matpoly_mul_add_hat_cyclic_dev")
+MATPOLY_MUL_ADD_HOST = ("psf_matpoly_mul_add_negacyclic", "psf_matpoly_mul_add_cyclic")
+
 _lib = None
 
 
@@ -81,6 +84,13 @@ def open_library(path):
     L.psfgpv_destroy.argtypes = [C.c_void_p]
     L.psfring_destroy.restype = None
     L.psfring_destroy.argtypes = [C.c_void_p]
+    # the fused products E + sign * A B (psf_matpoly_mul_add_*): device forms (..., d_a, a_stride, trans_a, d_b, d_e, sign, d_c, io_bits, stream) and host forms
+    for name in MATPOLY_MUL_ADD_DEV:
+        getattr(L, name).argtypes = [C.c_int, C.c_uint64] + [C.c_size_t] * 5 + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                                                C.c_int, C.c_void_p]
+    for name in MATPOLY_MUL_ADD_HOST:
+        getattr(L, name).argtypes = [C.c_int, C.c_uint64] + [C.c_size_t] * 4 + [C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                                                                C.POINTER(C.c_uint64)]
     return L
 
 

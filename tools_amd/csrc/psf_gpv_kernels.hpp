@@ -153,9 +153,20 @@ __global__ __launch_bounds__(256) void k_polymul_negacyclic(uint64_t q, uint64_t
 // per output polynomial (c, i, j) at a time; per 256-coefficient chunk of it and per k < inner, A[c][i][k] and B[c][k][j] are staged in LDS (reduced mod
 // q) and thread t adds the terms of coefficient chunk + t.  Exact: for q < 2^31 the positive and negative parts are summed over all of `inner` in
 // 128 bits (inner n < 2^33 terms below 2^62) and reduced once; above, every term is reduced.
-__global__ __launch_bounds__(256) void k_matpoly_negacyclic(uint64_t q, uint64_t two64, uint32_t n, size_t count, size_t rows, size_t inner, size_t cols,
-                                                            const uint64_t* __restrict__ A, size_t a_stride, int trans_a, const int64_t* __restrict__ Bp,
-                                                            uint64_t* __restrict__ out) {
+// FMA (psf_matpoly_mul_add_*_dev): out = E + sign * product, sign = +1 or -1.  The thread that holds coefficient x in [0, q) reads the matching int64 e
+// of E (any value, reduced to [0, q)), forms e + x or e + (q - x) < 2q < 2^63 and subtracts q once if needed.  E may be out: the word is read by the
+// thread that then writes it.
+template <bool FMA> __device__ __forceinline__ uint64_t matpoly_epilogue(uint64_t x, uint64_t q, const int64_t* E, size_t idx, int sign) {
+  if constexpr (!FMA) return x;
+  else {
+    const int64_t v = E[idx] % (int64_t)q;
+    const uint64_t e = (uint64_t)(v < 0 ? v + (int64_t)q : v), s = e + (sign < 0 ? q - x : x);
+    return s >= q ? s - q : s;
+  }
+}
+template <bool FMA>
+__device__ __forceinline__ void matpoly_negacyclic_body(uint64_t q, uint64_t two64, uint32_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint64_t* A,
+                                                        size_t a_stride, int trans_a, const int64_t* Bp, const int64_t* E, int sign, uint64_t* out) {
   extern __shared__ __attribute__((aligned(16))) uint64_t mp_smem[];   // a[n] | b[n]
   uint64_t* sa = mp_smem;
   uint64_t* sb = mp_smem + n;
@@ -188,9 +199,20 @@ __global__ __launch_bounds__(256) void k_matpoly_negacyclic(uint64_t q, uint64_t
       }
       if (cc >= n) continue;
       if (small) { pos = acc128_mod(P, q, two64); neg = acc128_mod(N, q, two64); }
-      out[o * n + cc] = pos >= neg ? pos - neg : pos + q - neg;
+      out[o * n + cc] = matpoly_epilogue<FMA>(pos >= neg ? pos - neg : pos + q - neg, q, E, o * n + cc, sign);
     }
   }
+}
+__global__ __launch_bounds__(256) void k_matpoly_negacyclic(uint64_t q, uint64_t two64, uint32_t n, size_t count, size_t rows, size_t inner, size_t cols,
+                                                            const uint64_t* __restrict__ A, size_t a_stride, int trans_a, const int64_t* __restrict__ Bp,
+                                                            uint64_t* __restrict__ out) {
+  matpoly_negacyclic_body<false>(q, two64, n, count, rows, inner, cols, A, a_stride, trans_a, Bp, nullptr, 1, out);
+}
+// E and out without __restrict__: they may be the same buffer
+__global__ __launch_bounds__(256) void k_matpoly_fma_negacyclic(uint64_t q, uint64_t two64, uint32_t n, size_t count, size_t rows, size_t inner, size_t cols,
+                                                                const uint64_t* __restrict__ A, size_t a_stride, int trans_a, const int64_t* __restrict__ Bp,
+                                                                const int64_t* E, int sign, uint64_t* out) {
+  matpoly_negacyclic_body<true>(q, two64, n, count, rows, inner, cols, A, a_stride, trans_a, Bp, E, sign, out);
 }
 
 // ---- the cyclic ring Z_q[X]/(X^n - 1) (common_moduli.rs:72-79): the same two products for every q < 2^62 without an NTT ------------------------------
@@ -226,9 +248,9 @@ __global__ __launch_bounds__(256) void k_polymul_cyclic(uint64_t q, uint64_t two
   }
 }
 
-__global__ __launch_bounds__(256) void k_matpoly_cyclic(uint64_t q, uint64_t two64, uint32_t n, size_t count, size_t rows, size_t inner, size_t cols,
-                                                        const uint64_t* __restrict__ A, size_t a_stride, int trans_a, const int64_t* __restrict__ Bp,
-                                                        uint64_t* __restrict__ out) {
+template <bool FMA>
+__device__ __forceinline__ void matpoly_cyclic_body(uint64_t q, uint64_t two64, uint32_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint64_t* A,
+                                                    size_t a_stride, int trans_a, const int64_t* Bp, const int64_t* E, int sign, uint64_t* out) {
   extern __shared__ __attribute__((aligned(16))) uint64_t mc_smem[];   // a[n] | b[n]
   uint64_t* sa = mc_smem;
   uint64_t* sb = mc_smem + n;
@@ -260,9 +282,19 @@ __global__ __launch_bounds__(256) void k_matpoly_cyclic(uint64_t q, uint64_t two
         }
       }
       if (cc >= n) continue;
-      out[o * n + cc] = small ? acc128_mod(S, q, two64) : sum;
+      out[o * n + cc] = matpoly_epilogue<FMA>(small ? acc128_mod(S, q, two64) : sum, q, E, o * n + cc, sign);
     }
   }
+}
+__global__ __launch_bounds__(256) void k_matpoly_cyclic(uint64_t q, uint64_t two64, uint32_t n, size_t count, size_t rows, size_t inner, size_t cols,
+                                                        const uint64_t* __restrict__ A, size_t a_stride, int trans_a, const int64_t* __restrict__ Bp,
+                                                        uint64_t* __restrict__ out) {
+  matpoly_cyclic_body<false>(q, two64, n, count, rows, inner, cols, A, a_stride, trans_a, Bp, nullptr, 1, out);
+}
+__global__ __launch_bounds__(256) void k_matpoly_fma_cyclic(uint64_t q, uint64_t two64, uint32_t n, size_t count, size_t rows, size_t inner, size_t cols,
+                                                            const uint64_t* __restrict__ A, size_t a_stride, int trans_a, const int64_t* __restrict__ Bp,
+                                                            const int64_t* E, int sign, uint64_t* out) {
+  matpoly_cyclic_body<true>(q, two64, n, count, rows, inner, cols, A, a_stride, trans_a, Bp, E, sign, out);
 }
 
 // The NTT forms of these products (one transform per wavefront, Montgomery arithmetic) are in psf_ntt_kernels.hpp / psf_ntt.hip.

@@ -1,6 +1,7 @@
 // psf_ntt.hip -- NTT products over R_q = Z_q[X]/(X^n + 1) and Z_q[X]/(X^n - 1): plan cache, shape dispatch and launches (psf_ntt_api.hpp).
 // PolynomialRingZq multiplication under gadget_ring.rs:78 and gpv_ring.rs:243-247; the kernels are in psf_ntt_kernels.hpp / psf_ntt_core.hpp.  They read
 // the ring from the table of zetas alone (NttDev::zetas), so the cyclic ring takes the same instantiations with the table of make_ntt_plan_cyclic.
+// The fused products C = E +- op(A) B (k_matpoly_fma) are launched from psf_ntt_fma.hip, through the plan access of psf_ntt_api.hpp.
 #include <cstdlib>
 #include <map>
 #include <set>
@@ -14,6 +15,24 @@
 using namespace psf;
 using namespace psf::ntt;
 
+namespace {
+
+// the shapes that have a wave kernel (make_ntt_tables decides logn, ld, qb).  The one list of them: psf_ntt_fma.hip includes this file with
+// PSF_NTT_SHAPES_ONLY defined and gets this function alone, so both units instantiate their kernels over the same shapes.
+template <class F> bool for_shape(int logn, int ld, int qb, F&& f) {
+#define PSF_SHAPE(LN, LDV, QBV) if (logn == LN && ld == LDV && qb == QBV) { f(ic<LN>{}, ic<LDV>{}, ic<QBV>{}); return true; }
+  PSF_SHAPE(7, 0, 12) PSF_SHAPE(8, 1, 12) PSF_SHAPE(9, 2, 12)
+  PSF_SHAPE(7, 0, 14) PSF_SHAPE(7, 1, 14) PSF_SHAPE(8, 0, 14) PSF_SHAPE(8, 1, 14) PSF_SHAPE(8, 2, 14) PSF_SHAPE(9, 0, 14) PSF_SHAPE(9, 1, 14) PSF_SHAPE(9, 2, 14)
+  PSF_SHAPE(10, 0, 14) PSF_SHAPE(10, 1, 14) PSF_SHAPE(10, 2, 14)
+  PSF_SHAPE(7, 0, 0) PSF_SHAPE(7, 1, 0) PSF_SHAPE(8, 0, 0) PSF_SHAPE(8, 1, 0) PSF_SHAPE(8, 2, 0) PSF_SHAPE(9, 0, 0) PSF_SHAPE(9, 1, 0) PSF_SHAPE(9, 2, 0)
+  PSF_SHAPE(10, 0, 0) PSF_SHAPE(10, 1, 0) PSF_SHAPE(10, 2, 0)
+#undef PSF_SHAPE
+  return false;
+}
+
+}  // namespace
+
+#ifndef PSF_NTT_SHAPES_ONLY
 namespace {
 
 // ---- generic form: any power-of-two n <= 8192, any plan (leaf degree d = n >> L of any size), 32-bit Montgomery arithmetic, data in LDS ------------
@@ -108,18 +127,6 @@ Plan* plan_for(int device, uint64_t q, size_t n, psf_status* st, NttRing ring = 
   return P->route ? P : nullptr;
 }
 
-// the shapes that have a wave kernel (make_ntt_tables decides logn, ld, qb)
-template <class F> bool for_shape(int logn, int ld, int qb, F&& f) {
-#define PSF_SHAPE(LN, LDV, QBV) if (logn == LN && ld == LDV && qb == QBV) { f(ic<LN>{}, ic<LDV>{}, ic<QBV>{}); return true; }
-  PSF_SHAPE(7, 0, 12) PSF_SHAPE(8, 1, 12) PSF_SHAPE(9, 2, 12)
-  PSF_SHAPE(7, 0, 14) PSF_SHAPE(7, 1, 14) PSF_SHAPE(8, 0, 14) PSF_SHAPE(8, 1, 14) PSF_SHAPE(8, 2, 14) PSF_SHAPE(9, 0, 14) PSF_SHAPE(9, 1, 14) PSF_SHAPE(9, 2, 14)
-  PSF_SHAPE(10, 0, 14) PSF_SHAPE(10, 1, 14) PSF_SHAPE(10, 2, 14)
-  PSF_SHAPE(7, 0, 0) PSF_SHAPE(7, 1, 0) PSF_SHAPE(8, 0, 0) PSF_SHAPE(8, 1, 0) PSF_SHAPE(8, 2, 0) PSF_SHAPE(9, 0, 0) PSF_SHAPE(9, 1, 0) PSF_SHAPE(9, 2, 0)
-  PSF_SHAPE(10, 0, 0) PSF_SHAPE(10, 1, 0) PSF_SHAPE(10, 2, 0)
-#undef PSF_SHAPE
-  return false;
-}
-
 NttDev dev_args(const Plan* P, int e, int e_fa) {
   NttDev a;
   a.q = P->tb.q; a.qinv16 = P->tb.qinv16; a.nqinv32 = P->tb.nqinv32; a.r2 = P->tb.r2;
@@ -137,6 +144,18 @@ unsigned wave_grid(size_t count) {                                       // four
 }  // namespace
 
 namespace psf {
+
+psf_status ntt_wave_plan(int device, uint64_t q, size_t n, NttRing ring, int io_bits, NttWavePlan* out) {
+  psf_status rc;
+  Plan* P = plan_for(device, q, n, &rc, ring);
+  if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
+  if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
+  out->plan = P; out->logn = P->tb.logn; out->ld = P->tb.ld; out->qb = P->tb.qb; out->q = P->tb.q;
+  out->zeta_words = (P->tb.qb == 12 ? 4u : 2u) << P->pl.L;
+  return PSF_OK;
+}
+void ntt_dev_args(const NttWavePlan& w, int e, int e_fa, ntt::NttDev* out) { *out = dev_args(static_cast<const Plan*>(w.plan), e, e_fa); }
+unsigned ntt_wave_grid(size_t items) { return wave_grid(items); }
 
 int ntt_route(uint64_t q, size_t n, NttRing ring) {
   psf_status st;
@@ -263,12 +282,7 @@ psf_status ntt_matmul_dev(int device, uint64_t q, size_t n, const NttMatShape& s
   const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
     constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
     const NttDev a = dev_args(P, Kern<LN, LDV, QBV>::E, Kern<LN, LDV, QBV>::E + 1);
-    MatArgs m;
-    m.count = s.count; m.rows = s.rows; m.inner = s.inner; m.cols = s.cols; m.a_stride = a_stride; m.trans_a = s.trans_a;
-    m.tiles = (s.rows + MatTile<LN>::RT - 1) / MatTile<LN>::RT;
-    m.items = s.count * s.cols * m.tiles;
-    const int r1 = (int)((1u << 16) % P->tb.q);
-    m.r1 = r1 > (int)(P->tb.q / 2) ? r1 - (int)P->tb.q : r1;
+    const MatArgs m = make_mat_args(s.count, s.rows, s.inner, s.cols, s.trans_a, a_stride, MatTile<LN>::RT, P->tb.q);
     const size_t smem = (zn + (stage ? s.rows * s.inner * n : 0)) * sizeof(uint32_t);
     const dim3 grid(wave_grid(m.items));
     auto go = [&](auto io) {
@@ -288,3 +302,4 @@ psf_status ntt_matmul_dev(int device, uint64_t q, size_t n, const NttMatShape& s
 }
 
 }  // namespace psf
+#endif  // PSF_NTT_SHAPES_ONLY

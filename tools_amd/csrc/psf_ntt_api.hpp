@@ -34,4 +34,24 @@ struct NttMatShape { size_t count, rows, inner, cols; int trans_a; };
 psf_status ntt_matmul_dev(int device, uint64_t q, size_t n, const NttMatShape& s, const void* d_a, size_t a_stride, bool hat, const void* d_b, void* d_c,
                           int io_bits, hipStream_t st, NttRing ring = kNegacyclic);
 
+// C[c] = E[c] + sign * op(A[c]) B[c] (psf_matpoly_mul_add_*_dev; arguments checked by the caller, sign = +1 or -1): ntt_matmul_dev with the epilogue of
+// k_matpoly_fma.  E in the io_bits layout and value contract of B; d_e == d_c is the one overlap allowed.  Defined in psf_ntt_fma.hip.
+psf_status ntt_matfma_dev(int device, uint64_t q, size_t n, const NttMatShape& s, const void* d_a, size_t a_stride, bool hat, const void* d_b, const void* d_e,
+                          int sign, void* d_c, int io_bits, hipStream_t st, NttRing ring = kNegacyclic);
+
+// ---- what another translation unit of wave kernels needs from psf_ntt.hip: the cached plan of (device, q, n, ring) and the launch conventions ----------
+namespace ntt { struct NttDev; }
+struct NttWavePlan {
+  const void* plan;          // the cache entry (owned by psf_ntt.hip)
+  int logn, ld, qb;          // the wave shape (for_shape)
+  uint32_t q;
+  size_t zeta_words;         // words of LDS the zetas of this shape take in front of anything else
+};
+// PSF_ERR_UNSUPPORTED unless (q, n) has a wave kernel that reads io_bits words; PSF_ERR_HIP when the tables cannot be placed on the device
+psf_status ntt_wave_plan(int device, uint64_t q, size_t n, NttRing ring, int io_bits, NttWavePlan* out);
+// the kernel argument of the plan for a product that carries e (e_fa: one more) factors R^-1 (Kern::E)
+void ntt_dev_args(const NttWavePlan& w, int e, int e_fa, ntt::NttDev* out);
+// workgroups of 256 threads for `items` wave-sized work items
+unsigned ntt_wave_grid(size_t items);
+
 }  // namespace psf

@@ -6,8 +6,10 @@
 //                      K leaf products accumulated, ONE inverse transform per preimage
 //   k_matpoly_mul      C = op(A) B over R_q for batches of matrices of polynomials: B transformed once per row tile, sums of leaf products at one
 //                      Montgomery scale (Core::acc_add / acc_tick), ONE inverse transform per output polynomial
+//   k_matpoly_fma      C = E +- op(A) B: the same body with an epilogue that adds the matching word of E before the store
 // 16-bit I/O (a: uint16 in [0, q), b: int16 in (-q, q), out: uint16) beside the 64-bit ABI of psf_poly_mul_negacyclic.
 #pragma once
+#include <cstddef>
 #include <hip/hip_runtime.h>
 #include "psf_ntt_core.hpp"
 
@@ -176,6 +178,18 @@ template <int QB, class M> __device__ __forceinline__ typename M::V reduce_u64(u
   }
 }
 
+// The same residue in [0, q) for the 32-bit form WITHOUT a division (the epilogue of k_matpoly_fma): x = hi 2^32 + lo with hi read as unsigned, minus
+// 2^64 when x < 0.  A Montgomery product with R^2 (p.r2) is a multiplication by R = 2^32, one with 1 a division by it: lo mod q = (lo R) R^-1,
+// hi 2^32 mod q = hi R, 2^64 mod q = R^2.  mul takes any 32-bit first factor beside a canonical second one ((a b + m q) / 2^32 < 2q still holds).
+template <class M> __device__ __forceinline__ uint32_t reduce_i64_mont32(int64_t x, const M& md, const NttDev& p) {
+  if (__all(x >= 0 && x < (int64_t)p.q)) return (uint32_t)x;
+  const uint32_t lo = (uint32_t)x, hi = (uint32_t)((uint64_t)x >> 32);
+  const uint32_t l = md.mul(md.mul(lo, p.r2), 1u);
+  uint32_t h = md.mul(hi, p.r2);
+  h = x < 0 ? md.sub(h, p.r2) : h;
+  return md.add(h, l);
+}
+
 // the wave's number inside its workgroup as a SCALAR: row addresses are then computed once per wave, in SGPRs
 static __device__ __forceinline__ unsigned wave_in_block() { return (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
@@ -205,6 +219,26 @@ template <int LOGN, int LD, int QB> struct Kern {
         if constexpr (SIGNED) x[r] = reduce_i64<QB>(reinterpret_cast<const int64_t*>(base)[i], md, p);
         else x[r] = reduce_u64<QB>(reinterpret_cast<const uint64_t*>(base)[i], md, p);
       }
+    }
+  }
+  // the addend E of k_matpoly_fma, read like operand b (load<IO, true>); 64-bit words in the 32-bit form are reduced without a division
+  template <int IO> static __device__ __forceinline__ void load_addend(V (&e)[C], const void* base, size_t row, int lane, const M& md, const NttDev& p) {
+    if constexpr (IO == 64 && QB == 0) {
+#pragma unroll
+      for (int r = 0; r < C; ++r) e[r] = reduce_i64_mont32(reinterpret_cast<const int64_t*>(base)[row * N + (size_t)r * 64 + lane], md, p);
+    } else {
+      load<IO, true>(e, base, row, lane, md, p);
+    }
+  }
+  // x in [0, q), e in (-q, q) (16-bit form; load<IO, true>) or [0, q) (32-bit form)  ->  x = e + sign x mod q in [0, q), sign = +1 or -1.
+  // With xs = x or q - x (in [0, q]) the sum e + xs lies in (-q, 2q) / [0, 2q) for either sign: one conditional +q (16-bit form only), one conditional -q.
+  static __device__ __forceinline__ void add_signed(V (&x)[C], const V (&e)[C], int sign, const NttDev& p) {
+#pragma unroll
+    for (int r = 0; r < C; ++r) {
+      const uint32_t xs = sign < 0 ? p.q - (uint32_t)x[r] : (uint32_t)x[r];
+      uint32_t s = (uint32_t)e[r] + xs;
+      if constexpr (QB != 0) s = DevWave::cadd(s, p.q);
+      x[r] = (V)DevWave::csub(s, p.q);
     }
   }
   template <int IO> static __device__ __forceinline__ void store(const V (&x)[C], void* base, size_t row, int lane) {
@@ -337,71 +371,34 @@ struct MatArgs {
 // finish per output polynomial.  HAT = 0: A as polynomials (IO layout of a), transformed here; 1: A as images (psf_ntt_forward_dev) in global
 // memory; 2: one set of images for every batch, staged in LDS behind the zetas.
 template <int LOGN> struct MatTile { static constexpr int C = 1 << (LOGN - 6), RT = 32 / C > 8 ? 8 : 32 / C; };   // RT * C = 32 accumulator registers
+// the arguments of a launch (host side): rt = MatTile<LOGN>::RT of the shape, q the modulus of the plan
+inline MatArgs make_mat_args(size_t count, size_t rows, size_t inner, size_t cols, int trans_a, size_t a_stride, int rt, uint32_t q) {
+  MatArgs m;
+  m.count = count; m.rows = rows; m.inner = inner; m.cols = cols; m.a_stride = a_stride; m.trans_a = trans_a;
+  m.tiles = (rows + rt - 1) / rt;
+  m.items = count * cols * m.tiles;
+  const int r1 = (int)((1u << 16) % q);
+  m.r1 = r1 > (int)(q / 2) ? r1 - (int)q : r1;
+  return m;
+}
 template <int LOGN, int LD, int QB, int IO, int HAT>
 __global__ __launch_bounds__(256) void k_matpoly_mul(NttDev p, MatArgs m, const void* __restrict__ A, const void* __restrict__ B, void* __restrict__ out) {
-  using KN = Kern<LOGN, LD, QB>;
-  using V = typename KN::V;
-  constexpr int C = KN::C, RT = MatTile<LOGN>::RT;
-  extern __shared__ __attribute__((aligned(16))) uint32_t mm_smem[];   // zetas [ZN] (| images [rows * inner][C][64] when HAT = 2)
-  uint32_t* zt = mm_smem;
-  const uint32_t* ah = mm_smem + KN::ZN;
-  if constexpr (HAT == 2) {
-    const size_t words = m.rows * m.inner * (size_t)KN::N;
-    for (size_t i = threadIdx.x; i < words; i += blockDim.x) mm_smem[KN::ZN + i] = reinterpret_cast<const uint32_t*>(A)[i];
-  }
-  KN::load_tables(zt, p);
-  const auto md = make_policy<QB>(p, KN::L);
-  const int lane = DevWave::lane();
-  const size_t waves = (size_t)gridDim.x * (blockDim.x >> 6);
-  const uint32_t* zf = zt;
-  const uint32_t* zi = zt + (1 << KN::L);
-  for (size_t it = (size_t)blockIdx.x * (blockDim.x >> 6) + wave_in_block(); it < m.items; it += waves) {
-    const size_t tile = it % m.tiles, cj = it / m.tiles, j = cj % m.cols, c = cj / m.cols, i0 = tile * RT;
-    const int nr = (int)(m.rows - i0 < (size_t)RT ? m.rows - i0 : (size_t)RT);
-    V acc[RT][C];
-#pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-      for (int r = 0; r < C; ++r) acc[t][r] = 0;
-    int since = 0;
-    const size_t dia = m.trans_a ? 1 : m.inner;                         // A[i][k] -> A[i + 1][k] in storage order
-    for (size_t k = 0; k < m.inner; ++k) {
-      V b[C];
-      KN::template load<IO, true>(b, B, (c * m.inner + k) * m.cols + j, lane, md, p);
-      KN::K::forward(b, md, zf, lane);
-      const size_t ia0 = m.trans_a ? k * m.rows + i0 : i0 * m.inner + k;
-#pragma unroll
-      for (int t = 0; t < RT; ++t) {
-        if (t < nr) {
-          const size_t ia = ia0 + t * dia;
-          V a[C], pr[C];
-          if constexpr (HAT == 0) {
-            KN::template load<IO, false>(a, A, c * m.a_stride + ia, lane, md, p);
-            KN::K::forward(a, md, zf, lane);
-          } else if constexpr (HAT == 1) {
-            const uint32_t* h = reinterpret_cast<const uint32_t*>(A) + c * m.a_stride + ia * KN::N;
-#pragma unroll
-            for (int r = 0; r < C; ++r) a[r] = (V)h[r * 64 + lane];
-          } else {
-#pragma unroll
-            for (int r = 0; r < C; ++r) a[r] = (V)ah[ia * KN::N + r * 64 + lane];
-          }
-          KN::K::leafmul(pr, a, b, md, zf, lane);
-          KN::K::acc_add(acc[t], pr, md);
-        }
-      }
-      KN::K::acc_tick(acc, md, (V)m.r1, since);
-    }
-#pragma unroll
-    for (int t = 0; t < RT; ++t) {
-      if (t < nr) {
-        KN::K::acc_close(acc[t], md);
-        KN::K::inverse(acc[t], md, zi, lane);
-        KN::K::finish(acc[t], md, (V)(QB != 0 ? p.fin_fa : p.fin));
-        KN::template store<IO>(acc[t], out, (c * m.rows + i0 + t) * m.cols + j, lane);
-      }
-    }
-  }
+#define PSF_MATPOLY_FMA 0
+#include "psf_ntt_matpoly_body.hpp"
+#undef PSF_MATPOLY_FMA
+}
+// C[c] = E[c] + sign * op(A[c]) B[c] (psf_matpoly_mul_add_*_dev): the same body with the epilogue.  E and out carry no __restrict__: they may be the
+// same buffer.  Instantiated in psf_ntt_fma.hip, a translation unit of its own.
+// The kernel-argument segment of k_matpoly_fma as a struct: the arguments in their order, each at its natural alignment (the layout rule of the
+// segment is the layout rule of a struct).  The epilogue reads E, sign and out through it; tests/test_matpoly_add_isa.py compares the offsets with
+// the code object's.
+struct MatFmaKernArgs { NttDev p; MatArgs m; const void* A; const void* B; const void* E; int sign; void* out; };
+static_assert(offsetof(MatFmaKernArgs, E) == 112 && offsetof(MatFmaKernArgs, sign) == 120 && offsetof(MatFmaKernArgs, out) == 128, "k_matpoly_fma: argument layout");
+template <int LOGN, int LD, int QB, int IO, int HAT>
+__global__ __launch_bounds__(256) void k_matpoly_fma(NttDev p, MatArgs m, const void* __restrict__ A, const void* __restrict__ B, const void* E, int sign, void* out) {
+#define PSF_MATPOLY_FMA 1
+#include "psf_ntt_matpoly_body.hpp"
+#undef PSF_MATPOLY_FMA
 }
 
 }  // namespace ntt

@@ -1161,11 +1161,15 @@ psf_status psf_poly_mul_hat_cyclic_dev(int device, uint64_t q, size_t n, size_t 
 // ---- R_q matrix products (MatPolynomialRingZq * MatPolynomialRingZq: gpv_ring.rs:245, gadget_ring.rs:78 and :190-202, short_basis_ring.rs:183-198) ----
 // Every argument is checked here, before the first HIP call (plan_for allocates on the device, so it comes after).  hat: A given by its images.
 static constexpr size_t kMatpolyMaxInner = (size_t)1 << 20;
+// The addend E of the fused forms C = E + sign * op(A) B (psf_matpoly_mul_add_*): laid out like C, in B's word type; sign is +1 or -1.
+struct MatAddend { const void* d_e; int sign; };
+// add = nullptr: a plain product.  Otherwise E is checked with the rest: not NULL, and either E == C exactly (in place) or no byte in common with C.
 static psf_status matpoly_check(uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride, bool hat,
-                                int trans_a, const void* d_b, const void* d_c, int io_bits, NttRing ring = kNegacyclic) {
+                                int trans_a, const void* d_b, const void* d_c, int io_bits, NttRing ring = kNegacyclic, const MatAddend* add = nullptr) {
   if (q <= 1 || q >= (1ull << 62) || n < 1 || n > 8192) return PSF_ERR_PARAM;
   if (rows == 0 || inner == 0 || cols == 0 || (trans_a != 0 && trans_a != 1) || (io_bits != 16 && io_bits != 64)) return PSF_ERR_PARAM;
-  if (count && (!d_a || !d_b || !d_c)) return PSF_ERR_PARAM;
+  if (add && add->sign != 1 && add->sign != -1) return PSF_ERR_PARAM;
+  if (count && (!d_a || !d_b || !d_c || (add && !add->d_e))) return PSF_ERR_PARAM;
   // byte ranges of A (all batches), B and C; any product that overflows size_t is a malformed call
   const size_t w = io_bits / 8, wa = hat ? sizeof(uint32_t) : w;
   size_t ri, ic, rc, a_one, a_all = 0, b_all, c_all;
@@ -1182,6 +1186,11 @@ static psf_status matpoly_check(uint64_t q, size_t n, size_t count, size_t rows,
     const uintptr_t a0 = (uintptr_t)d_a, b0 = (uintptr_t)d_b, c0 = (uintptr_t)d_c;
     if (a0 + a_all < a0 || b0 + b_all < b0 || c0 + c_all < c0) return PSF_ERR_PARAM;
     if ((c0 < a0 + a_all && a0 < c0 + c_all) || (c0 < b0 + b_all && b0 < c0 + c_all)) return PSF_ERR_PARAM;   // the output overlaps an input
+    if (add) {                                              // E: c_all bytes; on top of C exactly, or apart from it
+      const uintptr_t e0 = (uintptr_t)add->d_e;
+      if (e0 + c_all < e0) return PSF_ERR_PARAM;
+      if (e0 != c0 && c0 < e0 + c_all && e0 < c0 + c_all) return PSF_ERR_PARAM;
+    }
   }
   if (inner > kMatpolyMaxInner) return PSF_ERR_UNSUPPORTED;
   const int route = ntt_route(q, n, ring);                  // host tables only (device -1): no HIP call
@@ -1223,7 +1232,82 @@ static psf_status matpoly_dev_any(int device, uint64_t q, size_t n, size_t count
   return PSF_OK;
 }
 
+// C[c] = E[c] + sign * op(A[c]) B[c]: the checks of matpoly_dev_any with E and sign, then the fused kernels (k_matpoly_fma from psf_ntt_fma.hip, or
+// the schoolbook kernels with the same epilogue).  What the product entry points launch is untouched.
+static psf_status matpoly_add_dev_any(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
+                                      bool hat, int trans_a, const void* d_b, const void* d_e, int sign, void* d_c, int io_bits, hipStream_t st,
+                                      NttRing ring = kNegacyclic) {
+  const MatAddend add{d_e, sign};
+  const psf_status chk = matpoly_check(q, n, count, rows, inner, cols, d_a, a_stride, hat, trans_a, d_b, d_c, io_bits, ring, &add);
+  if (chk != PSF_OK || count == 0) return chk;
+  const psf_status ud = use_device(device);
+  if (ud != PSF_OK) return ud;
+  if (ntt_route(q, n, ring) == 2)
+    return ntt_matfma_dev(device, q, n, NttMatShape{count, rows, inner, cols, trans_a}, d_a, a_stride, hat, d_b, d_e, sign, d_c, io_bits, st, ring);
+  const uint64_t two64 = (uint64_t)((((u128)1) << 64) % q);
+  const size_t outs = count * rows * cols;
+  const unsigned grid = (unsigned)(outs < 16384 ? outs : 16384);
+  const void* kern = ring == kCyclic ? reinterpret_cast<const void*>(k_matpoly_fma_cyclic) : reinterpret_cast<const void*>(k_matpoly_fma_negacyclic);
+  const psf_status rl = raise_lds_once(kern, device, 2 * n * sizeof(uint64_t));      // n > 4096: above the default LDS limit
+  if (rl != PSF_OK) return rl;
+  if (ring == kCyclic)
+    hipLaunchKernelGGL(k_matpoly_fma_cyclic, dim3(grid), dim3(256), 2 * n * sizeof(uint64_t), st, q, two64, (uint32_t)n, count, rows, inner, cols,
+                       (const uint64_t*)d_a, a_stride, trans_a, (const int64_t*)d_b, (const int64_t*)d_e, sign, (uint64_t*)d_c);
+  else
+    hipLaunchKernelGGL(k_matpoly_fma_negacyclic, dim3(grid), dim3(256), 2 * n * sizeof(uint64_t), st, q, two64, (uint32_t)n, count, rows, inner, cols,
+                       (const uint64_t*)d_a, a_stride, trans_a, (const int64_t*)d_b, (const int64_t*)d_e, sign, (uint64_t*)d_c);
+  HIP_TRY(hipGetLastError());
+  return PSF_OK;
+}
+// host buffers, one batch: c = e + sign * a b.  c == e (in place) is allowed, like d_e == d_c.
+static psf_status matpoly_add_host(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, const int64_t* e,
+                                   int sign, uint64_t* c, NttRing ring) {
+  const MatAddend add{e, sign};
+  const psf_status chk = matpoly_check(q, n, 1, rows, inner, cols, a, 0, false, 0, b, c, 64, ring, &add);
+  if (chk != PSF_OK) return chk;
+  const psf_status ud = use_device(device);
+  if (ud != PSF_OK) return ud;
+  const size_t na = rows * inner * n * sizeof(uint64_t), nb = inner * cols * n * sizeof(int64_t), nc = rows * cols * n * sizeof(uint64_t);
+  DevBuf da, db, dc;
+  HIP_TRY(da.alloc(na));
+  HIP_TRY(db.alloc(nb));
+  HIP_TRY(dc.alloc(nc));
+  HIP_TRY(da.upload(a, na));
+  HIP_TRY(db.upload(b, nb));
+  HIP_TRY(dc.upload(e, nc));                                // E goes into C's buffer: the device call runs in place
+  const psf_status rc = matpoly_add_dev_any(device, q, n, 1, rows, inner, cols, da.as<void>(), 0, false, 0, db.as<void>(), dc.as<void>(), sign, dc.as<void>(), 64,
+                                            nullptr, ring);
+  if (rc != PSF_OK) return rc;
+  HIP_TRY(dc.download(c, nc));
+  return PSF_OK;
+}
+
 extern "C" {
+
+psf_status psf_matpoly_mul_add_negacyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
+                                              int trans_a, const void* d_b, const void* d_e, int sign, void* d_c, int io_bits, void* stream) {
+  return matpoly_add_dev_any(device, q, n, count, rows, inner, cols, d_a, a_stride, false, trans_a, d_b, d_e, sign, d_c, io_bits, (hipStream_t)stream);
+}
+psf_status psf_matpoly_mul_add_hat_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint32_t* d_hat, size_t hat_stride,
+                                       int trans_a, const void* d_b, const void* d_e, int sign, void* d_c, int io_bits, void* stream) {
+  return matpoly_add_dev_any(device, q, n, count, rows, inner, cols, d_hat, hat_stride, true, trans_a, d_b, d_e, sign, d_c, io_bits, (hipStream_t)stream);
+}
+psf_status psf_matpoly_mul_add_negacyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, const int64_t* e,
+                                          int sign, uint64_t* c) {
+  return matpoly_add_host(device, q, n, rows, inner, cols, a, b, e, sign, c, kNegacyclic);
+}
+psf_status psf_matpoly_mul_add_cyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
+                                          int trans_a, const void* d_b, const void* d_e, int sign, void* d_c, int io_bits, void* stream) {
+  return matpoly_add_dev_any(device, q, n, count, rows, inner, cols, d_a, a_stride, false, trans_a, d_b, d_e, sign, d_c, io_bits, (hipStream_t)stream, kCyclic);
+}
+psf_status psf_matpoly_mul_add_hat_cyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const uint32_t* d_hat,
+                                              size_t hat_stride, int trans_a, const void* d_b, const void* d_e, int sign, void* d_c, int io_bits, void* stream) {
+  return matpoly_add_dev_any(device, q, n, count, rows, inner, cols, d_hat, hat_stride, true, trans_a, d_b, d_e, sign, d_c, io_bits, (hipStream_t)stream, kCyclic);
+}
+psf_status psf_matpoly_mul_add_cyclic(int device, uint64_t q, size_t n, size_t rows, size_t inner, size_t cols, const uint64_t* a, const int64_t* b, const int64_t* e,
+                                      int sign, uint64_t* c) {
+  return matpoly_add_host(device, q, n, rows, inner, cols, a, b, e, sign, c, kCyclic);
+}
 
 psf_status psf_matpoly_mul_negacyclic_dev(int device, uint64_t q, size_t n, size_t count, size_t rows, size_t inner, size_t cols, const void* d_a, size_t a_stride,
                                           int trans_a, const void* d_b, void* d_c, int io_bits, void* stream) {
