@@ -276,7 +276,8 @@ psf_status psf_decode_decompress_dev(int device, uint64_t q, uint32_t d, size_t 
  *                   |center| + 6 s + 1 < 2^15.  A draw that ends at the cap of 65 536 attempts writes floor(c + 1/2), a centre with
  *                   |c| >= 2^62 writes 0; either ORs 1 into *d_fail (a device int, may be NULL, never cleared by the call), and the host form
  *                   returns PSF_ERR_SAMPLER.
- * Not offered: binomials with p != 1/2, and the SHAKE-derived byte-exact SampleNTT / SamplePolyCBD of FIPS 203 (different contracts).
+ * Not offered: binomials with p != 1/2.  The SHAKE-derived, byte-exact SampleNTT / SamplePolyCBD of FIPS 203 are psf_sample_ntt_fips203* /
+ * psf_sample_cbd_fips203* below (a different contract: their bits come from Keccak, not from the randomness contract of this library).
  * PSF_ERR_PARAM, in this order: tag outside 64 ... 255; io_bits not 16 / 64; n = 0 or n >= 2^32; first_index + count > 2^56 or a byte count that
  * overflows size_t; a NULL output pointer with count > 0; q < 2; eta = 0; s not finite or s <= 0; a shared centre that is not finite.  Then
  * PSF_ERR_UNSUPPORTED: q >= 2^62; io_bits = 16 with q > 2^16; eta > 16; s > 2^28 (the candidate count must fit 32 bits); io_bits = 16 with
@@ -294,6 +295,55 @@ psf_status psf_sample_uniform(int device, uint64_t seed, uint32_t tag, uint64_t 
 psf_status psf_sample_cbd(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, uint32_t eta, int64_t* out);
 psf_status psf_sample_discrete_gauss(int device, uint64_t seed, uint32_t tag, uint64_t first_index, size_t count, size_t n, double center,
                                      const double* centers, double s, int64_t* out);
+/* FIPS 202 on the device: `count` independent messages of in_len bytes, message c at d_in + c * in_stride, digest c (out_len bytes) at
+ * d_out + c * out_stride -- the functions H (SHA3-256), G (SHA3-512), J and PRF (SHAKE256) and XOF (SHAKE128) of FIPS 203, batched.  One Keccak
+ * state per lane.  Any in_len (0 included; a message may take several absorb blocks) and, for the SHAKEs, any out_len >= 1 (several squeeze
+ * blocks); out_len must be 32 for SHA3-256 and 64 for SHA3-512.  Pointers and strides need no alignment (8-byte groups move as one load or store
+ * when base and stride are multiples of 8).
+ * PSF_ERR_PARAM, in this order: unknown func; the wrong out_len for a SHA3; out_len = 0; a stride smaller than its length; a NULL pointer with
+ * count > 0 (d_in may be NULL when in_len = 0); a byte count that overflows size_t; an output range that overlaps the input range.  count = 0 is
+ * PSF_OK.  Every check runs before the first HIP call; nothing is launched or written on an error.  A valid call without a device is PSF_ERR_HIP
+ * (no CPU fallback).  The device form is ordered on `stream`, allocates nothing and never synchronises; the host form allocates per call. */
+enum { PSF_SHA3_256 = 0, PSF_SHA3_512 = 1, PSF_SHAKE128 = 2, PSF_SHAKE256 = 3 };
+psf_status psf_keccak_dev(int device, int func, size_t count, const uint8_t* d_in, size_t in_len, size_t in_stride, uint8_t* d_out, size_t out_len,
+                          size_t out_stride, void* stream);
+psf_status psf_keccak(int device, int func, size_t count, const uint8_t* in, size_t in_len, size_t in_stride, uint8_t* out, size_t out_len, size_t out_stride);
+/* The byte-exact samplers of FIPS 203 (q = 3329, n = 256), one polynomial per lane, 256 coefficients per polynomial, polynomials contiguous.
+ *   sample_ntt  SampleNTT (Algorithm 7): coefficients in [0, q) in the order the algorithm produces them -- FIPS 203's NTT-domain representation
+ *               (psf_ntt_image_from_fips203_dev makes it an operand of the *_hat_dev products).  Words: uint16 or uint64 (operand a).
+ *               k = 0, the raw form: input c is the 34 bytes at d_seed + c * seed_stride, output polynomial c.
+ *               1 <= k <= 16, the matrix form: input c is a 32-byte rho_c; the output is count * k * k polynomials, polynomial (c, i, j), row-major,
+ *               = SampleNTT(rho_c || byte(j) || byte(i)): A_hat[i][j] of K-PKE.KeyGen, the rows = inner = k operand A of batch c.
+ *               The squeeze loop is capped at 8 SHAKE128 blocks (the standard's loop is unbounded; more than 6 are needed with probability below
+ *               2^-440): a polynomial that reaches the cap gets zeros for its remaining coefficients and ORs 1 into *d_fail (a device int, may be
+ *               NULL, never cleared by the call); the host form returns PSF_ERR_SAMPLER.
+ *   sample_cbd  SamplePolyCBD_eta(PRF_eta(sigma, N)) (Algorithm 8, PRF_eta(sigma, N) = SHAKE256(sigma || byte(N), 64 eta)): `count` 32-byte seeds
+ *               sigma_c at d_sigma + c * sigma_stride; polynomial (c, t), t < per_seed, uses N = first_nonce + t; count * per_seed polynomials of
+ *               signed coefficients in [-eta, eta].  Words: int16 or int64 (operand b and the addend E).
+ * PSF_ERR_PARAM, in this order: k > 16; eta = 0; first_nonce + per_seed > 256; io_bits not 16 / 64; a stride smaller than the seed; a NULL seed or
+ * output pointer with count > 0; a byte count that overflows size_t; an output range that overlaps the seeds.  Then PSF_ERR_UNSUPPORTED: eta other
+ * than 2 or 3.  count = 0 (or per_seed = 0) is PSF_OK.  Every check runs before the first HIP call; nothing is launched or written on an error.  A
+ * valid call without a device is PSF_ERR_HIP.  Device forms: ordered on `stream`, nothing allocated, never synchronising; seeds need no alignment,
+ * the output that of its word.  Host forms: 64-bit words, allocate per call, run on the device. */
+psf_status psf_sample_ntt_fips203_dev(int device, size_t count, uint32_t k, const uint8_t* d_seed, size_t seed_stride, void* d_out, int* d_fail, int io_bits,
+                                      void* stream);
+psf_status psf_sample_cbd_fips203_dev(int device, size_t count, uint32_t eta, const uint8_t* d_sigma, size_t sigma_stride, uint32_t first_nonce, uint32_t per_seed,
+                                      void* d_out, int io_bits, void* stream);
+psf_status psf_sample_ntt_fips203(int device, size_t count, uint32_t k, const uint8_t* seed, size_t seed_stride, uint64_t* out);
+psf_status psf_sample_cbd_fips203(int device, size_t count, uint32_t eta, const uint8_t* sigma, size_t sigma_stride, uint32_t first_nonce, uint32_t per_seed,
+                                  int64_t* out);
+/* NTT-domain interop at q = 3329, n = 256, the ring X^n + 1: FIPS 203 keeps A_hat, t_hat and s_hat in the NTT domain (an encapsulation key is
+ * ByteEncode_12(t_hat) || rho).  `from` reads `count` polynomials in FIPS 203's representation (uint16 in [0, q), or uint64 of any value read mod q)
+ * and writes images (count * 256 32-bit words) that every negacyclic *_hat_dev product accepts at (3329, 256), with exactly the results of the
+ * coefficient-domain polynomial NTT^-1(f_hat) of Algorithm 10.  `to` reads images written by psf_ntt_forward_dev or by `from` and writes canonical
+ * residues in [0, q): for an image of f, the output of Algorithm 9 on f.  Both representations hold the residues of f modulo the same 128 quadratic
+ * factors; the conversion is a fixed permutation of the factors and a change of scale.  Images of the cyclic ring and of other (q, n) have no such form.
+ * PSF_ERR_PARAM: io_bits not 16 / 64, a NULL pointer with count > 0, a byte count that overflows size_t, overlapping buffers.  count = 0 is PSF_OK.
+ * Checks before the first HIP call, PSF_ERR_HIP without a device.  Device forms: ordered on `stream`, nothing allocated.  Host forms: 64-bit words. */
+psf_status psf_ntt_image_from_fips203_dev(int device, size_t count, const void* d_fhat, int io_bits, uint32_t* d_hat, void* stream);
+psf_status psf_ntt_image_to_fips203_dev(int device, size_t count, const uint32_t* d_hat, void* d_fhat, int io_bits, void* stream);
+psf_status psf_ntt_image_from_fips203(int device, size_t count, const uint64_t* fhat, uint32_t* hat);
+psf_status psf_ntt_image_to_fips203(int device, size_t count, const uint32_t* hat, uint64_t* fhat);
 /* rot_minus_matrix (rotation_matrix.rs:85-96): mat[rows x cols] -> out[rows x rows*cols] */
 psf_status psf_rot_minus_matrix(const int64_t* mat, size_t rows, size_t cols, int64_t* out);
 

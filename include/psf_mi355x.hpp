@@ -66,6 +66,35 @@ inline MatZq matpoly_mul_add(int device, uint64_t q, size_t n, size_t rows, size
   return c;
 }
 
+// ---- FIPS 202 / FIPS 203 on device buffers (psf_keccak_dev, psf_sample_*_fips203_dev, psf_ntt_image_*_fips203_dev; rules in psf_mi355x.h) ----------
+inline void keccak_dev(int device, int func, size_t count, const uint8_t* d_in, size_t in_len, size_t in_stride, uint8_t* d_out, size_t out_len, size_t out_stride,
+                       void* stream = nullptr) {
+  check(psf_keccak_dev(device, func, count, d_in, in_len, in_stride, d_out, out_len, out_stride, stream), "keccak_dev");
+}
+// `count` messages of in_len bytes, packed; returns their digests of out_len bytes, packed
+inline std::vector<uint8_t> keccak(int device, int func, size_t count, const std::vector<uint8_t>& in, size_t in_len, size_t out_len) {
+  if (in.size() != count * in_len) throw PsfError(PSF_ERR_PARAM, "keccak");
+  std::vector<uint8_t> out(count * out_len);
+  check(psf_keccak(device, func, count, in.data(), in_len, in_len, out.data(), out_len, out_len), "keccak");
+  return out;
+}
+// SampleNTT: k = 0 raw form (34-byte inputs), 1 <= k <= 16 matrix form (32-byte rho, count k k polynomials)
+inline void sample_ntt_fips203_dev(int device, size_t count, uint32_t k, const uint8_t* d_seed, size_t seed_stride, void* d_out, int* d_fail = nullptr, int io_bits = 64,
+                                   void* stream = nullptr) {
+  check(psf_sample_ntt_fips203_dev(device, count, k, d_seed, seed_stride, d_out, d_fail, io_bits, stream), "sample_ntt_fips203_dev");
+}
+// SamplePolyCBD_eta(PRF_eta(sigma_c, first_nonce + t)), t < per_seed
+inline void sample_cbd_fips203_dev(int device, size_t count, uint32_t eta, const uint8_t* d_sigma, size_t sigma_stride, uint32_t first_nonce, uint32_t per_seed, void* d_out,
+                                   int io_bits = 64, void* stream = nullptr) {
+  check(psf_sample_cbd_fips203_dev(device, count, eta, d_sigma, sigma_stride, first_nonce, per_seed, d_out, io_bits, stream), "sample_cbd_fips203_dev");
+}
+inline void ntt_image_from_fips203_dev(int device, size_t count, const void* d_fhat, uint32_t* d_hat, int io_bits = 64, void* stream = nullptr) {
+  check(psf_ntt_image_from_fips203_dev(device, count, d_fhat, io_bits, d_hat, stream), "ntt_image_from_fips203_dev");
+}
+inline void ntt_image_to_fips203_dev(int device, size_t count, const uint32_t* d_hat, void* d_fhat, int io_bits = 64, void* stream = nullptr) {
+  check(psf_ntt_image_to_fips203_dev(device, count, d_hat, d_fhat, io_bits, stream), "ntt_image_to_fips203_dev");
+}
+
 // ---- PSFPerturbation (mp_perturbation.rs:57-62, :193-403) -------------------------------------------------------------
 class PSFPerturbation {
  public:

@@ -91,6 +91,18 @@ def open_library(path):
     for name in MATPOLY_MUL_ADD_HOST:
         getattr(L, name).argtypes = [C.c_int, C.c_uint64] + [C.c_size_t] * 4 + [C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
                                                                                 C.POINTER(C.c_uint64)]
+    # FIPS 202 / FIPS 203 (psf_keccak*, psf_sample_*_fips203*, psf_ntt_image_*_fips203*): byte buffers and strides
+    vp, sz, u32 = C.c_void_p, C.c_size_t, C.c_uint32
+    L.psf_keccak_dev.argtypes = [C.c_int, C.c_int, sz, vp, sz, sz, vp, sz, sz, vp]
+    L.psf_keccak.argtypes = [C.c_int, C.c_int, sz, vp, sz, sz, vp, sz, sz]
+    L.psf_sample_ntt_fips203_dev.argtypes = [C.c_int, sz, u32, vp, sz, vp, vp, C.c_int, vp]
+    L.psf_sample_ntt_fips203.argtypes = [C.c_int, sz, u32, vp, sz, vp]
+    L.psf_sample_cbd_fips203_dev.argtypes = [C.c_int, sz, u32, vp, sz, u32, u32, vp, C.c_int, vp]
+    L.psf_sample_cbd_fips203.argtypes = [C.c_int, sz, u32, vp, sz, u32, u32, vp]
+    L.psf_ntt_image_from_fips203_dev.argtypes = [C.c_int, sz, vp, C.c_int, vp, vp]
+    L.psf_ntt_image_to_fips203_dev.argtypes = [C.c_int, sz, vp, vp, C.c_int, vp]
+    L.psf_ntt_image_from_fips203.argtypes = [C.c_int, sz, vp, vp]
+    L.psf_ntt_image_to_fips203.argtypes = [C.c_int, sz, vp, vp]
     return L
 
 

@@ -1,6 +1,10 @@
 // psf_host.cpp -- host-side mirror of the reference's deterministic gadget helpers (see psf_host.hpp).
 #include <climits>
 #include "psf_host.hpp"
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>   // the library build compiles this file as HIP: psf_ntt_core.hpp then marks its functions for the device
+#endif
+#include "psf_ntt_fips.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -512,6 +516,46 @@ uint32_t ntt_final_scale(const NttTables& t, const NttPlan& pl, int e) {
   uint64_t f = pl.inv_scale % q;
   for (int i = 0; i <= e; ++i) f = mulmod_u64(f, R, q);
   return ntt_form(f, q, t.qb);
+}
+
+// FIPS 203's NTT-domain representation against the register image of the wave kernel at (3329, 256): see psf_ntt_fips.hpp
+ntt::FipsImageMap make_fips203_image_map() {
+  using S = ntt::Sched<8>;
+  using BD = ntt::Bounds16<12, 8, 1>;
+  ntt::FipsImageMap m;
+  const uint64_t q = 3329;
+  const NttPlan pl = make_ntt_plan(q, 256);
+  const NttTables tb = make_ntt_tables(pl);
+  if (!pl.ok || pl.L != 7 || pl.d != 2 || !tb.wave || tb.qb != 12) return m;
+  uint64_t gamma_fips[128];                                             // 17^(2 BitRev7(i) + 1)
+  for (uint32_t i = 0; i < 128; ++i) {
+    uint32_t br = 0;
+    for (uint32_t b = 0; b < 7; ++b) if (i & (1u << b)) br |= 1u << (6 - b);
+    gamma_fips[i] = powmod_u64(17, 2 * br + 1, q);
+  }
+  bool seen[128] = {};
+  for (uint32_t g = 0; g < 128; ++g) {
+    const uint64_t z = pl.zetas[64 + (g >> 1)] % q;
+    const uint64_t gamma = (g & 1) ? (q - z) % q : z;                   // the sign of Core::leafmul
+    uint32_t i = 0;
+    while (i < 128 && gamma_fips[i] != gamma) ++i;
+    if (i == 128 || seen[i]) return m;                                  // the two sets of leaf moduli differ: no map
+    seen[i] = true;
+    for (uint32_t e = 0; e < 2; ++e) {
+      const uint32_t p = 2 * g + e, word = (uint32_t)S::reg_of_nat((int)(p & 3)) * 64 + (p >> 2);
+      m.word_of[2 * i + e] = (uint8_t)word;
+      m.fips_of[word] = (uint8_t)(2 * i + e);
+    }
+  }
+  const uint64_t R = (1ull << 16) % q, Rinv = powmod_u64(R, q - 2, q);
+  uint64_t cf = R, ct = R;
+  for (int k = 0; k < BD::r.nrf; ++k) { cf = mulmod_u64(cf, Rinv, q); ct = mulmod_u64(ct, R, q); }
+  m.q = (int32_t)q;
+  m.qinv16 = tb.qinv16;
+  m.c_from = (int32_t)ntt_form(cf, q, 12);
+  m.c_to = (int32_t)ntt_form(ct, q, 12);
+  m.ok = true;
+  return m;
 }
 
 // gpv_ring.rs:172-178
