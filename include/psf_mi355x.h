@@ -439,7 +439,11 @@ psf_status psfp_wait_ticket(psfp_handle*, uint64_t ticket);
 /* PSF::f_a (mp_perturbation.rs:366-369): u[b] = A e[b] mod q; PSF_ERR_DOMAIN (u still written) if any
  * row fails check_domain */
 psf_status psfp_f_a(psfp_handle*, size_t B, const int64_t* e, uint64_t* u);
-/* PSF::check_domain (mp_perturbation.rs:396-402) for rows of length `len`; ok[b] = 0/1 */
+/* PSF::check_domain (mp_perturbation.rs:396-402) for rows of length `len`; ok[b] = 0/1.  Decided as the reference decides it, in exact arithmetic:
+ * ok[b] = (len == m and ||e_b||^2 <= s^2 m r^2) with s and r standing for the rationals those doubles denote (r = 1 for psfgpv_ / psfring_check_domain,
+ * gpv.rs:219-224 and gpv_ring.rs:274-283).  The host forms floor(s^2 m r^2) in multi-limb integers from the mantissas and exponents of s and r, the kernel
+ * sums the squares in 192 bits (no row of int64 wraps them, INT64_MIN included) and compares integers; nothing is rounded.  The same test is the d_ok of
+ * X_f_a_dev and the PSF_ERR_DOMAIN of X_f_a. */
 psf_status psfp_check_domain(psfp_handle*, size_t B, const int64_t* e, size_t len, uint8_t* ok);
 
 /* One job over `count` handles, one per GPU of the node, each holding the same key (psfp_trap_gen with the same seed, or psfp_load_key):

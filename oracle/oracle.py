@@ -396,6 +396,15 @@ class PSFPerturbation:
                                                          _p(v, C.c_uint64), _p(z, C.c_int64)))
         return z
 
+    def gadget_sample_trace(self, seed, index, v):
+        """the gadget walk of one preimage with every draw's (centre, width, coefficient): z, centre, width, coef (n k entries, index j k + i)"""
+        v = _u64(v).reshape(self.n)
+        z, coef = np.zeros(self.w, dtype=np.int64), np.zeros(self.w, dtype=np.int64)
+        cen, wid = np.zeros(self.w), np.zeros(self.w)
+        _check(lib().orc_randomized_nearest_plane_gadget_trace(self._h, C.c_uint64(seed), C.c_uint64(index), _p(v, C.c_uint64), _p(z, C.c_int64),
+                                                               _p(cen, C.c_double), _p(wid, C.c_double), _p(coef, C.c_int64)))
+        return z, cen, wid, coef
+
 
 def normals(seed, index, m):
     """d <- N(0,1)^m of preimage `index` (stream TAG_NORMAL)."""

@@ -690,7 +690,7 @@ static void gadget_tables(const orc_psfp* h, double* norm2, double* s2) {
  *   x = G^{-1}(v) (gadget_classical.rs:219-229); c = -x; for i = k-1..0 (per block j):
  *   c' = <c, b~_i>/||b~_i||^2 ; z_i <- D_{Z, s_G/||b~_i||, c'} ; c -= z_i b_i ; result z = x + sum z_i b_i = -c. */
 static int gadget_sample_one(const orc_psfp* h, const double* norm2, const double* s2, uint64_t seed,
-                             uint64_t index, const uint64_t* v, int64_t* z) {
+                             uint64_t index, const uint64_t* v, int64_t* z, double* tr_centre, double* tr_width, int64_t* tr_coef) {
   size_t n = h->gp.n, k = h->gp.k;
   int64_t* c = (int64_t*)malloc(k * sizeof(int64_t));
   for (size_t j = 0; j < n; ++j) {
@@ -702,6 +702,7 @@ static int gadget_sample_one(const orc_psfp* h, const double* norm2, const doubl
       for (size_t t = 0; t < k; ++t) dot = fma((double)c[t], h->Sk_gso[t * k + ii], dot);
       double c2 = dot / norm2[ii];
       int64_t zi = orc_sample_z(seed, ORC_TAG_GADGET, index, (uint32_t)(j * k + ii), c2, s2[ii]);
+      if (tr_centre) { tr_centre[j * k + ii] = c2; tr_width[j * k + ii] = s2[ii]; tr_coef[j * k + ii] = zi; }
       for (size_t t = 0; t < k; ++t) c[t] -= zi * h->Sk[t * k + ii];
     }
     for (size_t t = 0; t < k; ++t) z[j * k + t] = -c[t];
@@ -714,7 +715,20 @@ int orc_randomized_nearest_plane_gadget(const orc_psfp* h, uint64_t seed, uint64
   size_t k = h->gp.k;
   double* norm2 = (double*)malloc(2 * k * sizeof(double));
   gadget_tables(h, norm2, norm2 + k);
-  int rc = gadget_sample_one(h, norm2, norm2 + k, seed, index, v, z);
+  int rc = gadget_sample_one(h, norm2, norm2 + k, seed, index, v, z, NULL, NULL, NULL);
+  free(norm2);
+  return rc;
+}
+
+/* the same walk with what every draw saw: centre[j k + i] = c' and width[j k + i] = s_G / ||b~_i|| as passed to SampleZ, coef[j k + i] = the z_i drawn
+ * (n k entries each).  tests/test_oracle_gadget_centre_precision.py recomputes the centres in exact rationals. */
+int orc_randomized_nearest_plane_gadget_trace(const orc_psfp* h, uint64_t seed, uint64_t index, const uint64_t* v, int64_t* z,
+                                              double* centre, double* width, int64_t* coef) {
+  size_t k = h->gp.k;
+  if (!centre || !width || !coef) return ORC_ERR_PARAM;
+  double* norm2 = (double*)malloc(2 * k * sizeof(double));
+  gadget_tables(h, norm2, norm2 + k);
+  int rc = gadget_sample_one(h, norm2, norm2 + k, seed, index, v, z, centre, width, coef);
   free(norm2);
   return rc;
 }
@@ -956,7 +970,7 @@ int orc_psfp_samp_p(const orc_psfp* h, uint64_t seed, uint64_t first_index, size
       }
       v[i] = submod(u[bg * n + i] % q, red, q);
     }
-    int rc = gadget_sample_one(h, norm2, norm2 + k, seed, first_index + bg, v, zt);
+    int rc = gadget_sample_one(h, norm2, norm2 + k, seed, first_index + bg, v, zt, NULL, NULL, NULL);
     if (rc) { status = rc; }
     for (size_t c = 0; c < w; ++c) Z[c * GRP + b] = (int32_t)zt[c];
     free(v); free(zt);
@@ -1002,16 +1016,57 @@ int orc_psfp_samp_d(const orc_psfp* h, uint64_t seed, uint64_t first_index, size
   return cap_status(cap0, ORC_OK);
 }
 
-/* mp_perturbation.rs:396-402: column vector of length m with ||sigma||^2 <= s^2 m r^2 */
+/* floor(s^2 m r^2) as three 64-bit limbs (least significant first), every double taken as the rational it denotes: s = ms 2^es and
+ * r = mr 2^er with 53-bit integers ms, mr, so the bound is (ms^2 mr^2 m) 2^(2 es + 2 er) -- a product of at most 276 bits, shifted.  Saturates
+ * at 2^192 - 1, above every norm a row of int64 can have (each square is at most 2^126).  Nothing here rounds. */
+void orc_domain_bound_limbs(double s, double r, uint64_t m, uint64_t out[3]) {
+  out[0] = out[1] = out[2] = 0;
+  if (!(s > 0.0) || !(r > 0.0) || m == 0) return;
+  if (isinf(s) || isinf(r)) { out[0] = out[1] = out[2] = ~0ull; return; }
+  int es, er;
+  const uint64_t ms = (uint64_t)ldexp(frexp(s, &es), 53), mr = (uint64_t)ldexp(frexp(r, &er), 53);
+  const uint64_t f[5] = {ms, ms, mr, mr, m};
+  uint64_t P[6] = {1, 0, 0, 0, 0, 0};
+  for (int t = 0; t < 5; ++t) {
+    u128 carry = 0;
+    for (int i = 0; i < 5; ++i) { const u128 v = (u128)P[i] * f[t] + carry; P[i] = (uint64_t)v; carry = v >> 64; }
+  }
+  const long E = 2 * ((long)es - 53 + (long)er - 53);                /* bound = P 2^E */
+  int bits = 0;
+  for (int i = 4; i >= 0 && !bits; --i) if (P[i]) bits = 64 * i + 64 - __builtin_clzll(P[i]);
+  if (bits + E > 192) { out[0] = out[1] = out[2] = ~0ull; return; }
+  if (bits + E <= 0) return;
+  for (int j = 0; j < 3; ++j) {                                       /* limb j = bits [64 j - E, 64 j - E + 64) of P */
+    const long lo = 64 * (long)j - E;
+    for (int b = 0; b < 64; ++b) {
+      const long src = lo + b;
+      if (src >= 0 && src < 320 && ((P[src >> 6] >> (src & 63)) & 1)) out[j] |= 1ull << b;
+    }
+  }
+}
+
+/* ok = (||e||^2 <= floor(bound)) in integers: the norm in 192 bits (no wrap for any len), |v| in unsigned arithmetic */
+int orc_norm_within(const int64_t* e, size_t len, const uint64_t bound[3]) {
+  u128 lo = 0;
+  uint64_t hi = 0;
+  for (size_t i = 0; i < len; ++i) {
+    const uint64_t a = e[i] < 0 ? 0 - (uint64_t)e[i] : (uint64_t)e[i];
+    const u128 sq = (u128)a * a;
+    lo += sq;
+    if (lo < sq) ++hi;
+  }
+  const uint64_t n1 = (uint64_t)(lo >> 64), n0 = (uint64_t)lo;
+  if (hi != bound[2]) return hi < bound[2];
+  if (n1 != bound[1]) return n1 < bound[1];
+  return n0 <= bound[0];
+}
+
+/* mp_perturbation.rs:396-402: column vector of length m with ||sigma||^2 <= s^2 m r^2, compared as exact rationals */
 int orc_psfp_check_domain(const orc_psfp* h, size_t B, const int64_t* e, size_t len, uint8_t* ok) {
   size_t m = h->m;
-  double bound = ((h->s * h->s) * (double)m) * (h->r * h->r);
-  for (size_t b = 0; b < B; ++b) {
-    if (len != m) { ok[b] = 0; continue; }
-    u128 nn = 0;
-    for (size_t i = 0; i < m; ++i) { i128 v = e[b * len + i]; nn += (u128)(v * v); }
-    ok[b] = ((double)nn <= bound) ? 1 : 0;
-  }
+  uint64_t bound[3];
+  orc_domain_bound_limbs(h->s, h->r, m, bound);
+  for (size_t b = 0; b < B; ++b) ok[b] = (len == m && orc_norm_within(e + b * len, len, bound)) ? 1 : 0;
   return ORC_OK;
 }
 

@@ -126,8 +126,15 @@ int orc_psfp_samp_p_trace(const orc_psfp*, uint64_t seed, uint64_t index, const 
 int orc_psfp_samp_d(const orc_psfp*, uint64_t seed, uint64_t first_index, size_t B, int64_t* e); /* :264-267 */
 int orc_psfp_f_a(const orc_psfp*, size_t B, const int64_t* e, uint64_t* u);                      /* :366-369 */
 int orc_psfp_check_domain(const orc_psfp*, size_t B, const int64_t* e, size_t len, uint8_t* ok);  /* :396-402 */
+/* the exact test behind check_domain: floor(s^2 m r^2) in three 64-bit limbs (least significant first; each double is the rational it denotes;
+ * saturated at 2^192 - 1), and ||e||^2 <= that bound with the norm in 192 bits */
+void orc_domain_bound_limbs(double s, double r, uint64_t m, uint64_t out[3]);
+int orc_norm_within(const int64_t* e, size_t len, const uint64_t bound[3]);
 /* mp_perturbation.rs:173-191 for one target vector v (n) -> z (nk) */
 int orc_randomized_nearest_plane_gadget(const orc_psfp*, uint64_t seed, uint64_t index, const uint64_t* v, int64_t* z);
+/* the same walk, with the centre and the width every SampleZ call was given and the coefficient it returned (n k entries each, index j k + i) */
+int orc_randomized_nearest_plane_gadget_trace(const orc_psfp*, uint64_t seed, uint64_t index, const uint64_t* v, int64_t* z,
+                                              double* centre, double* width, int64_t* coef);
 
 int orc_num_threads(void);
 

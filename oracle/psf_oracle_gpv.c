@@ -407,16 +407,12 @@ int orc_gpv_samp_d(const void* hv, uint64_t seed, uint64_t first_index, size_t B
   return orc_sample_z_cap_hits() != cap0 ? ORC_ERR_SAMPLER : ORC_OK;
 }
 
-/* gpv.rs:219-224 */
+/* gpv.rs:219-224: ||e||^2 <= s^2 m as exact rationals (gpv_ring.rs:274-283 is the same test with m = n (k + 2)) */
 int orc_gpv_check_domain(const void* hv, size_t B, const int64_t* e, size_t len, uint8_t* ok) {
   const orc_gpv* h = (const orc_gpv*)hv;
-  const double bound = (h->s * h->s) * (double)h->m;
-  for (size_t b = 0; b < B; ++b) {
-    if (len != h->m) { ok[b] = 0; continue; }
-    u128 nn = 0;
-    for (size_t i = 0; i < len; ++i) { i128 v = e[b * len + i]; nn += (u128)(v * v); }
-    ok[b] = ((double)nn <= bound) ? 1 : 0;
-  }
+  uint64_t bound[3];
+  orc_domain_bound_limbs(h->s, 1.0, h->m, bound);
+  for (size_t b = 0; b < B; ++b) ok[b] = (len == h->m && orc_norm_within(e + b * len, len, bound)) ? 1 : 0;
   return ORC_OK;
 }
 

@@ -24,7 +24,28 @@ static void perturbation(uint64_t n, uint64_t q, double r, double s) {
   CHECK(orc_psfp_check_domain(h, B, e, m, ok) == 0 && ok[0] && ok[1] && ok[2]);
   CHECK(orc_psfp_samp_d(h, 3, 0, B, e) == 0);
   CHECK(orc_psfp_check_domain(h, B, e, m, ok) == 0 && ok[0] && ok[1] && ok[2]);
+  /* check_domain in exact integers: a row of norm 2^128 (four entries -2^63; a 128-bit sum wraps to 0) is outside */
+  for (size_t i = 0; i < B * m; ++i) e[i] = 0;
+  for (size_t i = 0; i < 4; ++i) e[i] = INT64_MIN;
+  CHECK(orc_psfp_check_domain(h, B, e, m, ok) == 0 && !ok[0] && ok[1] && ok[2]);
   free(u); free(u2); free(e);
+  orc_psfp_free(h);
+}
+
+/* n = 8, q = 128 (m = 121), r = 3, s = 24.98853731704157: s^2 m r^2 = 680000.99..., which ((s*s)*m)*(r*r) rounds to 680001.0; the reference compares
+ * exact rationals (mp_perturbation.rs:396-402), so a row of norm 680000 is inside and a row of norm 680001 = 824^2 + 32^2 + 1 is outside */
+static void on_the_bound(void) {
+  orc_gadget_params gp;
+  CHECK(orc_gadget_params_default(8, 128, &gp) == 0);
+  orc_psfp* h = orc_psfp_new(&gp, 3.0, 24.98853731704157);
+  const size_t m = gp.m_bar + gp.n * gp.k;
+  CHECK(h && m == 121);
+  int64_t* e = (int64_t*)calloc(2 * m, sizeof(int64_t));
+  uint8_t ok[2];
+  e[0] = 824; e[5] = -32;                      /* 680000 */
+  e[m] = -824; e[m + 7] = 32; e[2 * m - 1] = 1;  /* 680001 */
+  CHECK(orc_psfp_check_domain(h, 2, e, m, ok) == 0 && ok[0] && !ok[1]);
+  free(e);
   orc_psfp_free(h);
 }
 
@@ -70,6 +91,7 @@ int main(void) {
   perturbation(5, 32, 2.5, 25.0);
   perturbation(3, 125, 2.0, 40.0);
   perturbation(2, 1ull << 60, 2.0, 70.0);
+  on_the_bound();
   gpv(4, 23, 12.0);
   gpv(5, 256, 10.0);
   ring(8, 17);

@@ -49,6 +49,38 @@ inline bool gadget_too_short(uint64_t base, uint64_t k, uint64_t q) {
   return p < (u128)q;
 }
 
+// floor(s^2 m r^2), the bound of check_domain (mp_perturbation.rs:396-402; r = 1 for gpv.rs:219-224 and gpv_ring.rs:274-283), as three 64-bit limbs, least
+// significant first.  The reference compares exact rationals, so every double is taken as the rational it denotes: s = ms 2^es and r = mr 2^er with 53-bit
+// integers ms and mr, the bound is (ms^2 mr^2 m) 2^(2 es + 2 er) -- a product of at most 276 bits, then one shift.  Nothing rounds.  A norm is an integer, so
+// ||e||^2 <= s^2 m r^2 is ||e||^2 <= this floor.  Saturates at 2^192 - 1, above every norm a row of int64 can reach (k_check_domain sums squares <= 2^126 in
+// 192 bits).
+struct NormBound { uint64_t w[3]; };
+inline NormBound domain_bound_exact(double s, double r, uint64_t m) {
+  const NormBound zero = {{0, 0, 0}}, top = {{~0ull, ~0ull, ~0ull}};
+  if (!(s > 0.0) || !(r > 0.0) || m == 0) return zero;
+  if (std::isinf(s) || std::isinf(r)) return top;
+  int es, er;
+  const uint64_t ms = (uint64_t)std::ldexp(std::frexp(s, &es), 53), mr = (uint64_t)std::ldexp(std::frexp(r, &er), 53);
+  const uint64_t f[5] = {ms, ms, mr, mr, m};
+  uint64_t P[5] = {1, 0, 0, 0, 0};
+  for (uint64_t ft : f) {
+    u128 carry = 0;
+    for (uint64_t& limb : P) { const u128 v = (u128)limb * ft + carry; limb = (uint64_t)v; carry = v >> 64; }
+  }
+  const long E = 2 * ((long)es - 53 + (long)er - 53);                   // bound = P 2^E
+  long bits = 0;
+  for (int i = 4; i >= 0 && !bits; --i) if (P[i]) bits = 64 * i + 64 - __builtin_clzll(P[i]);
+  if (bits + E > 192) return top;
+  NormBound out = zero;
+  if (bits + E <= 0) return out;
+  for (int j = 0; j < 3; ++j)                                            // limb j = bits [64 j - E, 64 j - E + 64) of P
+    for (int b = 0; b < 64; ++b) {
+      const long src = 64 * (long)j - E + b;
+      if (src >= 0 && src < 320 && ((P[src >> 6] >> (src & 63)) & 1)) out.w[j] |= 1ull << b;
+    }
+  return out;
+}
+
 psf_status gadget_params_default(uint64_t n, uint64_t q, psf_gadget_params* out);
 psf_status gadget_params_ring_default(uint64_t n, uint64_t q, psf_gadget_params* out);
 

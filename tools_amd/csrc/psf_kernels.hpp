@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "psf_rng.hpp"
+#include "psf_host.hpp"
 
 namespace psf {
 
@@ -1856,34 +1857,42 @@ __global__ void k_samp_d(uint64_t seed, uint64_t first_index, size_t m, size_t B
   if (f) atomicOr(fail, 1);
 }
 
-// ok[b] = (||e_b||^2 <= bound), exact 128-bit norm (mp_perturbation.rs:396-402)
-__global__ __launch_bounds__(256) void k_check_domain(const int64_t* __restrict__ E, size_t len, size_t m, double bound,
+// ok[b] = (len == m and ||e_b||^2 <= bound) in integers (mp_perturbation.rs:396-402 compares exact rationals): bound = floor(s^2 m r^2) from
+// psf::domain_bound_exact, the norm in three 64-bit limbs -- a square is at most 2^126, so no len wraps them.  |v| is taken in unsigned arithmetic
+// (INT64_MIN has no int64 negation).
+__global__ __launch_bounds__(256) void k_check_domain(const int64_t* __restrict__ E, size_t len, size_t m, psf::NormBound bound,
                                                       uint8_t* __restrict__ ok) {
-  __shared__ uint64_t s_lo[256];
-  __shared__ uint64_t s_hi[256];
+  __shared__ uint64_t s_w[3][256];
   const size_t b = blockIdx.x;
-  uint64_t lo = 0, hi = 0;
+  uint64_t w0 = 0, w1 = 0, w2 = 0;
   for (size_t i = threadIdx.x; i < len; i += 256) {
     const int64_t v = E[b * len + i];
-    const uint64_t a = (uint64_t)(v < 0 ? -v : v);
-    const uint64_t pl = a * a, ph = __umul64hi(a, a);
-    const uint64_t nl = lo + pl;
-    hi += ph + (nl < lo ? 1 : 0);
-    lo = nl;
+    const uint64_t a = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    const uint64_t pl = a * a, ph = __umul64hi(a, a);                     // ph <= 2^62
+    w0 += pl;
+    const uint64_t t = ph + (w0 < pl ? 1 : 0);                            // no wrap: ph + 1 < 2^64
+    w1 += t;
+    w2 += w1 < t ? 1 : 0;
   }
-  s_lo[threadIdx.x] = lo; s_hi[threadIdx.x] = hi;
+  s_w[0][threadIdx.x] = w0; s_w[1][threadIdx.x] = w1; s_w[2][threadIdx.x] = w2;
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s) {
-      const uint64_t nl = s_lo[threadIdx.x] + s_lo[threadIdx.x + s];
-      s_hi[threadIdx.x] += s_hi[threadIdx.x + s] + (nl < s_lo[threadIdx.x] ? 1 : 0);
-      s_lo[threadIdx.x] = nl;
+      const uint64_t a0 = s_w[0][threadIdx.x], a1 = s_w[1][threadIdx.x];
+      const uint64_t b0 = s_w[0][threadIdx.x + s], b1 = s_w[1][threadIdx.x + s];
+      const uint64_t n0 = a0 + b0, c0 = n0 < a0 ? 1 : 0;
+      const uint64_t t1 = a1 + b1, n1 = t1 + c0;
+      const uint64_t c1 = (t1 < a1 ? 1 : 0) + (n1 < t1 ? 1 : 0);
+      s_w[0][threadIdx.x] = n0;
+      s_w[1][threadIdx.x] = n1;
+      s_w[2][threadIdx.x] += s_w[2][threadIdx.x + s] + c1;
     }
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    const double nn = (double)s_hi[0] * 18446744073709551616.0 + (double)s_lo[0];
-    ok[b] = (len == m && nn <= bound) ? 1 : 0;
+    const uint64_t n0 = s_w[0][0], n1 = s_w[1][0], n2 = s_w[2][0];
+    const bool within = n2 != bound.w[2] ? n2 < bound.w[2] : (n1 != bound.w[1] ? n1 < bound.w[1] : n0 <= bound.w[0]);
+    ok[b] = (len == m && within) ? 1 : 0;
   }
 }
 

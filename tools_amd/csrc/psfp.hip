@@ -59,6 +59,7 @@ struct psfp_handle {
   uint64_t q, two64, two31;
   bool wide;            // q >= 2^31: two 31-bit limbs
   bool has_key = false;      // A, R and sqrt(Sigma_2) installed
+  NormBound dom = {{0, 0, 0}};   // floor(s^2 m r^2): check_domain's bound in exact integers (domain_bound_exact), fixed by the parameters
   bool has_pub = false;      // A installed (f_a, check_domain, samp_d work; samp_p needs has_key)
   bool has_R = false;        // R installed (compute_sqrt_sigma_2 can complete the key; samp_p also needs has_pub)
   // key material
@@ -439,6 +440,7 @@ static psf_status psfp_init(psfp_handle* h, const psfp_params* prm) {
   const psf_gadget_params& gp = prm->gp;
   h->prm = *prm;
   h->n = gp.n; h->k = gp.k; h->mb = gp.m_bar; h->w = gp.n * gp.k; h->m = h->mb + h->w; h->q = gp.q;
+  h->dom = domain_bound_exact(prm->s, prm->r, h->m);
   h->two64 = (uint64_t)((((u128)1) << 64) % gp.q);
   h->two31 = (uint64_t)((1ull << 31) % gp.q);
   h->wide = gp.q >= (1ull << 31);
@@ -2008,9 +2010,7 @@ psf_status psfp_samp_d(psfp_handle* h, uint64_t seed, uint64_t first_index, size
   return rc;
 }
 
-static double domain_bound(const psfp_handle* h) {   // s^2 * m * r^2, mp_perturbation.rs:401
-  return ((h->prm.s * h->prm.s) * (double)h->m) * (h->prm.r * h->prm.r);
-}
+static NormBound domain_bound(const psfp_handle* h) { return h->dom; }   // floor(s^2 * m * r^2), mp_perturbation.rs:401 (r = 1 under PSFGPV / PSFGPVRing)
 
 psf_status psfp_check_domain(psfp_handle* h, size_t B, const int64_t* e, size_t len, uint8_t* ok) {
   if (!h || (B && (!e || !ok))) return PSF_ERR_PARAM;
