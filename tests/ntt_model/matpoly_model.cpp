@@ -1,5 +1,5 @@
 // CPU model of the accumulation step of the R_q matrix product (k_matpoly_mul): the templates of tools_amd/csrc/psf_ntt_core.hpp -- forward,
-// leafmul, acc_add / acc_tick / acc_close, inverse, finish -- instantiated over a 64-lane array, for EVERY wave shape of psf_ntt.hip's for_shape.
+// leafmul, acc_add / acc_tick / acc_close, inverse, finish -- instantiated over a 64-lane array, for EVERY wave shape of for_shape (psf_ntt_shapes.hpp).
 // Test infrastructure (built and run by tests/test_matpoly_model.py).  Each shape runs
 //   * worst-case operands: a = q - 1 everywhere, b = +-(q - 1) by coefficient parity, the SAME summand `inner` = 4099 times (every leaf product of
 //     one sign, the fastest growth of the accumulators), past the fold interval of the 16-bit form; and
@@ -232,7 +232,7 @@ int main() {
   int bad = 0;
   for (int ex = 1; ex >= 0; --ex) {
 #define PSF_SHAPE(LN, LDV, QBV) bad += run_case<LN, LDV, QBV>(ex);
-    // the wave shapes of psf_ntt.hip's for_shape
+    // the wave shapes of for_shape (psf_ntt_shapes.hpp)
     PSF_SHAPE(7, 0, 12) PSF_SHAPE(8, 1, 12) PSF_SHAPE(9, 2, 12)
     PSF_SHAPE(7, 0, 14) PSF_SHAPE(7, 1, 14) PSF_SHAPE(8, 0, 14) PSF_SHAPE(8, 1, 14) PSF_SHAPE(8, 2, 14) PSF_SHAPE(9, 0, 14) PSF_SHAPE(9, 1, 14) PSF_SHAPE(9, 2, 14)
     PSF_SHAPE(10, 0, 14) PSF_SHAPE(10, 1, 14) PSF_SHAPE(10, 2, 14)

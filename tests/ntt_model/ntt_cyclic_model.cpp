@@ -5,7 +5,7 @@
 //     of the device tests;
 //   * the pair product (forward, leafmul, inverse, finish) on the 16 shapes of ntt_model.cpp, random and extreme operands, against a schoolbook
 //     product mod X^n - 1;
-//   * the accumulation step of the matrix product (acc_add / acc_tick / acc_close) on every wave shape of psf_ntt.hip's for_shape, worst-case
+//   * the accumulation step of the matrix product (acc_add / acc_tick / acc_close) on every wave shape of for_shape (psf_ntt_shapes.hpp), worst-case
 //     summands added 4099 times (past the fold interval of the 16-bit form) and 37 random ones.
 // Every 24-bit multiply and Montgomery step asserts its operand ranges: the bound analysis assumes only centred constants |z| <= q/2.
 #include <array>
@@ -330,7 +330,7 @@ int main() {
   }
   for (int mode = 2; mode >= 0; --mode) {
 #define PSF_SHAPE(LN, LDV, QBV) bad += run_acc<LN, LDV, QBV>(mode);
-    // the wave shapes of psf_ntt.hip's for_shape
+    // the wave shapes of for_shape (psf_ntt_shapes.hpp)
     PSF_SHAPE(7, 0, 12) PSF_SHAPE(8, 1, 12) PSF_SHAPE(9, 2, 12)
     PSF_SHAPE(7, 0, 14) PSF_SHAPE(7, 1, 14) PSF_SHAPE(8, 0, 14) PSF_SHAPE(8, 1, 14) PSF_SHAPE(8, 2, 14) PSF_SHAPE(9, 0, 14) PSF_SHAPE(9, 1, 14) PSF_SHAPE(9, 2, 14)
     PSF_SHAPE(10, 0, 14) PSF_SHAPE(10, 1, 14) PSF_SHAPE(10, 2, 14)

@@ -331,3 +331,85 @@ def test_kpke_round_trip(T, torch):
     for name, d, want in (("t", dt, t), ("u", du, u), ("v", dv, v), ("w", dw, w)):
         assert (_np(d, 16).reshape(want.shape) == want).all(), name
     assert (_np(dgot, 16).reshape(bits.shape) == bits.astype(np.uint64)).all()
+
+
+# ---- the schoolbook matrix kernels above the default LDS limit --------------------------------------------------------------------------------------------
+BIG = dict(n=8192, q=1 << 30, rows=1, inner=2, cols=2, seed=20260731)
+
+
+def _big_case():
+    """A dense residues; every polynomial of B with at most 8 non-zero signed coefficients, degrees 0 and n - 1 among them; E any int64"""
+    n, q, rows, inner, cols = (BIG[x] for x in ("n", "q", "rows", "inner", "cols"))
+    rng = np.random.default_rng(BIG["seed"])
+    A = rng.integers(0, q, size=(rows, inner, n), dtype=np.uint64)
+    B = np.zeros((inner, cols, n), dtype=np.int64)
+    for k in range(inner):
+        for j in range(cols):
+            deg = np.concatenate(([0, n - 1], rng.choice(np.arange(1, n - 1), size=6, replace=False)))
+            mag = rng.integers(1, q, size=deg.size, dtype=np.int64)
+            B[k, j, deg] = mag * rng.choice(np.array([-1, 1], dtype=np.int64), size=deg.size)
+    B[0, 0, 0], B[0, 0, n - 1], B[1, 1, 0], B[1, 1, n - 1] = q - 1, -(q - 1), -(q - 1), q - 1     # both signs at both ends
+    E = rng.integers(np.iinfo(np.int64).min, np.iinfo(np.int64).max, size=(rows, cols, n), dtype=np.int64, endpoint=True)
+    return A, B, E
+
+
+def _sparse_product(A, B, q, wrap):
+    """A B mod (X^n - wrap, q) by one shifted add per non-zero coefficient of B.  Exact in int64: a term a * |b| is below 2^60 and is reduced mod q
+    before it is added to a sum that is kept in [0, q)."""
+    rows, inner, n = A.shape
+    cols = B.shape[1]
+    assert q <= 1 << 30 and int(A.max()) < q and int(np.abs(B).max()) < q
+    out = np.zeros((rows, cols, n), dtype=np.int64)
+    for i in range(rows):
+        for j in range(cols):
+            for k in range(inner):
+                for d in np.flatnonzero(B[k, j]).tolist():
+                    b = int(B[k, j, d])
+                    t = np.roll(((A[i, k] * np.uint64(abs(b))) % np.uint64(q)).astype(np.int64), d)      # X^d a: coefficient c - d at c, the last d wrapped
+                    t[:d] *= wrap
+                    out[i, j] = np.mod(out[i, j] + (t if b > 0 else -t), q)
+    return out
+
+
+@pytest.fixture(scope="module")
+def big_case():
+    A, B, E = _big_case()
+    q = BIG["q"]
+    return A, B, E, {ring: _sparse_product(A, B, q, wrap) for ring, wrap in (("negacyclic", -1), ("cyclic", 1))}
+
+
+def test_shifted_add_reference_equals_the_model_at_a_small_size():
+    """the reference of the next test against the big-integer models, where those are quick (n = 64, the same modulus and kind of operands)"""
+    q, n = BIG["q"], 64
+    rng = np.random.default_rng(5)
+    A = rng.integers(0, q, size=(2, 2, n), dtype=np.uint64)
+    B = np.zeros((2, 2, n), dtype=np.int64)
+    for k in range(2):
+        for j in range(2):
+            deg = np.concatenate(([0, n - 1], rng.choice(np.arange(1, n - 1), size=6, replace=False)))
+            B[k, j, deg] = rng.integers(1, q, size=8, dtype=np.int64) * rng.choice(np.array([-1, 1], dtype=np.int64), size=8)
+    assert (_sparse_product(A, B, q, -1).astype(np.uint64) == M.matpoly_mul(A, B, q)).all()
+    assert (_sparse_product(A, B, q, 1).astype(np.uint64) == MC.matpoly_mul(A, B, q)).all()
+
+
+def test_schoolbook_matrix_kernels_above_the_default_lds_limit(T, big_case):
+    """n = 8192 at q = 2^30 (no NTT; 128-bit accumulation): the four schoolbook matrix kernels run with 128 KiB of dynamic LDS, above the 64 KiB a
+    kernel gets by default.  Host forms, bit for bit; each entry twice -- the first call raises the kernel's limit, the second finds it raised."""
+    A, B, E, P = big_case
+    q = BIG["q"]
+    want = {
+        "matpoly_mul": P["negacyclic"],
+        "matpoly_mul_cyclic": P["cyclic"],
+        "matpoly_mul_add": np.mod(np.mod(E, q) - P["negacyclic"], q),
+        "matpoly_mul_add_cyclic": np.mod(np.mod(E, q) + P["cyclic"], q),
+    }
+    calls = {
+        "matpoly_mul": lambda: T.rq.matpoly_mul(A, B, q),
+        "matpoly_mul_cyclic": lambda: T.rq.matpoly_mul_cyclic(A, B, q),
+        "matpoly_mul_add": lambda: T.rq.matpoly_mul_add(A, B, E, q, sign=-1),
+        "matpoly_mul_add_cyclic": lambda: T.rq.matpoly_mul_add_cyclic(A, B, E, q, sign=1),
+    }
+    for name, call in calls.items():
+        for attempt in (1, 2):
+            got = call()
+            assert got.dtype == np.uint64 and (got == want[name].astype(np.uint64)).all(), (name, attempt)

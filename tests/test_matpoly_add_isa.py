@@ -1,7 +1,7 @@
 """The fused R_q matrix-product kernels compiled for gfx950 here (no GPU needed): k_matpoly_fma (psf_ntt_kernels.hpp, instantiated in psf_ntt_fma.hip)
-has one instantiation per wave shape of for_shape (psf_ntt.hip), I/O width (16 bits only in the 16-bit Montgomery forms) and form of A (polynomials,
-images in global memory, images in LDS), exactly like k_matpoly_mul; k_matpoly_fma_negacyclic / k_matpoly_fma_cyclic (psf_gpv_kernels.hpp, built in
-psfp.hip) are the schoolbook routes.  None of them has scratch, spills or calls.  Resource checks only.
+has one instantiation per wave shape of for_shape (psf_ntt_shapes.hpp), I/O width (16 bits only in the 16-bit Montgomery forms) and form of A (polynomials,
+images in global memory, images in LDS), exactly like k_matpoly_mul; k_matpoly_fma_negacyclic / k_matpoly_fma_cyclic (psf_rq_kernels.hpp, built in
+psf_rq.hip) are the schoolbook routes.  None of them has scratch, spills or calls.  Resource checks only.
 
 The epilogue of k_matpoly_fma reads E, sign and out from the kernel-argument segment through MatFmaKernArgs (psf_ntt_kernels.hpp): the offsets of that
 struct are compared here with the offsets the code object records for every instantiation."""
@@ -33,8 +33,8 @@ def fma_asm(tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
-def psfp_asm(tmp_path_factory):
-    return _asm(tmp_path_factory, "psfp.hip")
+def rq_asm(tmp_path_factory):
+    return _asm(tmp_path_factory, "psf_rq.hip")
 
 
 def kernels(asm, pattern):
@@ -67,7 +67,7 @@ def check_clean(asm, ks, pattern):
 
 
 def wave_shapes():
-    src = open(os.path.join(CSRC, "psf_ntt.hip")).read()
+    src = open(os.path.join(CSRC, "psf_ntt_shapes.hpp")).read()
     body = src[src.index("template <class F> bool for_shape"):]
     body = body[:body.index("#undef PSF_SHAPE")]
     return [tuple(int(v) for v in m) for m in re.findall(r"PSF_SHAPE\((\d+), (\d+), (\d+)\)", body)]
@@ -106,7 +106,7 @@ def test_wave_kernels_have_no_scratch_spills_or_calls(fma_asm):
 
 
 @pytest.mark.parametrize("pattern", [r"_ZN3psf24k_matpoly_fma_negacyclic", r"_ZN3psf20k_matpoly_fma_cyclic"])
-def test_schoolbook_kernels_are_clean(psfp_asm, pattern):
-    ks = kernels(psfp_asm, pattern)
+def test_schoolbook_kernels_are_clean(rq_asm, pattern):
+    ks = kernels(rq_asm, pattern)
     assert len(ks) == 1, sorted(ks)
-    check_clean(psfp_asm, ks, pattern)
+    check_clean(rq_asm, ks, pattern)

@@ -1,6 +1,6 @@
 """The R_q matrix-product kernels compiled for gfx950 here (no GPU needed): k_matpoly_mul (psf_ntt_kernels.hpp) has one instantiation per wave shape of
-psf_ntt.hip's for_shape, I/O width (16 bits only in the 16-bit Montgomery forms) and form of A (polynomials, images in global memory, images in LDS);
-k_matpoly_negacyclic (psf_gpv_kernels.hpp, built in psfp.hip) is the schoolbook route.  None of them has scratch, spills or calls."""
+for_shape (psf_ntt_shapes.hpp), I/O width (16 bits only in the 16-bit Montgomery forms) and form of A (polynomials, images in global memory, images in LDS);
+k_matpoly_negacyclic (psf_rq_kernels.hpp, built in psf_rq.hip) is the schoolbook route.  None of them has scratch, spills or calls."""
 import os
 import re
 import shutil
@@ -28,8 +28,8 @@ def ntt_asm(tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
-def psfp_asm(tmp_path_factory):
-    return _asm(tmp_path_factory, "psfp.hip")
+def rq_asm(tmp_path_factory):
+    return _asm(tmp_path_factory, "psf_rq.hip")
 
 
 def kernels(asm, pattern):
@@ -58,7 +58,7 @@ def check_clean(asm, ks, pattern):
 
 
 def wave_shapes():
-    src = open(os.path.join(CSRC, "psf_ntt.hip")).read()
+    src = open(os.path.join(CSRC, "psf_ntt_shapes.hpp")).read()
     body = src[src.index("template <class F> bool for_shape"):]
     body = body[:body.index("#undef PSF_SHAPE")]
     return [tuple(int(v) for v in m) for m in re.findall(r"PSF_SHAPE\((\d+), (\d+), (\d+)\)", body)]
@@ -77,8 +77,8 @@ def test_one_instantiation_per_wave_shape_io_width_and_form(ntt_asm):
     assert sorted(got) == sorted(want), (len(got), len(want))
 
 
-def test_no_scratch_spills_or_calls(ntt_asm, psfp_asm):
+def test_no_scratch_spills_or_calls(ntt_asm, rq_asm):
     check_clean(ntt_asm, kernels(ntt_asm, r"_ZN3psf3ntt13k_matpoly_mul"), r"_ZN3psf3ntt13k_matpoly_mul")
-    ks = kernels(psfp_asm, r"_ZN3psf20k_matpoly_negacyclic")
+    ks = kernels(rq_asm, r"_ZN3psf20k_matpoly_negacyclic")
     assert len(ks) == 1, sorted(ks)
-    check_clean(psfp_asm, ks, r"_ZN3psf20k_matpoly_negacyclic")
+    check_clean(rq_asm, ks, r"_ZN3psf20k_matpoly_negacyclic")

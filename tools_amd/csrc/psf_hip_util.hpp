@@ -1,10 +1,14 @@
 // psf_hip_util.hpp -- what the host side of every HIP translation unit shares: the error macro, the device check, the compute-unit count, an
-// owning device buffer for allocations that live for one call, and the dispatch of a runtime integer to a template argument.
+// owning device buffer for allocations that live for one call, the dynamic-LDS limit of a kernel, and the dispatch of a runtime integer to a
+// template argument.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdio>
 #include <mutex>
 #include <type_traits>
+#include <utility>
+#include <vector>
 #include "../../include/psf_mi355x.h"
 
 #define HIP_TRY(expr)                                                                  \
@@ -35,6 +39,19 @@ inline psf_status use_device(int device) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return PSF_ERR_HIP;
   HIP_TRY(hipSetDevice(device));
+  return PSF_OK;
+}
+
+// a launch of `kern` with `smem` bytes of dynamic LDS: above the default 64 KiB the kernel's limit is raised to the 160 KiB of a gfx950 workgroup, once per
+// process, kernel and device (`device` is current)
+inline psf_status raise_lds_once(const void* kern, int device, size_t smem) {
+  if (smem <= 64 * 1024) return PSF_OK;
+  static std::mutex mu; static std::vector<std::pair<const void*, int>> raised;
+  std::lock_guard<std::mutex> lk(mu);
+  if (std::find(raised.begin(), raised.end(), std::make_pair(kern, device)) == raised.end()) {
+    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    raised.emplace_back(kern, device);
+  }
   return PSF_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include "psf_rng.hpp"
 #include "psf_host.hpp"
+#include "psf_acc128.hpp"
 
 namespace psf {
 
@@ -718,30 +719,6 @@ __global__ __launch_bounds__(256) void k_perturb_round_tab(uint64_t seed, uint64
 // a is split into 31-bit limbs; each 32-term tile is summed in int64 (|a_limb * p| < 2^31 * 2^25) and folded
 // into a 128-bit running total, so no intermediate ever wraps for any q < 2^62.
 enum ZqMode { ZQ_SYNDROME = 0, ZQ_FA = 1, ZQ_TRAPDOOR = 2 };
-
-struct Acc128 { uint64_t lo; int64_t hi; };
-__device__ inline void acc128_add(Acc128& t, int64_t v) {
-  const uint64_t nl = t.lo + (uint64_t)v;
-  t.hi += (v >> 63) + (nl < t.lo ? 1 : 0);
-  t.lo = nl;
-}
-// (hi * 2^64 + lo) mod q for |hi| small; two64 = 2^64 mod q
-__device__ inline uint64_t acc128_mod(Acc128 t, uint64_t q, uint64_t two64) {
-  uint64_t r = t.lo % q;
-  int64_t h = t.hi;
-  const bool neg = h < 0;
-  uint64_t hm = (uint64_t)(neg ? -h : h);
-  // hm * two64 mod q by double-and-add (hm < 2^16 in every use)
-  uint64_t term = 0, base = two64;
-  while (hm) {
-    if (hm & 1) { term += base; if (term >= q) term -= q; }
-    base += base; if (base >= q) base -= q;
-    hm >>= 1;
-  }
-  if (neg) { r = r >= term ? r - term : r + q - term; }
-  else { r += term; if (r >= q) r -= q; }
-  return r;
-}
 
 template <typename PT, bool WIDE>
 __global__ __launch_bounds__(256) void k_zq_matmul(int mode, const uint64_t* __restrict__ Amat, size_t lda, size_t a_off,

@@ -1,38 +1,18 @@
 // psf_ntt.hip -- NTT products over R_q = Z_q[X]/(X^n + 1) and Z_q[X]/(X^n - 1): plan cache, shape dispatch and launches (psf_ntt_api.hpp).
 // PolynomialRingZq multiplication under gadget_ring.rs:78 and gpv_ring.rs:243-247; the kernels are in psf_ntt_kernels.hpp / psf_ntt_core.hpp.  They read
 // the ring from the table of zetas alone (NttDev::zetas), so the cyclic ring takes the same instantiations with the table of make_ntt_plan_cyclic.
-// The fused products C = E +- op(A) B (k_matpoly_fma) are launched from psf_ntt_fma.hip, through the plan access of psf_ntt_api.hpp.
+// The list of wave shapes is psf_ntt_shapes.hpp; the launch skeleton of every wave kernel and the launch of the matrix products are psf_ntt_launch.hpp,
+// which psf_ntt_fma.hip instantiates a second time for the fused products C = E +- op(A) B (k_matpoly_fma), through the plan access of psf_ntt_api.hpp.
 #include <cstdlib>
 #include <map>
-#include <set>
 #include <mutex>
 #include <tuple>
-#include "psf_hip_util.hpp"
 #include "psf_host.hpp"
-#include "psf_ntt_api.hpp"
-#include "psf_ntt_kernels.hpp"
+#include "psf_ntt_launch.hpp"
 
 using namespace psf;
 using namespace psf::ntt;
 
-namespace {
-
-// the shapes that have a wave kernel (make_ntt_tables decides logn, ld, qb).  The one list of them: psf_ntt_fma.hip includes this file with
-// PSF_NTT_SHAPES_ONLY defined and gets this function alone, so both units instantiate their kernels over the same shapes.
-template <class F> bool for_shape(int logn, int ld, int qb, F&& f) {
-#define PSF_SHAPE(LN, LDV, QBV) if (logn == LN && ld == LDV && qb == QBV) { f(ic<LN>{}, ic<LDV>{}, ic<QBV>{}); return true; }
-  PSF_SHAPE(7, 0, 12) PSF_SHAPE(8, 1, 12) PSF_SHAPE(9, 2, 12)
-  PSF_SHAPE(7, 0, 14) PSF_SHAPE(7, 1, 14) PSF_SHAPE(8, 0, 14) PSF_SHAPE(8, 1, 14) PSF_SHAPE(8, 2, 14) PSF_SHAPE(9, 0, 14) PSF_SHAPE(9, 1, 14) PSF_SHAPE(9, 2, 14)
-  PSF_SHAPE(10, 0, 14) PSF_SHAPE(10, 1, 14) PSF_SHAPE(10, 2, 14)
-  PSF_SHAPE(7, 0, 0) PSF_SHAPE(7, 1, 0) PSF_SHAPE(8, 0, 0) PSF_SHAPE(8, 1, 0) PSF_SHAPE(8, 2, 0) PSF_SHAPE(9, 0, 0) PSF_SHAPE(9, 1, 0) PSF_SHAPE(9, 2, 0)
-  PSF_SHAPE(10, 0, 0) PSF_SHAPE(10, 1, 0) PSF_SHAPE(10, 2, 0)
-#undef PSF_SHAPE
-  return false;
-}
-
-}  // namespace
-
-#ifndef PSF_NTT_SHAPES_ONLY
 namespace {
 
 // ---- generic form: any power-of-two n <= 8192, any plan (leaf degree d = n >> L of any size), 32-bit Montgomery arithmetic, data in LDS ------------
@@ -135,6 +115,9 @@ NttDev dev_args(const Plan* P, int e, int e_fa) {
   a.zetas = P->d_zetas;
   return a;
 }
+NttWavePlan wave_of(const Plan* P) {                                     // a route-2 plan as the launches see it
+  return NttWavePlan{P, P->tb.logn, P->tb.ld, P->tb.qb, P->tb.q, (size_t)((P->tb.qb == 12 ? 4u : 2u) << P->pl.L)};
+}
 unsigned wave_grid(size_t count) {                                       // four products per workgroup at a time, at most 8 workgroups per CU
   static const size_t cap = [] { const char* e = psf_exp_env("PSF_NTT_GRID"); const long v = e ? std::atol(e) : 0; return (size_t)(v > 0 ? v : 2048); }();
   const size_t g = (count + 3) / 4;
@@ -143,6 +126,7 @@ unsigned wave_grid(size_t count) {                                       // four
 
 }  // namespace
 
+
 namespace psf {
 
 psf_status ntt_wave_plan(int device, uint64_t q, size_t n, NttRing ring, int io_bits, NttWavePlan* out) {
@@ -150,8 +134,7 @@ psf_status ntt_wave_plan(int device, uint64_t q, size_t n, NttRing ring, int io_
   Plan* P = plan_for(device, q, n, &rc, ring);
   if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
   if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
-  out->plan = P; out->logn = P->tb.logn; out->ld = P->tb.ld; out->qb = P->tb.qb; out->q = P->tb.q;
-  out->zeta_words = (P->tb.qb == 12 ? 4u : 2u) << P->pl.L;
+  *out = wave_of(P);
   return PSF_OK;
 }
 void ntt_dev_args(const NttWavePlan& w, int e, int e_fa, ntt::NttDev* out) { *out = dev_args(static_cast<const Plan*>(w.plan), e, e_fa); }
@@ -177,129 +160,64 @@ psf_status ntt_polymul_dev(int device, uint64_t q, size_t n, size_t count, const
     const NttDev a = dev_args(P, 1, 1);
     const size_t smem = ((2u << P->pl.L) + 3 * n) * sizeof(uint32_t);
     if (smem > 160 * 1024) return PSF_ERR_UNSUPPORTED;                   // gfx950: 160 KiB of LDS per workgroup (n = 8192 with a fully splitting prime needs 160 KiB exactly)
-    if (smem > 64 * 1024) {                                              // above the default limit the kernel's attribute is raised once per process and device
-      static std::mutex mu; static std::set<int> raised;
-      std::lock_guard<std::mutex> lk(mu);
-      if (!raised.count(device)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_polymul_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised.insert(device);
-      }
-    }
+    const psf_status rl = raise_lds_once(reinterpret_cast<const void*>(k_ntt_polymul_lds), device, smem);
+    if (rl != PSF_OK) return rl;
     hipLaunchKernelGGL(k_ntt_polymul_lds, dim3((unsigned)(count > 4096 ? 4096 : count)), dim3(256), smem, st, a, (uint32_t)n, P->pl.L, P->pl.d,
                        (const uint64_t*)d_a, (const int64_t*)d_b, (uint64_t*)d_out, count);
     HIP_TRY(hipGetLastError());
     return PSF_OK;
   }
   if (io_bits == 16 && P->tb.qb == 0) return PSF_ERR_UNSUPPORTED;
-  const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
-    constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
-    const NttDev a = dev_args(P, Kern<LN, LDV, QBV>::E, Kern<LN, LDV, QBV>::E + 1);
-    if constexpr (QBV != 0) {
-      if (io_bits == 16) { hipLaunchKernelGGL((k_ntt_polymul<LN, LDV, QBV, 16>), dim3(wave_grid(count)), dim3(256), 0, st, a, d_a, d_b, d_out, count); return; }
-    }
-    hipLaunchKernelGGL((k_ntt_polymul<LN, LDV, QBV, 64>), dim3(wave_grid(count)), dim3(256), 0, st, a, d_a, d_b, d_out, count);
+  const NttWavePlan w = wave_of(P);
+  return ntt_launch_wave(w, io_bits, [&](auto ln, auto ldv, auto qbv, auto io) {
+    hipLaunchKernelGGL((k_ntt_polymul<ln(), ldv(), qbv(), io()>), dim3(wave_grid(count)), dim3(256), 0, st, ntt_product_args<ln(), ldv(), qbv()>(w), d_a, d_b, d_out, count);
   });
-  if (!ok) return PSF_ERR_UNSUPPORTED;
-  HIP_TRY(hipGetLastError());
-  return PSF_OK;
 }
 
 psf_status ntt_forward_dev(int device, uint64_t q, size_t n, size_t count, const void* d_a, int io_bits, uint32_t* d_hat, hipStream_t st, NttRing ring) {
   if (io_bits != 16 && io_bits != 64) return PSF_ERR_PARAM;
   if (count && (!d_a || !d_hat)) return PSF_ERR_PARAM;
-  psf_status rc;
-  Plan* P = plan_for(device, q, n, &rc, ring);
-  if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
-  if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
+  NttWavePlan w;
+  const psf_status rc = ntt_wave_plan(device, q, n, ring, io_bits, &w);
+  if (rc != PSF_OK) return rc;
   if (count == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(device));
-  const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
-    constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
-    const NttDev a = dev_args(P, 1, 1);
-    if constexpr (QBV != 0) {
-      if (io_bits == 16) { hipLaunchKernelGGL((k_ntt_forward<LN, LDV, QBV, 16, false>), dim3(wave_grid(count)), dim3(256), 0, st, a, d_a, d_hat, count); return; }
-    }
-    hipLaunchKernelGGL((k_ntt_forward<LN, LDV, QBV, 64, false>), dim3(wave_grid(count)), dim3(256), 0, st, a, d_a, d_hat, count);
+  return ntt_launch_wave(w, io_bits, [&](auto ln, auto ldv, auto qbv, auto io) {
+    hipLaunchKernelGGL((k_ntt_forward<ln(), ldv(), qbv(), io(), false>), dim3(wave_grid(count)), dim3(256), 0, st, dev_args(static_cast<const Plan*>(w.plan), 1, 1), d_a, d_hat, count);
   });
-  if (!ok) return PSF_ERR_UNSUPPORTED;                      // route 2 without an instantiated shape: nothing was launched
-  HIP_TRY(hipGetLastError());
-  return PSF_OK;
 }
 
 psf_status ntt_mul_hat_dev(int device, uint64_t q, size_t n, size_t count, const uint32_t* d_hat, size_t hat_stride, const void* d_b, void* d_out, int io_bits, hipStream_t st,
                            NttRing ring) {
   if (io_bits != 16 && io_bits != 64) return PSF_ERR_PARAM;
   if (count && (!d_hat || !d_b || !d_out)) return PSF_ERR_PARAM;
-  psf_status rc;
-  Plan* P = plan_for(device, q, n, &rc, ring);
-  if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
-  if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
+  NttWavePlan w;
+  const psf_status rc = ntt_wave_plan(device, q, n, ring, io_bits, &w);
+  if (rc != PSF_OK) return rc;
   if (count == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(device));
-  const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
-    constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
-    const NttDev a = dev_args(P, Kern<LN, LDV, QBV>::E, Kern<LN, LDV, QBV>::E + 1);
-    if constexpr (QBV != 0) {
-      if (io_bits == 16) { hipLaunchKernelGGL((k_ntt_mul_hat<LN, LDV, QBV, 16>), dim3(wave_grid(count)), dim3(256), 0, st, a, d_hat, hat_stride, d_b, d_out, count); return; }
-    }
-    hipLaunchKernelGGL((k_ntt_mul_hat<LN, LDV, QBV, 64>), dim3(wave_grid(count)), dim3(256), 0, st, a, d_hat, hat_stride, d_b, d_out, count);
+  return ntt_launch_wave(w, io_bits, [&](auto ln, auto ldv, auto qbv, auto io) {
+    hipLaunchKernelGGL((k_ntt_mul_hat<ln(), ldv(), qbv(), io()>), dim3(wave_grid(count)), dim3(256), 0, st, ntt_product_args<ln(), ldv(), qbv()>(w), d_hat, hat_stride, d_b, d_out, count);
   });
-  if (!ok) return PSF_ERR_UNSUPPORTED;                      // route 2 without an instantiated shape: nothing was launched
-  HIP_TRY(hipGetLastError());
-  return PSF_OK;
 }
 
 psf_status ntt_ring_fa_dev(int device, uint64_t q, size_t n, uint32_t K, const uint32_t* d_hat, const int64_t* d_sigma, uint64_t* d_u, size_t B, hipStream_t st) {
   if (B && (!d_hat || !d_sigma || !d_u)) return PSF_ERR_PARAM;
-  psf_status rc;
-  Plan* P = plan_for(device, q, n, &rc);
-  if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
-  const size_t smem = (((P->tb.qb == 12 ? 4u : 2u) << P->pl.L) + (size_t)K * n) * sizeof(uint32_t);
-  if (P->route != 2 || smem > 64 * 1024) return PSF_ERR_UNSUPPORTED;
+  NttWavePlan w;
+  const psf_status rc = ntt_wave_plan(device, q, n, kNegacyclic, 64, &w);
+  if (rc != PSF_OK) return rc;
+  const size_t smem = (w.zeta_words + (size_t)K * n) * sizeof(uint32_t);
+  if (smem > 64 * 1024) return PSF_ERR_UNSUPPORTED;
   if (B == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(device));
-  const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
-    constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
-    const NttDev a = dev_args(P, Kern<LN, LDV, QBV>::E, Kern<LN, LDV, QBV>::E + 1);
-    hipLaunchKernelGGL((k_ring_fa<LN, LDV, QBV>), dim3(wave_grid(B)), dim3(256), smem, st, a, d_hat, K, d_sigma, d_u, B);
+  return ntt_launch_wave(w, 64, [&](auto ln, auto ldv, auto qbv, auto) {     // 64-bit words only
+    hipLaunchKernelGGL((k_ring_fa<ln(), ldv(), qbv()>), dim3(wave_grid(B)), dim3(256), smem, st, ntt_product_args<ln(), ldv(), qbv()>(w), d_hat, K, d_sigma, d_u, B);
   });
-  if (!ok) return PSF_ERR_UNSUPPORTED;                      // route 2 without an instantiated shape: nothing was launched
-  HIP_TRY(hipGetLastError());
-  return PSF_OK;
 }
-
 
 psf_status ntt_matmul_dev(int device, uint64_t q, size_t n, const NttMatShape& s, const void* d_a, size_t a_stride, bool hat, const void* d_b, void* d_c,
                           int io_bits, hipStream_t st, NttRing ring) {
-  psf_status rc;
-  Plan* P = plan_for(device, q, n, &rc, ring);
-  if (!P) return rc != PSF_OK ? rc : PSF_ERR_UNSUPPORTED;
-  if (P->route != 2 || (io_bits == 16 && P->tb.qb == 0)) return PSF_ERR_UNSUPPORTED;
-  const size_t zn = (P->tb.qb == 12 ? 4u : 2u) << P->pl.L;
-  const bool stage = hat && a_stride == 0 && (zn + s.rows * s.inner * n) * sizeof(uint32_t) <= 64 * 1024;   // one A for all: its images in LDS
-  if (s.count == 0) return PSF_OK;
-  HIP_TRY(hipSetDevice(device));
-  const bool ok = for_shape(P->tb.logn, P->tb.ld, P->tb.qb, [&](auto ln, auto ldv, auto qbv) {
-    constexpr int LN = decltype(ln)::value, LDV = decltype(ldv)::value, QBV = decltype(qbv)::value;
-    const NttDev a = dev_args(P, Kern<LN, LDV, QBV>::E, Kern<LN, LDV, QBV>::E + 1);
-    const MatArgs m = make_mat_args(s.count, s.rows, s.inner, s.cols, s.trans_a, a_stride, MatTile<LN>::RT, P->tb.q);
-    const size_t smem = (zn + (stage ? s.rows * s.inner * n : 0)) * sizeof(uint32_t);
-    const dim3 grid(wave_grid(m.items));
-    auto go = [&](auto io) {
-      constexpr int IO = decltype(io)::value;
-      if (!hat) hipLaunchKernelGGL((k_matpoly_mul<LN, LDV, QBV, IO, 0>), grid, dim3(256), smem, st, a, m, d_a, d_b, d_c);
-      else if (!stage) hipLaunchKernelGGL((k_matpoly_mul<LN, LDV, QBV, IO, 1>), grid, dim3(256), smem, st, a, m, d_a, d_b, d_c);
-      else hipLaunchKernelGGL((k_matpoly_mul<LN, LDV, QBV, IO, 2>), grid, dim3(256), smem, st, a, m, d_a, d_b, d_c);
-    };
-    if constexpr (QBV != 0) {
-      if (io_bits == 16) { go(ic<16>{}); return; }
-    }
-    go(ic<64>{});
-  });
-  if (!ok) return PSF_ERR_UNSUPPORTED;                      // route 2 without an instantiated shape: nothing was launched
-  HIP_TRY(hipGetLastError());
-  return PSF_OK;
+  return ntt_matpoly_launch<false>(device, q, n, s, d_a, a_stride, hat, d_b, nullptr, 0, d_c, io_bits, st, ring);
 }
 
 }  // namespace psf
-#endif  // PSF_NTT_SHAPES_ONLY

@@ -1,5 +1,6 @@
-// psf_ntt_api.hpp -- what psf_ntt.hip (the translation unit of the NTT kernels) offers the rest of the library.  Device pointers, the caller's
-// stream, no allocation per call: the tables of a (device, q, n) are built at first use and kept.
+// psf_ntt_api.hpp -- what psf_ntt.hip and psf_ntt_fma.hip (the translation units of the NTT kernels) offer the rest of the library: psf_rq.hip (the
+// C ABI of the R_q products) and the ring PSF of psfgpv_impl.hpp.  Device pointers, the caller's stream, no allocation per call: the tables of a
+// (device, q, n) are built at first use and kept.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -43,7 +44,7 @@ psf_status ntt_matfma_dev(int device, uint64_t q, size_t n, const NttMatShape& s
 namespace ntt { struct NttDev; }
 struct NttWavePlan {
   const void* plan;          // the cache entry (owned by psf_ntt.hip)
-  int logn, ld, qb;          // the wave shape (for_shape)
+  int logn, ld, qb;          // the wave shape (for_shape, psf_ntt_shapes.hpp)
   uint32_t q;
   size_t zeta_words;         // words of LDS the zetas of this shape take in front of anything else
 };
