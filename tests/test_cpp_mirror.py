@@ -63,6 +63,21 @@ def test_stream_split_and_grid_under_address_and_ub_sanitizers():
     assert r.returncode == 0 and "STREAM_HOST_OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
 
 
+def test_hostpipe_host_arithmetic_under_address_and_ub_sanitizers():
+    """tools_amd/csrc/psf_hostpipe_host.hpp (no HIP in it): widen_rows at every alignment and length 0..40 with an exactly sized source and a guard word
+    behind the destination, the slice cuts of a host call, the chunk geometry with the slice a chunk waits for, and the four pieces of a nearest-plane
+    batch, swept by tests/cpp/hostpipe_host_check.cpp.  widen_rows uses clang's vector extensions and streaming stores, so the program is built with the
+    ROCm toolchain's clang++ (host code only); nothing of it is loaded into Python."""
+    src = os.path.join(ROOT, "tests", "cpp", "hostpipe_host_check.cpp")
+    exe = os.path.join(ROOT, "tests", "cpp", "hostpipe_host_check")
+    clangxx = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
+    b = subprocess.run([clangxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src],
+                       capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "HOSTPIPE_HOST_OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
 def test_oracle_under_address_and_ub_sanitizers():
     """The checker itself: oracle/*.c built with gcc -fsanitize=address,undefined and run through one small flow per scheme
     (tests/cpp/oracle_sanitize.c)."""

@@ -454,3 +454,83 @@ def test_two_ranks_rehearse_the_multi_gpu_path_on_the_gpus_there_are(config):
     assert "self-spawned" in d["launcher"] and "oversubscribed" in d and "gloo gather" in d["config"]["parallelism"]
     per = {"bench64": 4096, "c2": 1024}[config]
     assert d["config"]["global_batch"] == 2 * per
+
+
+def test_a_handle_carries_nothing_from_one_call_into_the_next(oracle):
+    """What a samp_p pass is told by its caller (keep the failure words, the whole batch for a stage export, the staging of the targets, the column-block
+    count of its rows) travels as arguments of that pass: after a stage export, a sliced host call or a many-call, the next call on the same handle H gives
+    the rows and the plan of a fresh handle F that holds the same key and has only ever made device-pointer calls."""
+    import numpy as np
+    import torch
+    import tools_amd as T
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream().cuda_stream
+
+    def dev_call(psf, u, seed, first_index=0):
+        ud = torch.from_numpy(u.astype(np.int64)).to(dev)
+        ed = torch.empty((u.shape[0], psf.m), dtype=torch.int64, device=dev)
+        psf.samp_p_dev(ud.data_ptr(), ed.data_ptr(), u.shape[0], seed=seed, first_index=first_index, stream=st)
+        torch.cuda.synchronize()
+        assert psf.last_status() == 0
+        return ed.cpu().numpy()
+
+    # one-launch eligible: the stage export must not leave "whole batch" behind
+    n, q, r, s = 8, 128, 3.0, 30.0
+    H = T.PSFPerturbation(T.GadgetParameters.init_default(n, q), r, s)
+    A, (R, Lp, _) = H.trap_gen(3)
+    orc = oracle.PSFPerturbation(oracle.gadget_params_default(n, q), r, s)
+    orc.load_key(A, R, Lp)
+    u = oracle.uniform_targets(21, 5, n, q)
+    stages = H.samp_p_stages(u, seed=8)
+    plan_stages = H.last_plan()
+    e = H.samp_p(u, seed=8)
+    assert (e == stages["e"]).all()
+    assert plan_stages["one_launch"] == 0 and H.last_plan()["one_launch"] == 1
+    assert (e == orc.samp_p(8, u)).all()
+    H.close()
+
+    # a sliced host call (2600 rows of m = 505: slices of 1576 and 1024 rows), then device-pointer calls and a many-call
+    n, q, r, s = 24, 2**10, 4.0, 80.0
+    H = T.PSFPerturbation(T.GadgetParameters.init_default(n, q), r, s)
+    A, (R, Lp, _) = H.trap_gen(5)
+    assert H.m == 505
+    F = T.PSFPerturbation(T.GadgetParameters.init_default(n, q), r, s)
+    F.load_key(A, R, Lp)
+    B = 2600
+    u = oracle.uniform_targets(31, B, n, q)
+    sliced = H.samp_p(u, seed=60, first_index=7)
+    rows = dev_call(H, u, 61, 9)
+    assert H.last_plan() == H.query_plan(B)
+    assert (rows == dev_call(F, u, 61, 9)).all()
+    count, Bm = 3, 64
+    um = oracle.uniform_targets(32, count * Bm, n, q)
+    ud = torch.from_numpy(um.astype(np.int64)).to(dev)
+    ed = torch.empty((count * Bm, H.m), dtype=torch.int64, device=dev)
+    H.samp_p_dev_many(ud.data_ptr(), ed.data_ptr(), Bm, seeds=[70, 71, 72], first_indices=[0, 100, 200], stream=st)
+    after = dev_call(H, um[:Bm], 73, 300)
+    assert H.last_status() == 0
+    many = ed.cpu().numpy()
+    for i in range(count):
+        assert (many[i * Bm:(i + 1) * Bm] == dev_call(F, um[i * Bm:(i + 1) * Bm], 70 + i, 100 * i)).all(), i
+    assert (after == dev_call(F, um[:Bm], 73, 300)).all()
+    orc = oracle.PSFPerturbation(oracle.gadget_params_default(n, q), r, s)
+    orc.load_key(A, R, Lp)
+    assert (sliced[:64] == orc.samp_p(60, u[:64], first_index=7)).all()
+    assert (sliced == dev_call(F, u, 60, 7)).all()
+    H.close()
+    F.close()
+
+    # nearest plane: the batch form, the small form and the device-pointer call decode the same flag words
+    n, q, s = 16, 257, 60.0
+    H = T.PSFGPV(T.GadgetParameters.init_default(n, q), s)
+    A, (Bt, Gt) = H.trap_gen(4)
+    F = T.PSFGPV(T.GadgetParameters.init_default(n, q), s)
+    F.load_key(A, Bt, Gt)
+    u = oracle.uniform_targets(41, 1200, n, q)
+    for Bc, seed, host in ((1200, 90, True), (3, 91, True), (1200, 92, False)):
+        got = H.samp_p(u[:Bc], seed=seed, first_index=5) if host else dev_call(H, u[:Bc], seed, 5)
+        assert (got == dev_call(F, u[:Bc], seed, 5)).all(), (Bc, seed)
+        assert H.nearest_plane_form()[:3] == F.nearest_plane_form()[:3], (Bc, seed)           # (form, G, blocks; the fourth is a count of contended walks)
+        assert H.nearest_plane_stats()[1] == F.nearest_plane_stats()[1], (Bc, seed)           # recombined in 64-bit integers?
+    H.close()
+    F.close()

@@ -1,4 +1,4 @@
-// Measurement harness (not product code): the host-side widening of a C3 batch of int32 rows into int64 rows (psfp.hip, widen_rows) -- ordinary stores against
+// Measurement harness (not product code): the host-side widening of a C3 batch of int32 rows into int64 rows (psf_hostpipe_host.hpp, widen_rows) -- ordinary stores against
 // streaming stores, N threads over 16 MiB chunks.   clang++ -O3 -std=c++17 -pthread tools/probe_widen.cpp -o tools/bin/probe_widen ; tools/bin/probe_widen [threads]
 #include <cstdint>
 #include <cstring>

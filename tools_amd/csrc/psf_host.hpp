@@ -12,7 +12,7 @@
 // branches behind it fold away and the kernels that lost their A/B but are still compared (k_np_walk2, k_np_walk<2> / k_np_walk_solo<2>, the per-pair k_np_combine8) are not
 // compiled.  `make exp` builds libpsf_mi355x_exp.so with -DPSF_EXPERIMENTS: the same sources with every PSF_* switch alive --
 // what the form-comparison tests and the A/B scripts under tools/ load through PSF_LIB.  A switch a USER needs is a field of the params structs or, for
-// the one host-side resource knob (PSF_HOST_WORKERS), read and validated in psfp.hip.
+// the one host-side resource knob (PSF_HOST_WORKERS), read and validated in psf_hostpipe.hpp.
 #ifdef PSF_EXPERIMENTS
 inline const char* psf_exp_env(const char* name) { return std::getenv(name); }
 constexpr bool psf_experiments_build = true;

@@ -758,18 +758,25 @@ psf_status psfgpv_samp_p_dev_many(psfgpv_handle* g, size_t count, const uint64_t
   return PSF_OK;
 }
 
+// The status of a call from its 1 + 8 flag words -- [0] the inner handle's failure word, [1 ..] the walk's: [1 + 0] and [1 + 4] a sampler failure of the first /
+// second pass, [1 + 3] / [1 + 7] the generic recombination of the last pass (kept for psfgpv_get_nearest_plane_form unless the call failed in the inner handle)
+static psf_status gpv_flags_status(psfgpv_handle* g, const int* fl) {
+  if (fl[0]) return PSF_ERR_SAMPLER;
+  g->last_generic = g->basis_generic || fl[1 + (g->two_pass ? 7 : 3)] != 0;
+  return (fl[1 + 0] || fl[1 + 4]) ? PSF_ERR_SAMPLER : PSF_OK;
+}
+
 psf_status psfgpv_last_status(psfgpv_handle* g) {
   if (!g) return PSF_ERR_PARAM;
   psf_status rc = psfp_last_status(g->base);              // synchronises the stream of the last call (behind both lanes after a many-call)
   if (rc != PSF_OK) return rc;
-  int fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int fl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};                // ([0]: the inner handle's word has just been answered for)
   for (int l = 0; l < g->last_lanes; ++l) {
     int f[8];
     HIP_TRY(hipMemcpy(f, g->ln[l].dFlags, sizeof(f), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 8; ++i) fl[i] |= f[i];
+    for (int i = 0; i < 8; ++i) fl[1 + i] |= f[i];
   }
-  g->last_generic = g->basis_generic || fl[g->two_pass ? 7 : 3] != 0;
-  return (fl[0] || fl[4]) ? PSF_ERR_SAMPLER : PSF_OK;
+  return gpv_flags_status(g, fl);
 }
 
 psf_status psfgpv_samp_p(psfgpv_handle* g, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* u, int64_t* e) {
@@ -777,18 +784,14 @@ psf_status psfgpv_samp_p(psfgpv_handle* g, uint64_t seed, uint64_t first_index, 
   if (!g->has_key) return PSF_ERR_NO_KEY;
   if (B == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(g->base->prm.device));
+  psfp_handle* h = g->base;
+  int fl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (B * (g->n + g->m) * 8 <= SIO_MAX_BYTES && !psf_exp_env("PSF_HOST_STRAIGHT")) {
     // a small call (the reference's call is one preimage): cached device buffers, u / e / flags through one pinned buffer, one synchronisation
-    psfp_handle* h = g->base;
-    if (B * g->n > h->sio_du_cap) { hipFree(h->sio_du); h->sio_du = nullptr; h->sio_du_cap = 0; HIP_TRY(hipMalloc(&h->sio_du, B * g->n * sizeof(uint64_t))); h->sio_du_cap = B * g->n; }
-    if (B * g->m > h->sio_de_cap) { hipFree(h->sio_de); h->sio_de = nullptr; h->sio_de_cap = 0; HIP_TRY(hipMalloc(&h->sio_de, B * g->m * sizeof(int64_t))); h->sio_de_cap = B * g->m; }
-    int fl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    psf_status rc = sio_call(h, B * g->n, B * g->m, u, e, h->sio_du, h->sio_de, h->dFail, g->ln[0].dFlags, 8, fl,
-                             [&]() { return psfgpv_samp_p_dev(g, seed, first_index, B, h->sio_du, h->sio_de, nullptr); });
-    if (rc != PSF_OK) return rc;
-    if (fl[0]) return PSF_ERR_SAMPLER;
-    g->last_generic = g->basis_generic || fl[1 + (g->two_pass ? 7 : 3)] != 0;
-    return (fl[1 + 0] || fl[1 + 4]) ? PSF_ERR_SAMPLER : PSF_OK;
+    psf_status rc = sio_dev_rows(h->hp, B * g->n, B * g->m);
+    if (rc == PSF_OK) rc = sio_call(h->hp, B * g->n, B * g->m, u, e, h->hp.sio_du, h->hp.sio_de, h->dFail, g->ln[0].dFlags, 8, fl,
+                                    [&]() { return psfgpv_samp_p_dev(g, seed, first_index, B, h->hp.sio_du, h->hp.sio_de, nullptr); });
+    return rc != PSF_OK ? rc : gpv_flags_status(g, fl);
   }
   if (psf_exp_env("PSF_HOST_STRAIGHT")) {                      // the form of rounds 1-3 (comparison arm of the tests)
     DevBuf du, de;
@@ -800,66 +803,10 @@ psf_status psfgpv_samp_p(psfgpv_handle* g, uint64_t seed, uint64_t first_index, 
     if (de.download(e, B * g->m * sizeof(int64_t)) != hipSuccess && rcs == PSF_OK) rcs = PSF_ERR_HIP;
     return rcs;
   }
-  // A batch: cached device buffers (no hipMalloc / hipFree per call), u through the pinned buffer, the rows narrowed to int32 on the device (every entry of a preimage
-  // fits by far; k_narrow_rows raises a flag otherwise and the int64 rows are copied as before), ONE copy into pinned memory, widened into e by four threads with
-  // streaming stores.  The straight form (two pageable copies around two allocations) took 9.75 ms around 4.34 ms of kernels at C2.
-  psfp_handle* h = g->base;
-  const size_t nu = B * g->n, ne = B * g->m;
-  if (nu > h->sio_du_cap) { hipFree(h->sio_du); h->sio_du = nullptr; h->sio_du_cap = 0; HIP_TRY(hipMalloc(&h->sio_du, nu * sizeof(uint64_t))); h->sio_du_cap = nu; }
-  if (ne > h->sio_de_cap) { hipFree(h->sio_de); h->sio_de = nullptr; h->sio_de_cap = 0; HIP_TRY(hipMalloc(&h->sio_de, ne * sizeof(int64_t))); h->sio_de_cap = ne; }
-  if (ne > h->sio_d32_cap) { hipFree(h->sio_d32); h->sio_d32 = nullptr; h->sio_d32_cap = 0; HIP_TRY(hipMalloc(&h->sio_d32, ne * sizeof(int32_t) + 2 * sizeof(int))); h->sio_d32_cap = ne; }
-  const size_t ub = round_up(nu * 8, 64), eb = round_up(ne * 4, 64);
-  psf_status rc = sio_ensure(h, ub + eb + 64);
-  if (rc != PSF_OK) return rc;
-  uint64_t* hu = reinterpret_cast<uint64_t*>(h->sio_pin);
-  int32_t* he = reinterpret_cast<int32_t*>(h->sio_pin + ub);
-  int* hf = reinterpret_cast<int*>(h->sio_pin + ub + eb);
-  int* d_ovf = reinterpret_cast<int*>(h->sio_d32 + ne);                    // overflow word of the narrowing, behind the rows
-  std::memcpy(hu, u, nu * 8);
-  hipLaunchKernelGGL(k_copy_words, dim3(sio_grid(nu)), dim3(256), 0, nullptr, hu, h->sio_du, nu);
-  HIP_TRY(hipMemsetAsync(d_ovf, 0, 2 * sizeof(int), nullptr));
-  rc = psfgpv_samp_p_dev(g, seed, first_index, B, h->sio_du, h->sio_de, nullptr);
-  if (rc != PSF_OK) { hipStreamSynchronize(nullptr); return rc; }
-  hipLaunchKernelGGL(k_narrow_rows, dim3(grid_for(ne / 2 + 1, 256, 256 * 16)), dim3(256), 0, nullptr, h->sio_de, h->sio_d32, ne, d_ovf);
-  // flags first (with the overflow word of the narrowing), then the rows in NT pieces, an event behind each: thread i widens piece i as soon as it has landed,
-  // while the later pieces are still crossing PCIe
-  hipLaunchKernelGGL(k_sio_flags, dim3(1), dim3(64), 0, nullptr, h->dFail, g->ln[0].dFlags, 8, hf);
-  HIP_TRY(hipMemcpyAsync(hf + 12, d_ovf, sizeof(int), hipMemcpyDeviceToHost, nullptr));
-  constexpr int NT = 4;
-  if (!h->sio_ev[0]) for (auto& ev : h->sio_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(h->sio_ev[NT], nullptr));                       // flags and overflow word are in pinned memory
-  const size_t per = round_up((ne + NT - 1) / NT, 16);
-  for (int i = 0; i < NT; ++i) {
-    const size_t b0 = (size_t)i * per, cnt = b0 >= ne ? 0 : (ne - b0 < per ? ne - b0 : per);
-    if (cnt) HIP_TRY(hipMemcpyAsync(he + b0, h->sio_d32 + b0, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipEventRecord(h->sio_ev[i], nullptr));
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventSynchronize(h->sio_ev[NT]));
-  if (hf[12]) {                                                            // an entry beyond 32 bits: the int64 rows, as before
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    HIP_TRY(hipMemcpy(e, h->sio_de, ne * sizeof(int64_t), hipMemcpyDeviceToHost));
-  } else {
-    std::thread th[NT];
-    std::atomic<int> bad{0};
-    const int device = h->prm.device;
-    auto piece = [&, device](int i, bool set_dev) {
-      const size_t b0 = (size_t)i * per, cnt = b0 >= ne ? 0 : (ne - b0 < per ? ne - b0 : per);
-      if (set_dev && hipSetDevice(device) != hipSuccess) { bad = 1; return; }
-      if (hipEventSynchronize(h->sio_ev[i]) != hipSuccess) { bad = 1; return; }
-      if (cnt) widen_rows(e + b0, he + b0, cnt);
-    };
-    int started = 0;
-    try {
-      for (; started < NT; ++started) th[started] = std::thread(piece, started, true);
-    } catch (...) { }
-    for (int i = started; i < NT; ++i) piece(i, false);                   // (no thread to be had: this one does the rest)
-    for (int i = 0; i < started; ++i) th[i].join();
-    if (bad) return PSF_ERR_HIP;
-  }
-  if (hf[0]) return PSF_ERR_SAMPLER;
-  g->last_generic = g->basis_generic || hf[1 + (g->two_pass ? 7 : 3)] != 0;
-  return (hf[1 + 0] || hf[1 + 4]) ? PSF_ERR_SAMPLER : PSF_OK;
+  // a batch: int32 rows in pieces through the pinned buffer, threaded widening (sio_batch)
+  const psf_status rc = sio_batch(h->hp, h->prm.device, B * g->n, B * g->m, u, e, h->dFail, g->ln[0].dFlags, 8, fl,
+                                  [&](uint64_t* d_u, int64_t* d_e) { return psfgpv_samp_p_dev(g, seed, first_index, B, d_u, d_e, nullptr); });
+  return rc != PSF_OK ? rc : gpv_flags_status(g, fl);
 }
 
 // gpv.rs:152-161 on host buffers without waiting (the machinery of psfp_samp_p_async on the inner handle: int32 narrowing, per-slot pinned rings, chunk transfers by the
@@ -877,9 +824,12 @@ psf_status psfgpv_samp_p_async(psfgpv_handle* g, uint64_t seed, uint64_t first_i
     const psf_status rb = ensure_np_batch(g, g->ln[0], B);
     if (rb != PSF_OK) return rb;
   }
-  return hp_async(h, B, u, e, false, false, g->ln[0].dFlags, [&](size_t off, size_t cnt, const uint64_t* d_u, int64_t* d_e, hipStream_t cs) -> psf_status {
+  const psf_status rc = hp_async(h->hp, host_call(h, B, g->ln[0].dFlags, false, false, true), B, u, e, [&]() { return host_resize(h, B); },
+                                 [&](size_t off, size_t cnt, const uint64_t* d_u, int64_t* d_e, hipStream_t cs, const HostStage*) -> psf_status {
     return gpv_samp_p_enqueue(g, seed, first_index + off, cnt, d_u, d_e, cs);
   });
+  if (rc == PSF_OK) h->last_stream = h->hp.compute;
+  return rc;
 }
 psf_status psfgpv_wait(psfgpv_handle* g) {
   if (!g) return PSF_ERR_PARAM;

@@ -19,7 +19,7 @@
 #include "psf_np_kernels.hpp"
 #include "psf_chol_kernels.hpp"
 #include "psf_gemm_kernels.hpp"
-#include "psf_sdma.hpp"
+#include "psf_hostpipe.hpp"
 #include "psf_ntt_api.hpp"
 
 // PSF_KEYGEN_TIMING=1: wall time of the phases of key generation on stderr (each mark drains the device first; off, a mark is one branch)
@@ -45,7 +45,6 @@ static inline unsigned grid_for(size_t total, unsigned block = 256, unsigned cap
   if (g < 1) g = 1;
   return (unsigned)(g > cap ? cap : g);
 }
-static inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // Rule of the handle (include/psf_mi355x.h, "Asynchronous calls"): an entry point that rewrites key material or reuses the handle's per-batch buffers first waits
 // for the asynchronous samp_p calls in flight (psfp_wait) and returns their status if one failed -- they run on a non-blocking stream and would otherwise read a
 // half-replaced key or share dP / dX / dV / the failure words with the new call.
@@ -92,7 +91,7 @@ struct psfp_handle {
   SampleZParams szR, szSR;
   uint32_t* dSzTab = nullptr; uint32_t szF = 0;      // table screen of the rounding sampler (psf_rng.hpp, k_perturb_round_tab); szF = 0: none (wide words, or the table would not fit)
   // batch work buffers
-  size_t Bcap = 0, ld = 0, nbj = 0;
+  size_t Bcap = 0, ld = 0;
   double* dDt = nullptr; double* dX = nullptr; int32_t* dP = nullptr; uint64_t* dV = nullptr;
   int8_t* dZlo = nullptr; int8_t* dZhi = nullptr; size_t mb_pad = 0;
   int8_t* dP8 = nullptr;                      // three digit planes of P, [K_pad/16][ld][16] each
@@ -102,51 +101,7 @@ struct psfp_handle {
   int32_t* dPf = nullptr; int8_t* dP8f = nullptr;   // scratch of f_a (kept apart from the samp_p intermediates)
   uint64_t* dPart = nullptr; int zq_split_cap = 1;   // per-split residues of the int8-MFMA Z_q product
   bool gadget_queue = true;   // task-queue gadget sampler (PSF_GADGET_QUEUE=0: lock-step kernel)
-  bool keep_fail = false;     // sliced host path: the failure flags accumulate over the slices of one call
-  // host path: the targets are first read by the syndrome stage, ~50 ms into a C3 batch -- this runs (once) on the calling thread right before that stage is
-  // enqueued, i.e. while the product already executes: staging and upload of u cost the call nothing
-  std::function<psf_status()> before_u;
-  // Host-pointer calls (psfp_samp_p / psfp_samp_p_async): rows are narrowed to int32 on the device, cross PCIe in chunks into pinned buffers and are
-  // widened into the caller's int64 rows by worker threads, while the compute stream already runs the next slice / the next call.
-  struct HostPipe {
-    static constexpr int NW = 8;                // at most this many worker threads per call (each: its own pinned chunk buffers, copies + widening of chunks c = w mod nw)
-    int nw = 4;                                 // workers in use (PSF_HOST_WORKERS)
-    int32_t* dE32[2] = {nullptr, nullptr};      // device: narrowed rows of the call in flight, two calls deep
-    size_t cap_entries[2] = {0, 0};             // entries dE32[slot] holds
-    bool slot_ready[2] = {false, false};        // the slot's flags, events, pinned chunk buffers and signals exist
-    bool common_ready = false;                  // streams, overflow word, transport
-    int32_t* hbuf[2][NW][2] = {};               // pinned chunk buffers [call slot][worker][double buffer]: two calls in flight never share one
-    hipEvent_t evC[2][NW][2] = {};              // chunk landed in its pinned buffer
-    size_t chunk_entries = 0;
-    hipEvent_t evSlice[2][4] = {};              // slice j of call slot s has been narrowed (compute stream)
-    int* hFlags[2] = {nullptr, nullptr};        // pinned: [0] sampler failure, [1] unused, [2] int32 overflow of a row entry
-    int* dOvf = nullptr;                        // device: overflow flag of the narrowing kernel
-    uint64_t* hU[2] = {nullptr, nullptr};       // pinned staging of the targets (a copy from pageable memory would block the caller behind the stream)
-    uint64_t* dU2[2] = {nullptr, nullptr};      // device copy of the targets per call in flight (filled by k_copy_words at the head of the call)
-    size_t u_cap[2] = {0, 0};
-    std::vector<std::thread> workers[2];
-    bool busy[2] = {false, false};
-    std::atomic<int> status[2] = {{0}, {0}};     // psf_status of the call in each slot (written by its workers)
-    size_t next = 0;                            // slot of the next asynchronous call
-    uint64_t seq = 0;                           // ticket of the next asynchronous call (0, 1, 2, ... since the handle was created)
-    uint64_t slot_seq[2] = {0, 0};              // ticket of the call in each slot
-    struct Done { uint64_t seq; int status; bool used; } done[8] = {};      // the last joined calls and their statuses (psfp_wait_ticket)
-    bool slice_tail = false;                    // set by psfp_samp_p around its own asynchronous call: cut a short last slice (single-call latency)
-    int copy_mode = 1;                          // how a chunk crosses PCIe: 1 = SDMA engine through the HSA runtime (psf_sdma.hpp), 0 = hipMemcpyAsync (PSF_HOST_COPY)
-    psf::SdmaCopy sdma;
-    hsa_signal_t sigC[2][NW][2] = {};           // mode 1: chunk landed in its pinned buffer
-    hsa_signal_t sigU = {};                     // mode 1: the call's targets have reached the device
-    hipStream_t copy = nullptr;                 // D2H stream (high priority)
-    hipStream_t compute = nullptr;              // stream of the asynchronous calls' kernels (normal priority)
-  } hp;
-  // small host-pointer calls (one preimage is the reference's call): u, e and the flags travel through ONE pinned buffer by kernels in stream order, one
-  // synchronisation per call -- the straight form (hipMemcpy in, flags out twice, hipMemcpy out: five blocking runtime calls) cost ~70 us around 47 us of kernels
-  std::thread hp_warm;        // hp_prewarm's worker; joined by whoever touches the host-pointer machinery next
-  uint8_t* sio_pin = nullptr; size_t sio_cap = 0;
-  uint64_t* sio_du = nullptr; int64_t* sio_de = nullptr; size_t sio_du_cap = 0, sio_de_cap = 0;      // device side for handles without their own (PSFGPV / ring)
-  int32_t* sio_d32 = nullptr; size_t sio_d32_cap = 0;         // narrowed rows of a PSFGPV / ring batch on their way to the host
-  hipEvent_t sio_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // pieces 0..3 of such a batch have landed; [4]: its flags have
-  bool no_slice = false;      // stage export wants the intermediates of the whole batch
+  HostPipe hp;                // host-pointer calls (psfp_samp_p / psfp_samp_p_async and their PSFGPV / ring forms): psf_hostpipe.hpp
   uint32_t normals_ncf = 0;   // layout of dDt after the last samp_p: 0 = chunk stream, else the compact stream with this many column fragments
   hipStream_t last_stream = nullptr;
   hipStream_t side = nullptr; hipEvent_t evSide = nullptr;      // psfp_trap_gen: A is computed on this low-priority stream beside the factorisation of Sigma_2
@@ -154,7 +109,6 @@ struct psfp_handle {
   bool timing = false;
   std::vector<TimingSlot> slots;
   // psfp_samp_p_multi: this handle's window inside the last call (host clock, ms since the call began)
-  const std::chrono::steady_clock::time_point* multi_t0 = nullptr;
   double multi_launched_ms = -1.0, multi_done_ms = -1.0;
   int last_plan[PSFP_PLAN_FIELDS] = {0}; bool has_last_plan = false;      // the forms of the last samp_p pass that ran (psfp_get_last_plan)
 };
@@ -236,15 +190,11 @@ static int zq_split_cap_for(const psfp_handle* h, size_t ld) {
 }
 
 static psf_status ensure_batch(psfp_handle* h, size_t B) {
-  if (B <= h->Bcap) {
-    h->nbj = round_up(B, TR_BN) / TR_BN;
-    return PSF_OK;
-  }
+  if (B <= h->Bcap) return PSF_OK;
   HIP_TRY(hipDeviceSynchronize());
   free_batch(h);
   const size_t ld = round_up(B, TR_BN);
   h->ld = ld;
-  h->nbj = ld / TR_BN;
   if (!(h->prm.flags & PSFP_FLAG_NO_PERTURB)) {
     HIP_TRY(hipMalloc(&h->dDt, (ld / TR_BN * h->nkb * TR_CHUNK + TS_SLACK_DOUBLES) * sizeof(double)));   // slack: k_trmm_stream reads past the diagonal
     HIP_TRY(hipMalloc(&h->dX, h->M_pad * ld * sizeof(double)));
@@ -543,26 +493,21 @@ static psf_status psfp_init(psfp_handle* h, const psfp_params* prm) {
   return PSF_OK;
 }
 
-static void hp_release(psfp_handle* h);
-static psf_status hp_ensure(psfp_handle* h, int slot, size_t entries, size_t u_words, bool from_prewarm = false);
 // A key whose batches will cross PCIe (m >= 8192: a preimage is >= 64 KiB) gets the batch-independent part of the host-pointer machinery -- streams, the DMA path,
 // one slot's pinned rings -- when the key is installed, next to a factorisation that takes a quarter of a second, instead of inside the first samp_p call
 // (PSF_HOST_PREWARM=0: on first use, as for small keys).
 static void hp_prewarm(psfp_handle* h) {
   if (h->m < 8192) return;
   if (const char* env = psf_exp_env("PSF_HOST_PREWARM")) if (std::atoi(env) == 0) return;
-  if (h->hp_warm.joinable()) h->hp_warm.join();
+  if (h->hp.hp_warm.joinable()) h->hp.hp_warm.join();
   try {
-    h->hp_warm = std::thread([h]() { if (hipSetDevice(h->prm.device) == hipSuccess) (void)hp_ensure(h, 0, 0, 0, true); });      // beside the factorisation, not behind it
+    h->hp.hp_warm = std::thread([h]() { if (hipSetDevice(h->prm.device) == hipSuccess) (void)hp_ensure(h->hp, h->prm.device, 0, 0, 0, true); });      // beside the factorisation, not behind it
   } catch (...) { }                                         // no thread: on first use then
 }
 void psfp_destroy(psfp_handle* h) {
   if (!h) return;
   hipSetDevice(h->prm.device);
-  hp_release(h);
-  if (h->sio_pin) hipHostFree(h->sio_pin);
-  hipFree(h->sio_du); hipFree(h->sio_de); hipFree(h->sio_d32);
-  for (auto& ev : h->sio_ev) if (ev) hipEventDestroy(ev);
+  hp_release(h->hp);
   free_batch(h);
   clear_slots(h);
   if (h->side) hipStreamDestroy(h->side);
@@ -1070,7 +1015,15 @@ static void launch_zq(psfp_handle* h, hipStream_t st, const ZqPlan& z, int mode,
                      dim3(256), 0, st, mode, h->dPart, z.splits, h->n, h->n_pad, ld, ncols, h->q, U, out, ldo, (size_t)0);
 }
 
+struct SampCall {      // what one samp_p pass is told by its caller: passed down from the entry point, nothing of it stays on the handle
+  bool keep_fail = false;                                    // dFail[0..3] are not cleared at the head of the pass (the slices of one host call; batch 1 and later of a many-call)
+  bool whole_batch = false;                                  // a stage export wants the intermediates of the whole batch: no one-launch form, the straight host path, no cuts
+  const HostStage* before_u = nullptr;                       // host path: stages the targets; run_samp_p calls it in front of the first stage that reads them (hp_async owns it)
+  const std::chrono::steady_clock::time_point* launched = nullptr;      // psfp_samp_p_multi: the call's start, against which the first enqueued pass stamps multi_launched_ms
+};
+
 struct SampPlan {      // every form choice of one samp_p call, with the launch parameters the choices fix
+  size_t nbj = 0;                                            // 128-column blocks of the rows of this pass
   bool one_launch = false;                                   // k_samp_p_small: the whole call
   int bc = 0; uint32_t ncf = 0, nseg = 0; size_t nwaves = 0;  // normals: dense stream of bc preimages; layout code (h->normals_ncf; 0 = chunk stream); positions per wave, waves
   enum Product : uint8_t { TASKS, TILES64, TILES32, TILES96, BIG } product = BIG;      // x = sqrt(Sigma_2) d
@@ -1090,16 +1043,16 @@ struct SampPlan {      // every form choice of one samp_p call, with the launch 
 
 struct BatchDims { size_t nbj; int zq_split_cap; };      // what ensure_batch derives from B and the plan reads
 
-// The forms of a call of B preimages, from the handle as it stands at the start of the call (after ensure_batch; psfp_query_plan hands in what ensure_batch would leave)
-static SampPlan plan_samp_p(const psfp_handle* h, size_t B, const BatchDims* bd = nullptr) {
+// The forms of a pass over B preimages, from the handle as it stands at the start of the call (after ensure_batch; psfp_query_plan hands in what ensure_batch would leave)
+static SampPlan plan_samp_p(const psfp_handle* h, size_t B, const SampCall& call, const BatchDims* bd = nullptr) {
   SampPlan p;
   const size_t m = h->m;
-  const size_t nbj = bd ? bd->nbj : h->nbj;
+  const size_t nbj = p.nbj = bd ? bd->nbj : round_up(B, TR_BN) / TR_BN;
   // small parameter sets, few preimages (the reference's own benchmarks: n = 8, one call; benches/psf.rs:51-66): the whole call in ONE launch, one
   // workgroup per preimage (k_samp_p_small).  PSF_FUSED_MAX = largest batch it serves (0: never).  Stage exports need the intermediates: not here.
   size_t fused_max = 64;
   if (const char* e = psf_exp_env("PSF_FUSED_MAX")) fused_max = (size_t)std::atol(e);
-  p.one_launch = !h->structured && !h->no_slice && h->gadget_queue && m <= (size_t)FS_MAX_M && h->n <= 64 && B <= fused_max;
+  p.one_launch = !h->structured && !call.whole_batch && h->gadget_queue && m <= (size_t)FS_MAX_M && h->n <= 64 && B <= fused_max;
   if (p.one_launch) return p;
   // Small batches (one samp_p call of the reference is ONE preimage, psf.rs:48-80): the streaming product, bound by reading the factor once, fed by
   // the compact normals stream.  PSF_TRMM_STREAM_MAX = largest batch it serves (0 switches it off); PSF_TRMM_STREAM_SHAPE = "RT,NB" forces a tile
@@ -1282,7 +1235,7 @@ static void prepare_samp_p(psfp_handle* h, hipStream_t st, SampPlan& p) {
 static void normals_stage(psfp_handle* h, hipStream_t st, const SampPlan& p, uint64_t seed, uint64_t first_index, size_t B) {
   ScopedTimer t(h, st, "k_normals");
   const NormalsFixed fx = h->structured ? NormalsFixed{h->mb, h->dD8, h->ldr * h->ld, h->ld, h->dX, h->h_const} : NormalsFixed{0, nullptr, 0, 0, nullptr, 0.0};
-  hipLaunchKernelGGL(k_normals_wave, dim3((unsigned)((p.nwaves + 3) / 4)), dim3(256), 0, st, seed, first_index, h->m, B, h->nkb, h->nbj, h->dDt, h->dFail, fx, p.ncf, p.nseg);
+  hipLaunchKernelGGL(k_normals_wave, dim3((unsigned)((p.nwaves + 3) / 4)), dim3(256), 0, st, seed, first_index, h->m, B, h->nkb, p.nbj, h->dDt, h->dFail, fx, p.ncf, p.nseg);
 }
 
 // x = sqrt(Sigma_2) d   (structured: the m_bar x m_bar block L_1 d_1; rows from m_bar on already hold x_bot = h d_2)
@@ -1290,7 +1243,7 @@ static void product_stage(psfp_handle* h, hipStream_t st, const SampPlan& p, siz
   ScopedTimer t(h, st, "k_trmm_f64");
   const size_t row_hi = h->structured ? h->mb : h->M_pad;
   if (p.product == SampPlan::BIG) {      // k_trmm_f64_big: one workgroup per CU, accumulators in AccVGPRs
-    hipLaunchKernelGGL(k_trmm_f64_big, dim3(tr_grid_size(((int)h->nbiL + 1) / 2, (int)h->nbj, p.GR, p.GC)), dim3(256), 0, st, h->dLt, h->dDt, h->dX, (int)h->nbiL, (int)h->nbj,
+    hipLaunchKernelGGL(k_trmm_f64_big, dim3(tr_grid_size(((int)h->nbiL + 1) / 2, (int)p.nbj, p.GR, p.GC)), dim3(256), 0, st, h->dLt, h->dDt, h->dX, (int)h->nbiL, (int)p.nbj,
                        h->nkb, h->ld, p.GR, p.GC, row_hi);
     return;
   }
@@ -1424,11 +1377,11 @@ static void recombine_stage(psfp_handle* h, hipStream_t st, const SampPlan& p, s
 }
 
 // One samp_p pass over B rows (mp_perturbation.rs:304-336), everything in order on the caller's stream.
-static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_e, hipStream_t st) {
-  if (!h->keep_fail) hipMemsetAsync(h->dFail, 0, 4 * sizeof(int), st);      // [0] sampler failure, [1] some |z| > 127, [2] some |p| >= 2^15 (third digit plane of the syndrome product in use)
+static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* d_u, int64_t* d_e, hipStream_t st, const SampCall& call) {
+  if (!call.keep_fail) hipMemsetAsync(h->dFail, 0, 4 * sizeof(int), st);      // [0] sampler failure, [1] some |z| > 127, [2] some |p| >= 2^15 (third digit plane of the syndrome product in use)
   psf_status gate_rc = PSF_OK;
-  auto u_gate = [&]() { if (h->before_u) { auto f = std::move(h->before_u); h->before_u = nullptr; gate_rc = f(); } };
-  SampPlan p = plan_samp_p(h, B);
+  auto u_gate = [&]() { if (call.before_u) gate_rc = (*call.before_u)(); };      // (once: each branch below passes it once)
+  SampPlan p = plan_samp_p(h, B, call);
   if (!p.one_launch) prepare_samp_p(h, st, p);
   plan_fields(p, h->last_plan);      // as it runs: prepare_samp_p has had its say on the fused tail
   h->has_last_plan = true;
@@ -1456,8 +1409,8 @@ static psf_status run_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index
   HIP_TRY(hipGetLastError());
   if (gate_rc != PSF_OK) return gate_rc;
   h->last_stream = st;
-  if (h->multi_t0 && h->multi_launched_ms < 0.0)
-    h->multi_launched_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - *h->multi_t0).count();
+  if (call.launched && h->multi_launched_ms < 0.0)
+    h->multi_launched_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - *call.launched).count();
   return PSF_OK;
 }
 
@@ -1478,11 +1431,11 @@ psf_status psfp_samp_p_dev(psfp_handle* h, uint64_t seed, uint64_t first_index, 
   psf_status rc = ensure_batch(h, B);
   if (rc != PSF_OK) return rc;
   if (h->timing) clear_slots(h);       // once per public call: the slices of a host-pointer call add up in psfp_get_timing
-  return run_samp_p(h, seed, first_index, B, d_u, d_e, (hipStream_t)stream);
+  return run_samp_p(h, seed, first_index, B, d_u, d_e, (hipStream_t)stream, SampCall{});
 }
 
 // `count` independent psfp_samp_p_dev calls in one submission, in order on the caller's stream (include/psf_mi355x.h).  No second lane: at large batches the FP64
-// product holds every SIMD and nothing issues beside it (profiles/r03_probe_coissue.log).  The failure word of every batch is kept (keep_fail, as the slices of a
+// product holds every SIMD and nothing issues beside it (profiles/r03_probe_coissue.log).  The failure word of every batch is kept (SampCall::keep_fail, as the slices of a
 // host-pointer call do); the gates of the later stages ([1..3]) are cleared in front of each batch as a single call clears them.
 psf_status psfp_samp_p_dev_many(psfp_handle* h, size_t count, const uint64_t* seeds, const uint64_t* first_indices, size_t B, const uint64_t* d_u, int64_t* d_e, void* stream) {
   if (!h || (count && B && (!seeds || !first_indices || !d_u || !d_e))) return PSF_ERR_PARAM;
@@ -1495,399 +1448,101 @@ psf_status psfp_samp_p_dev_many(psfp_handle* h, size_t count, const uint64_t* se
   if (rc != PSF_OK) return rc;
   if (h->timing) clear_slots(h);
   hipStream_t st = (hipStream_t)stream;
-  struct FailGuard { psfp_handle* h; ~FailGuard() { h->keep_fail = false; } } guard{h};
+  SampCall call;
   for (size_t i = 0; i < count && rc == PSF_OK; ++i) {
     if (i > 0) {
-      h->keep_fail = true;
+      call.keep_fail = true;
       HIP_TRY(hipMemsetAsync(h->dFail + 1, 0, 3 * sizeof(int), st));
     }
-    rc = run_samp_p(h, seeds[i], first_indices[i], B, d_u + i * B * h->n, d_e + i * B * h->m, st);
+    rc = run_samp_p(h, seeds[i], first_indices[i], B, d_u + i * B * h->n, d_e + i * B * h->m, st, call);
   }
   return rc;
 }
 
-// ---- host-pointer entry points ---------------------------------------------------------------------------------------------------------------
-constexpr size_t SIO_MAX_BYTES = (size_t)1 << 20;           // calls whose u + e fit this take the one-buffer form (at 4 MB the runtime's copies are faster again: 1.27 vs 1.17 ms at C3, 16 preimages)
-// flags of a small call into the pinned buffer: [0] = a[0] (the failure word psfp_last_status reads), [1 ..] = c[0 .. nc)
-__global__ void k_sio_flags(const int* __restrict__ a, const int* __restrict__ c, int nc, int* __restrict__ out) {
-  const int t = threadIdx.x;
-  if (t == 0) out[0] = a[0];
-  if (t >= 1 && t <= nc) out[t] = c[t - 1];
+// ---- host-pointer entry points (the transport: psf_hostpipe.hpp) ----------------------------------------------------------------------------
+// what hp_async is told about this handle; B: the rows of the call
+static HostCall host_call(psfp_handle* h, size_t B, const int* extra_flags, bool defer_u, bool cut_tail, bool whole_batch) {
+  return HostCall{h->prm.device, h->n, h->m, h->dFail, &h->dE, extra_flags, B > h->Bcap, defer_u, cut_tail, whole_batch};
 }
-static psf_status sio_ensure(psfp_handle* h, size_t bytes) {
-  if (bytes <= h->sio_cap) return PSF_OK;
-  if (h->sio_pin) { hipHostFree(h->sio_pin); h->sio_pin = nullptr; h->sio_cap = 0; }
-  const size_t cap = round_up(bytes, (size_t)64 << 10);
-  HIP_TRY(hipHostMalloc(&h->sio_pin, cap, hipHostMallocDefault));
-  h->sio_cap = cap;
-  return PSF_OK;
-}
-static inline unsigned sio_grid(size_t words) { const size_t g = (words / 2 + 255) / 256; return (unsigned)(g < 1 ? 1 : g > 64 ? 64 : g); }
-// u -> pinned -> d_u (kernel); [the caller's launches]; d_e -> pinned, flags -> pinned (kernels); one synchronisation; pinned -> e.  `flags_out` receives
-// 1 + nc ints.  `run` enqueues the call on the null stream and returns its status.
-static psf_status sio_call(psfp_handle* h, size_t nu, size_t ne, const uint64_t* u, int64_t* e, uint64_t* d_u, int64_t* d_e, const int* fa, const int* fc, int nc,
-                           int* flags_out, const std::function<psf_status()>& run) {
-  const size_t ub = round_up(nu * 8, 64), eb = round_up(ne * 8, 64);
-  psf_status rc = sio_ensure(h, ub + eb + 64);
-  if (rc != PSF_OK) return rc;
-  uint64_t* hu = reinterpret_cast<uint64_t*>(h->sio_pin);
-  int64_t* he = reinterpret_cast<int64_t*>(h->sio_pin + ub);
-  int* hf = reinterpret_cast<int*>(h->sio_pin + ub + eb);
-  std::memcpy(hu, u, nu * 8);
-  hipLaunchKernelGGL(k_copy_words, dim3(sio_grid(nu)), dim3(256), 0, nullptr, hu, d_u, nu);
-  rc = run();
-  if (rc != PSF_OK) { hipStreamSynchronize(nullptr); return rc; }
-  hipLaunchKernelGGL(k_copy_words, dim3(sio_grid(ne)), dim3(256), 0, nullptr, reinterpret_cast<const uint64_t*>(d_e), reinterpret_cast<uint64_t*>(he), ne);
-  hipLaunchKernelGGL(k_sio_flags, dim3(1), dim3(64), 0, nullptr, fa, fc, nc, hf);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  for (int i = 0; i <= nc; ++i) flags_out[i] = hf[i];
-  std::memcpy(e, he, ne * 8);
-  return PSF_OK;
-}
-
-// int32 -> int64 into the caller's rows with streaming stores: the destination is written once and not read here, so there is no point in pulling its
-// lines into the cache first (a plain loop moves 20 bytes per entry through the memory system, this one 12) -- the widening of a C3 batch is 1.5 GB of
-// host memory traffic per call and has to fit under the next call's 60 ms on a handful of threads.
-static void widen_rows(int64_t* __restrict__ dst, const int32_t* __restrict__ src, size_t cnt) {
-  typedef int v4i __attribute__((ext_vector_type(4)));
-  typedef int v2i __attribute__((ext_vector_type(2)));
-  typedef long long v2l __attribute__((ext_vector_type(2)));
-  size_t i = 0;
-  while (i < cnt && (reinterpret_cast<uintptr_t>(dst + i) & 15)) { dst[i] = (int64_t)src[i]; ++i; }
-  for (; i + 4 <= cnt; i += 4) {
-    v4i x;
-    std::memcpy(&x, src + i, sizeof(x));
-    const v2i a = __builtin_shufflevector(x, x, 0, 1), b = __builtin_shufflevector(x, x, 2, 3);
-    __builtin_nontemporal_store(__builtin_convertvector(a, v2l), reinterpret_cast<v2l*>(dst + i));
-    __builtin_nontemporal_store(__builtin_convertvector(b, v2l), reinterpret_cast<v2l*>(dst + i + 2));
-  }
-  for (; i < cnt; ++i) dst[i] = (int64_t)src[i];
-  std::atomic_thread_fence(std::memory_order_seq_cst);      // (streaming stores are weakly ordered: fence before the thread reports its chunk done)
-}
-
-// The flags of an asynchronous call: cleared and sent to pinned host memory by one-wave kernels in stream order.  (hipMemsetAsync / hipMemcpyAsync on the
-// compute stream go through the runtime's copy path, where they queue behind the chunk copies of the call before: the next call's kernels then waited for them.)
-__global__ void k_host_flags_clear(int* __restrict__ fail, int* __restrict__ ovf) { if (threadIdx.x < 4) fail[threadIdx.x] = 0; if (threadIdx.x < 2) ovf[threadIdx.x] = 0; }
-// extra: the eight flag words of a PSFGPV / PSFGPVRing call (psfgpv_impl.hpp: [0] and [4] = a sampler failure of the first / second pass), or nullptr
-__global__ void k_host_flags_send(const int* __restrict__ fail, const int* __restrict__ ovf, const int* __restrict__ extra, int* __restrict__ host_flags) {
-  if (threadIdx.x == 0) {
-    host_flags[0] = fail[0] | (extra ? (extra[0] | extra[4]) : 0);
-    host_flags[1] = fail[1]; host_flags[2] = ovf[0]; host_flags[3] = extra ? 1 : 0;        // [3]: a nearest-plane call (an overflow of the narrowing is not a sampler failure there)
-    __threadfence_system();
-  }
-}
-
-// wait for the asynchronous call in `slot` (its workers have copied and widened every row), release it, return its status
-static psf_status hp_join(psfp_handle* h, int slot) {
-  auto& hp = h->hp;
-  if (!hp.busy[slot]) return PSF_OK;
-  for (auto& t : hp.workers[slot]) if (t.joinable()) t.join();
-  hp.workers[slot].clear();
-  hp.busy[slot] = false;
-  psf_status rc = (psf_status)hp.status[slot].load();
-  if (rc == PSF_OK && hp.hFlags[slot][0]) rc = PSF_ERR_SAMPLER;
-  // an entry beyond 32 bits: impossible for PSFPerturbation (every entry is checked on the device: a sampler failure); a PSFGPV / PSFGPVRing row of that size
-  // needs the synchronous call, which copies 64-bit rows then
-  if (rc == PSF_OK && hp.hFlags[slot][2]) rc = hp.hFlags[slot][3] ? PSF_ERR_UNSUPPORTED : PSF_ERR_SAMPLER;
-  hp.done[hp.slot_seq[slot] & 7] = psfp_handle::HostPipe::Done{hp.slot_seq[slot], (int)rc, true};      // whoever joins consumes the status: the ticket keeps it
+// its resize step: the batch buffers for B rows; the timing slots of the call before go (once per public call: the slices of a host-pointer call add up in psfp_get_timing)
+static psf_status host_resize(psfp_handle* h, size_t B) {
+  const psf_status rc = ensure_batch(h, B);
+  if (rc == PSF_OK && h->timing) clear_slots(h);
   return rc;
 }
 
-static void hp_release(psfp_handle* h) {
-  if (h->hp_warm.joinable()) h->hp_warm.join();
-  auto& hp = h->hp;
-  for (int s = 0; s < 2; ++s) hp_join(h, s);
-  for (int s = 0; s < 2; ++s) {
-    hipFree(hp.dE32[s]); hp.dE32[s] = nullptr;
-    if (hp.hFlags[s]) { hipHostFree(hp.hFlags[s]); hp.hFlags[s] = nullptr; }
-    for (auto& ev : hp.evSlice[s]) if (ev) { hipEventDestroy(ev); ev = nullptr; }
-  }
-  for (int s = 0; s < 2; ++s)
-    for (int w = 0; w < psfp_handle::HostPipe::NW; ++w)
-      for (int k = 0; k < 2; ++k) {
-        if (hp.hbuf[s][w][k]) { hipHostFree(hp.hbuf[s][w][k]); hp.hbuf[s][w][k] = nullptr; }
-        if (hp.evC[s][w][k]) { hipEventDestroy(hp.evC[s][w][k]); hp.evC[s][w][k] = nullptr; }
-        if (hp.sigC[s][w][k].handle) { hp.sdma.drop_signal(hp.sigC[s][w][k]); hp.sigC[s][w][k].handle = 0; }
-      }
-  if (hp.sigU.handle) { hp.sdma.drop_signal(hp.sigU); hp.sigU.handle = 0; }
-  hp.sdma.close();
-  hipFree(hp.dOvf); hp.dOvf = nullptr;
-  for (int s = 0; s < 2; ++s) {
-    if (hp.hU[s]) { hipHostFree(hp.hU[s]); hp.hU[s] = nullptr; }
-    hipFree(hp.dU2[s]); hp.dU2[s] = nullptr;
-  }
-  hp.u_cap[0] = hp.u_cap[1] = 0;
-  if (hp.copy) { hipStreamDestroy(hp.copy); hp.copy = nullptr; }
-  if (hp.compute) { hipStreamDestroy(hp.compute); hp.compute = nullptr; }
-  hp.cap_entries[0] = hp.cap_entries[1] = 0; hp.chunk_entries = 0;
-  hp.slot_ready[0] = hp.slot_ready[1] = false; hp.common_ready = false;
+// psfp_samp_p_async behind its checks; cut_tail: see HostCall.  Each slice is a pass of its own that keeps the call's failure words (cleared once, in front of the first).
+static psf_status samp_p_host_async(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* u, int64_t* e, bool cut_tail, const SampCall& call) {
+  const psf_status rc = hp_async(h->hp, host_call(h, B, nullptr, true, cut_tail, call.whole_batch), B, u, e, [&]() { return host_resize(h, B); },
+                                 [&](size_t off, size_t cnt, const uint64_t* d_u, int64_t* d_e, hipStream_t cs, const HostStage* before_u) -> psf_status {
+    SampCall slice = call;
+    slice.keep_fail = true;
+    slice.before_u = before_u;
+    return run_samp_p(h, seed, first_index + off, cnt, d_u, d_e, cs, slice);
+  });
+  if (rc == PSF_OK) h->last_stream = h->hp.compute;
+  return rc;
 }
-
-// streams, transport and the rings of call slot `slot` (which the caller has joined).  Everything is allocated on first use and per slot: a caller that only ever
-// makes synchronous calls pays for one slot (pinning memory is the expensive part of a handle's first host-pointer call).
-static psf_status hp_ensure(psfp_handle* h, int slot, size_t entries, size_t u_words, bool from_prewarm) {
-  if (!from_prewarm && h->hp_warm.joinable()) h->hp_warm.join();      // (the prewarm worker itself never looks at h->hp_warm: the owner may still be assigning it)
-  auto& hp = h->hp;
-  constexpr int NW = psfp_handle::HostPipe::NW;
-  if (!hp.common_ready) {
-    {  // (matters for the HIP-copy transports only: their copies are shader kernels, which on a queue of lower priority than the compute stream ran only when
-       // that stream was idle -- copies on the HIGH-priority queue, the asynchronous calls' kernels on a normal one)
-      int lo_prio = 0, hi_prio = 0;
-      HIP_TRY(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
-      int pc = hi_prio, pk = (lo_prio + hi_prio) / 2;
-      if (const char* env = psf_exp_env("PSF_HOST_PRIO")) { if (std::atoi(env) == 0) pc = pk; else if (std::atoi(env) == 2) { pc = pk; pk = hi_prio; } }      // experiments: 0 = equal, 2 = compute high
-      if (!hp.copy) HIP_TRY(hipStreamCreateWithPriority(&hp.copy, hipStreamNonBlocking, pc));
-      if (!hp.compute) HIP_TRY(hipStreamCreateWithPriority(&hp.compute, hipStreamNonBlocking, pk));
-    }
-    if (!hp.dOvf) HIP_TRY(hipMalloc(&hp.dOvf, 2 * sizeof(int)));
-    hp.chunk_entries = (size_t)2 << 20;                                  // 8 MiB of int32 per chunk
-    if (const char* env = std::getenv("PSF_HOST_WORKERS")) { const int v = std::atoi(env); if (v >= 1 && v <= NW) hp.nw = v; }
-    if (const char* env = psf_exp_env("PSF_HOST_CHUNK_MB")) { const long v = std::atol(env); if (v >= 1 && v <= 256) hp.chunk_entries = (size_t)v << 18; }
-    if (const char* env = psf_exp_env("PSF_HOST_COPY")) if (std::strncmp(env, "runtime", 7) == 0) hp.copy_mode = 0;      // sdma (default) | runtime
-    if (hp.copy_mode == 1) {
-      int dom = 0, bus = 0, dv = 0;
-      HIP_TRY(hipDeviceGetAttribute(&dom, hipDeviceAttributePciDomainID, h->prm.device));
-      HIP_TRY(hipDeviceGetAttribute(&bus, hipDeviceAttributePciBusId, h->prm.device));
-      HIP_TRY(hipDeviceGetAttribute(&dv, hipDeviceAttributePciDeviceId, h->prm.device));
-      if (!hp.sdma.open(dom, bus, dv)) hp.copy_mode = 0;                  // no HSA agent for this device: the HIP copies (slower under overlap, same rows)
-      else if (!hp.sigU.handle && !hp.sdma.make_signal(&hp.sigU)) return PSF_ERR_HIP;
-    }
-    hp.common_ready = true;
-  }
-  if (!hp.slot_ready[slot]) {                                 // (every piece behind its own test: a call that failed half-way is completed, not repeated, by the next)
-    if (!hp.hFlags[slot]) HIP_TRY(hipHostMalloc(&hp.hFlags[slot], 4 * sizeof(int), hipHostMallocDefault));
-    for (auto& ev : hp.evSlice[slot]) if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    for (int w = 0; w < hp.nw; ++w)
-      for (int k = 0; k < 2; ++k) {
-        if (!hp.hbuf[slot][w][k]) HIP_TRY(hipHostMalloc(&hp.hbuf[slot][w][k], hp.chunk_entries * sizeof(int32_t), hipHostMallocDefault));
-        if (!hp.evC[slot][w][k]) HIP_TRY(hipEventCreateWithFlags(&hp.evC[slot][w][k], hipEventDisableTiming));
-        if (hp.copy_mode == 1 && !hp.sigC[slot][w][k].handle && !hp.sdma.make_signal(&hp.sigC[slot][w][k])) return PSF_ERR_HIP;
-      }
-    hp.slot_ready[slot] = true;
-  }
-  if (entries > hp.cap_entries[slot]) {
-    hipFree(hp.dE32[slot]); hp.dE32[slot] = nullptr;
-    hp.cap_entries[slot] = 0;
-    HIP_TRY(hipMalloc(&hp.dE32[slot], entries * sizeof(int32_t)));
-    hp.cap_entries[slot] = entries;
-  }
-  if (u_words > hp.u_cap[slot]) {
-    if (hp.hU[slot]) hipHostFree(hp.hU[slot]);
-    hp.hU[slot] = nullptr; hipFree(hp.dU2[slot]); hp.dU2[slot] = nullptr;
-    hp.u_cap[slot] = 0;
-    HIP_TRY(hipHostMalloc(&hp.hU[slot], u_words * sizeof(uint64_t), hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&hp.dU2[slot], u_words * sizeof(uint64_t)));
-    hp.u_cap[slot] = u_words;
-  }
-  return PSF_OK;
-}
-
-// Asynchronous samp_p on host buffers: returns once the work is enqueued (the targets have been staged); `e` is complete when psfp_wait returns.
-// At most two calls are in flight: a third waits for the first.  The compute stream runs the slices of the call back to back (row b draws from global
-// index first_index + b, so slicing changes no bit); behind each slice its rows are narrowed to int32 (every entry of a preimage is below 2^31: |p| < 2^23
-// and |R z| <= w 2^15, both checked on the device), copied in chunks to pinned memory on a second stream and widened into `e` by NW worker threads --
-// while the compute stream is already in the next slice or the next call.  A single call therefore ends one short slice after its product
-// (slices: all but the last ~1024 rows, then the rest), and back-to-back calls run at the device-resident rate.
-// What an asynchronous host-pointer call of any of the three types is made of: `compute(off, cnt, d_u, d_e, cs)` enqueues the samp_p pipeline of the rows
-// [off, off + cnt) on the stream cs (targets d_u: cnt x n, preimages d_e: cnt x m, both on the device); everything around it -- slots, staging of the targets,
-// int32 narrowing, chunk transfers by the DMA engines, widening workers, the flags -- is the same.  defer_u: the targets are uploaded when the pipeline asks for them
-// (h->before_u, PSFPerturbation: behind the product); otherwise at the head of the call.  extra_flags: see k_host_flags_send.
-using HpCompute = std::function<psf_status(size_t, size_t, const uint64_t*, int64_t*, hipStream_t)>;
-static psf_status hp_async(psfp_handle* h, size_t B, const uint64_t* u, int64_t* e, bool defer_u, bool allow_slices, const int* extra_flags, const HpCompute& compute);
 
 psf_status psfp_samp_p_async(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* u, int64_t* e) {
   if (!h || (B && (!u || !e))) return PSF_ERR_PARAM;
   if (!h->has_key || !h->has_pub) return PSF_ERR_NO_KEY;
   if (B == 0) return PSF_OK;
-  struct FailGuard { psfp_handle* h; size_t B; ~FailGuard() { h->keep_fail = false; h->nbj = round_up(B, TR_BN) / TR_BN; } } guard{h, B};
-  return hp_async(h, B, u, e, true, true, nullptr, [&](size_t off, size_t cnt, const uint64_t* d_u, int64_t* d_e, hipStream_t cs) -> psf_status {
-    h->keep_fail = true;                                    // the slices of a call share its failure words (cleared once, in front of the first)
-    h->nbj = round_up(cnt, TR_BN) / TR_BN;
-    return run_samp_p(h, seed, first_index + off, cnt, d_u, d_e, cs);
-  });
-}
-
-static psf_status hp_async(psfp_handle* h, size_t B, const uint64_t* u, int64_t* e, bool defer_u, bool allow_slices, const int* extra_flags, const HpCompute& compute) {
-  HIP_TRY(hipSetDevice(h->prm.device));
-  auto& hp = h->hp;
-  const size_t m = h->m, total = B * m;
-  if (!hp.busy[0] && !hp.busy[1]) hp.next = 0;              // nothing in flight: slot 0 (a caller that only makes synchronous calls never needs -- or allocates -- the second)
-  const int slot = (int)(hp.next & 1);
-  psf_status rc = hp_join(h, slot);                         // the call before last used this slot
-  if (rc != PSF_OK) return rc;
-  if (B > h->Bcap) { rc = hp_join(h, slot ^ 1); if (rc != PSF_OK) return rc; }      // ensure_batch reallocates: nothing may be in flight
-  rc = ensure_batch(h, B);
-  if (rc != PSF_OK) return rc;
-  rc = hp_ensure(h, slot, total, B * h->n);
-  if (rc != PSF_OK) return rc;
-  ++hp.next;
-  hp.slot_seq[slot] = hp.seq++;
-  hipStream_t cs = hp.compute;
-  // targets: pageable -> pinned (this thread) -> this call's device copy -- deferred until the syndrome stage of the first slice is about to be enqueued
-  // (h->before_u, run_samp_p): by then the product is executing, and neither the staging copy nor the upload delays the call
-  h->before_u = [h, slot, u, B, cs]() -> psf_status {
-    auto& hp = h->hp;
-    std::memcpy(hp.hU[slot], u, B * h->n * sizeof(uint64_t));
-    if (hp.copy_mode == 1) {                                // by the DMA engine (dU2[slot]'s last reader was joined before this call began)
-      if (!hp.sdma.start_upload(hp.dU2[slot], hp.hU[slot], B * h->n * sizeof(uint64_t), hp.sigU) || !hp.sdma.wait(hp.sigU)) return PSF_ERR_HIP;
-    } else {
-      hipLaunchKernelGGL(k_copy_words, dim3(64), dim3(256), 0, cs, hp.hU[slot], hp.dU2[slot], B * h->n);  // (see k_copy_words: a HIP copy would queue behind the download before)
-    }
-    return PSF_OK;
-  };
-  struct GateGuard { psfp_handle* h; ~GateGuard() { h->before_u = nullptr; } } gate_guard{h};      // (an error return must not leave a callback with dead captures behind)
-  if (hp.copy_mode != 1 || !defer_u) {                      // the copy kernel is ordered by the compute stream only: at the head of the call, as before
-    auto f = std::move(h->before_u); h->before_u = nullptr;
-    rc = f();
-    if (rc != PSF_OK) return rc;
-  }
-  const uint64_t* dUcall = hp.dU2[slot];
-  if (h->timing) clear_slots(h);
-  // slices: everything but a short tail, then the tail (its transfer is all that remains exposed behind the last kernel)
-  size_t cuts[5] = {0, B, B, B, B};
-  int nsl = 1;
-  // (two slices cost the product ~4 ms)
-  size_t tail = 1024;
-  if (const char* env = psf_exp_env("PSF_HOST_TAIL")) { const long v = std::atol(env); if (v >= 128) tail = (size_t)v; }
-  bool cut = hp.slice_tail;                                 // the synchronous form only: behind an asynchronous call the next call's compute covers the transfer
-  if (const char* env = psf_exp_env("PSF_HOST_ASYNC_SLICE")) cut = cut || std::atoi(env) != 0;      // experiments: 1 = asynchronous calls cut the tail slice too
-  if (cut && allow_slices && !h->no_slice && B >= 2 * tail) { cuts[1] = B - tail; cuts[2] = B; nsl = 2; }
-  if (const char* env = psf_exp_env("PSF_HOST_SLICE")) {    // experiments: equal slices of this many rows (at most four)
-    const long v = std::atol(env);
-    if (v >= 128 && allow_slices && !h->no_slice && (size_t)v < B) {
-      nsl = 0;
-      for (size_t off = 0; off < B && nsl < 4; off += (size_t)v) cuts[nsl++] = off;
-      cuts[nsl] = B;
-    }
-  }
-  hipLaunchKernelGGL(k_host_flags_clear, dim3(1), dim3(64), 0, cs, h->dFail, hp.dOvf);
-  for (int j = 0; j < nsl; ++j) {
-    const size_t off = cuts[j], cnt = cuts[j + 1] - cuts[j];
-    rc = compute(off, cnt, dUcall + off * h->n, h->dE + off * m, cs);
-    if (rc != PSF_OK) return rc;
-    hipLaunchKernelGGL(k_narrow_rows, dim3(grid_for(cnt * m / 2 + 1, 256, 256 * 16)), dim3(256), 0, cs, h->dE + off * m, hp.dE32[slot] + off * m, cnt * m, hp.dOvf);
-    if (j == nsl - 1) {                                     // the call's flags travel with its last slice
-      hipLaunchKernelGGL(k_host_flags_send, dim3(1), dim3(64), 0, cs, h->dFail, hp.dOvf, extra_flags, hp.hFlags[slot]);
-    }
-    HIP_TRY(hipEventRecord(hp.evSlice[slot][j], cs));
-  }
-  HIP_TRY(hipGetLastError());
-  h->last_stream = cs;
-  // workers: chunk c of the call's entries belongs to worker c % NW; a worker copies its chunk into one of its two pinned buffers and widens the
-  // previous one meanwhile
-  const size_t CE = hp.chunk_entries, nchunks = (total + CE - 1) / CE;
-  hp.status[slot] = (int)PSF_OK;
-  hp.busy[slot] = true;
-  const int32_t* src = hp.dE32[slot];
-  const int device = h->prm.device;
-  size_t slice_end[4]; hipEvent_t slice_ev[4];
-  for (int j = 0; j < nsl; ++j) { slice_end[j] = cuts[j + 1] * m; slice_ev[j] = hp.evSlice[slot][j]; }
-  const int nw = hp.nw;
-  int dbg = 0;
-  if (const char* env = psf_exp_env("PSF_HOST_DEBUG")) dbg = std::atoi(env);      // measurement only: 1 = no widening, 2 = no copies either (e is NOT filled)
-  const int copy_mode = hp.copy_mode;
-  const bool plain_widen = psf_exp_env("PSF_HOST_PLAIN_WIDEN") != nullptr;      // measurement only: the scalar loop with ordinary stores
-  auto worker = [&hp, slot, src, e, total, CE, nchunks, nsl, device, slice_end, slice_ev, nw, dbg, copy_mode, plain_widen](int w) {
-    if (hipSetDevice(device) != hipSuccess) { hp.status[slot] = (int)PSF_ERR_HIP; return; }
-    auto widen = [&](size_t c, int k) {
-      if (copy_mode == 1 ? (dbg < 2 && !hp.sdma.wait(hp.sigC[slot][w][k])) : hipEventSynchronize(hp.evC[slot][w][k]) != hipSuccess) { hp.status[slot] = (int)PSF_ERR_HIP; return; }
-      const size_t b0 = c * CE, cnt = total - b0 < CE ? total - b0 : CE;
-      const int32_t* hs = hp.hbuf[slot][w][k];
-      int64_t* dst = e + b0;
-      if (dbg) return;
-      if (plain_widen) { for (size_t i = 0; i < cnt; ++i) dst[i] = (int64_t)hs[i]; }
-      else widen_rows(dst, hs, cnt);
-    };
-    long prev = -1; int pk = 0, k = 0;
-    for (size_t c = (size_t)w; c < nchunks; c += (size_t)nw) {
-      const size_t b0 = c * CE, cnt = total - b0 < CE ? total - b0 : CE;
-      int j = 0;
-      while (j < nsl - 1 && b0 + cnt > slice_end[j]) ++j;                // the last slice this chunk touches
-      if (copy_mode == 1) {                                              // the slice's rows are complete (host wait), then the DMA engine moves the chunk
-        if (hipEventSynchronize(slice_ev[j]) != hipSuccess ||
-            (dbg < 2 && !hp.sdma.start(hp.hbuf[slot][w][k], src + b0, cnt * sizeof(int32_t), hp.sigC[slot][w][k]))) { hp.status[slot] = (int)PSF_ERR_HIP; break; }
-      } else if (hipStreamWaitEvent(hp.copy, slice_ev[j], 0) != hipSuccess ||
-                 (dbg < 2 ? hipMemcpyAsync(hp.hbuf[slot][w][k], src + b0, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, hp.copy) : hipSuccess) != hipSuccess ||
-                 hipEventRecord(hp.evC[slot][w][k], hp.copy) != hipSuccess) { hp.status[slot] = (int)PSF_ERR_HIP; break; }
-      if (prev >= 0) widen((size_t)prev, pk);
-      prev = (long)c; pk = k; k ^= 1;
-    }
-    if (prev >= 0) widen((size_t)prev, pk);
-  };
-  try {
-    for (int w = 0; w < nw && (size_t)w < nchunks; ++w) hp.workers[slot].emplace_back(worker, w);
-  } catch (...) {                                                        // no thread available: the started ones finish, the rest of the rows are missing
-    hp.status[slot] = (int)PSF_ERR_HIP;
-  }
-  // (the call's flags were copied on the compute stream in front of the last slice's event, which the worker of the last chunk waits for: once the
-  // workers have been joined the flags have landed)
-  return PSF_OK;
+  return samp_p_host_async(h, seed, first_index, B, u, e, false, SampCall{});
 }
 
 // all asynchronous calls of this handle have completed: their rows are in the callers' buffers; the first non-OK status (oldest call first)
 psf_status psfp_wait(psfp_handle* h) {
   if (!h) return PSF_ERR_PARAM;
   HIP_TRY(hipSetDevice(h->prm.device));
-  auto& hp = h->hp;
-  psf_status first = PSF_OK;
-  for (int i = 0; i < 2; ++i) {
-    const int slot = (int)((hp.next + (size_t)i) & 1);                   // oldest first
-    const psf_status rc = hp_join(h, slot);
-    if (first == PSF_OK) first = rc;
-  }
-  return first;
+  return hp_wait(h->hp);
 }
 
-// the ticket the next asynchronous call of this handle will carry, and the status of ONE asynchronous call by its ticket (waits for it and for the older call
-// in flight, nothing newer): psfp_wait returns the first failure of everything outstanding and thereby consumes the statuses of calls the caller may not be
-// asking about -- a caller that keeps several batches (the shim's PendingBatch) asks per ticket.  PSF_ERR_PARAM: a ticket never issued or older than the last 8 joined calls.
+// the ticket the next asynchronous call of this handle will carry, and the status of ONE asynchronous call by its ticket (hp_wait_ticket): psfp_wait returns the
+// first failure of everything outstanding and thereby consumes the statuses of calls the caller may not be asking about -- a caller that keeps several batches
+// (the shim's PendingBatch) asks per ticket.
 uint64_t psfp_async_next_ticket(const psfp_handle* h) { return h ? h->hp.seq : 0; }
 psf_status psfp_wait_ticket(psfp_handle* h, uint64_t ticket) {
   if (!h) return PSF_ERR_PARAM;
   HIP_TRY(hipSetDevice(h->prm.device));
-  auto& hp = h->hp;
-  if (ticket >= hp.seq) return PSF_ERR_PARAM;
-  for (int i = 0; i < 2; ++i) {                                         // oldest first, up to the ticket's own call
-    const int slot = (int)((hp.next + (size_t)i) & 1);
-    if (hp.busy[slot] && hp.slot_seq[slot] <= ticket) hp_join(h, slot);
-  }
-  const auto& d = hp.done[ticket & 7];
-  return (d.used && d.seq == ticket) ? (psf_status)d.status : PSF_ERR_PARAM;
+  return hp_wait_ticket(h->hp, ticket);
 }
 
-psf_status psfp_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* u, int64_t* e) {
+// psfp_samp_p, psfp_samp_p_stages and psfp_samp_p_multi behind their own checks
+static psf_status samp_p_host(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* u, int64_t* e, const SampCall& call) {
   if (!h || (B && (!u || !e))) return PSF_ERR_PARAM;
   if (!h->has_key || !h->has_pub) return PSF_ERR_NO_KEY;
   if (B == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(h->prm.device));
-  if (B * h->m < ((size_t)1 << 20) || h->no_slice) {
+  if (B * h->m < ((size_t)1 << 20) || call.whole_batch) {
     // a single call / a handful of preimages (or a stage export): nothing to overlap -- straight through on the default stream
     psf_status rc = psfp_wait(h);
     if (rc != PSF_OK) return rc;
     rc = ensure_batch(h, B);
     if (rc != PSF_OK) return rc;
-    if (!h->no_slice && B * (h->n + h->m) * 8 <= SIO_MAX_BYTES && !psf_exp_env("PSF_HOST_STRAIGHT")) {
+    if (!call.whole_batch && B * (h->n + h->m) * 8 <= SIO_MAX_BYTES && !psf_exp_env("PSF_HOST_STRAIGHT")) {
       if (h->timing) clear_slots(h);
       int fl[1] = {0};
-      rc = sio_call(h, B * h->n, B * h->m, u, e, h->dU, h->dE, h->dFail, nullptr, 0, fl,
-                    [&]() { return run_samp_p(h, seed, first_index, B, h->dU, h->dE, nullptr); });
+      rc = sio_call(h->hp, B * h->n, B * h->m, u, e, h->dU, h->dE, h->dFail, nullptr, 0, fl,
+                    [&]() { return run_samp_p(h, seed, first_index, B, h->dU, h->dE, nullptr, call); });
       if (rc != PSF_OK) return rc;
       return fl[0] ? PSF_ERR_SAMPLER : PSF_OK;
     }
     HIP_TRY(hipMemcpy(h->dU, u, B * h->n * sizeof(uint64_t), hipMemcpyHostToDevice));
     if (h->timing) clear_slots(h);
-    rc = run_samp_p(h, seed, first_index, B, h->dU, h->dE, nullptr);
+    rc = run_samp_p(h, seed, first_index, B, h->dU, h->dE, nullptr, call);
     if (rc != PSF_OK) return rc;
     rc = psfp_last_status(h);
     HIP_TRY(hipMemcpy(e, h->dE, B * h->m * sizeof(int64_t), hipMemcpyDeviceToHost));
     return rc;
   }
-  h->hp.slice_tail = true;
-  const psf_status rc = psfp_samp_p_async(h, seed, first_index, B, u, e);
-  h->hp.slice_tail = false;
+  const psf_status rc = samp_p_host_async(h, seed, first_index, B, u, e, true, call);      // a short last slice: single-call latency
   const psf_status rw = psfp_wait(h);
   return rc != PSF_OK ? rc : rw;
+}
+
+psf_status psfp_samp_p(psfp_handle* h, uint64_t seed, uint64_t first_index, size_t B, const uint64_t* u, int64_t* e) {
+  return samp_p_host(h, seed, first_index, B, u, e, SampCall{});
 }
 
 // One job over several handles (one per GPU of the node, each with the same key): rows are cut into contiguous shares
@@ -1920,9 +1575,9 @@ psf_status psfp_samp_p_multi(psfp_handle* const* handles, int count, uint64_t se
     psfp_handle* h = handles[i];
     h->multi_launched_ms = h->multi_done_ms = -1.0;
     if (!cnt[i]) return;
-    h->multi_t0 = &t0;
-    rc[i] = psfp_samp_p(h, seed, first_index + first[i], cnt[i], u + first[i] * h->n, e + first[i] * h->m);
-    h->multi_t0 = nullptr;
+    SampCall call;
+    call.launched = &t0;
+    rc[i] = samp_p_host(h, seed, first_index + first[i], cnt[i], u + first[i] * h->n, e + first[i] * h->m, call);
     h->multi_done_ms = ms_since(std::chrono::steady_clock::now());
   };
   std::vector<std::thread> pool;
@@ -1951,9 +1606,9 @@ psf_status psfp_samp_p_stages(psfp_handle* h, uint64_t seed, uint64_t first_inde
                               int64_t* p, uint64_t* v, int64_t* z, int64_t* e) {
   if (!h || !u || B == 0) return PSF_ERR_PARAM;
   std::vector<int64_t> etmp(B * h->m);
-  h->no_slice = true;
-  psf_status rc = psfp_samp_p(h, seed, first_index, B, u, etmp.data());
-  h->no_slice = false;
+  SampCall call;
+  call.whole_batch = true;
+  psf_status rc = samp_p_host(h, seed, first_index, B, u, etmp.data(), call);
   if (rc != PSF_OK && rc != PSF_ERR_SAMPLER) return rc;
   const size_t m = h->m, ld = h->ld;
   if (e) std::memcpy(e, etmp.data(), etmp.size() * sizeof(int64_t));
@@ -2078,7 +1733,7 @@ psf_status psf_narrow_rows_dev(const int64_t* d_src, int32_t* d_dst, size_t coun
   if (((uintptr_t)d_src & 15) || ((uintptr_t)d_dst & 7)) return PSF_ERR_PARAM;
   if (count == 0) return PSF_OK;
   HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(k_narrow_rows, dim3(grid_for(count / 2 + 1, 256, 256 * 16)), dim3(256), 0, (hipStream_t)stream, d_src, d_dst, count, d_overflow);
+  launch_narrow_rows((hipStream_t)stream, d_src, d_dst, count, d_overflow);
   HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
@@ -2091,7 +1746,7 @@ psf_status psfp_query_plan(const psfp_handle* h, size_t B, int* fields, size_t c
   BatchDims bd;
   bd.nbj = round_up(B, TR_BN) / TR_BN;
   bd.zq_split_cap = B <= h->Bcap ? h->zq_split_cap : zq_split_cap_for(h, round_up(B, TR_BN));
-  plan_fields(plan_samp_p(h, B, &bd), fields);
+  plan_fields(plan_samp_p(h, B, SampCall{}, &bd), fields);
   return PSF_OK;
 }
 
