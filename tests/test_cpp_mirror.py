@@ -78,6 +78,22 @@ def test_hostpipe_host_arithmetic_under_address_and_ub_sanitizers():
     assert r.returncode == 0 and "HOSTPIPE_HOST_OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
 
 
+def test_owning_templates_under_address_and_ub_sanitizers():
+    """tools_amd/csrc/psf_owned.hpp (no HIP in it): the owners of a handle's device arrays, pinned arrays, streams and events, over a fake acquire /
+    release pair that records every handle.  tests/cpp/owned_check.cpp asserts that each handle acquired is released exactly once and in the documented
+    order: default construction, destruction when empty, alloc over a held resource, a failing alloc (empty, capacity 0), reset, move construction, move
+    assignment onto a held resource, self-move-assignment, growth below / at / above the capacity, an array of owners and a struct's members destroyed
+    together.  Built with the ROCm toolchain's clang++ (host code only); nothing of it is loaded into Python."""
+    src = os.path.join(ROOT, "tests", "cpp", "owned_check.cpp")
+    exe = os.path.join(ROOT, "tests", "cpp", "owned_check")
+    clangxx = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
+    b = subprocess.run([clangxx, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src],
+                       capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert r.returncode == 0 and "OWNED_OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
 def test_oracle_under_address_and_ub_sanitizers():
     """The checker itself: oracle/*.c built with gcc -fsanitize=address,undefined and run through one small flow per scheme
     (tests/cpp/oracle_sanitize.c)."""

@@ -10,6 +10,7 @@
 // Skinny products (M = one panel) are cut along K over gridDim.z workgroups; the partial tiles go to a workspace and k_gemm_reduce adds them
 // in split order -- no atomics, so every result is reproducible bit for bit (every rank regenerates the key from the seed).
 #pragma once
+#include "psf_hip_util.hpp"
 #include "psf_kernels.hpp"
 
 namespace psf {
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(256) void k_rows_inv_norm2(const double* __restrict
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-struct GemmWorkspace { double* ws = nullptr; size_t bytes = 0; };
+struct GemmWorkspace { double* ws = nullptr; size_t bytes = 0; };      // (a view: whoever made ws releases it)
 
 // launches C = beta C + alpha (A op(B)) diag(colscale); cuts K when the tile grid alone would leave most of the chip idle
 template <bool NT>
@@ -319,18 +320,18 @@ inline hipError_t gemm_prepare() {
 inline hipError_t gso_blocked(hipStream_t st, double* Gt, size_t nrows, size_t d, int* d_info) {
   hipError_t e = gemm_prepare();
   if (e != hipSuccess) return e;
-  double *dInv = nullptr, *dC = nullptr, *dG = nullptr, *dLi = nullptr;
+  DevArr<double> dInv, dC, dG, dLi, dWs;                                     // released on every return
   GemmWorkspace w;
   const size_t dpad = (d + GM_T - 1) / GM_T * GM_T, rpad = (nrows + GM_T - 1) / GM_T * GM_T;
   w.bytes = (size_t)64 * GM_T * GM_T * sizeof(double);                       // a single 128 x 128 tile cut 64 ways ...
   const size_t alt = (size_t)900 * GM_T * GM_T * sizeof(double) + (dpad > rpad ? dpad : rpad) * GM_T * sizeof(double);   // ... or < 384 + 512 (tile, split) pairs
   if (alt > w.bytes) w.bytes = alt;
-  auto fail = [&](hipError_t err) { hipFree(dInv); hipFree(dC); hipFree(dG); hipFree(dLi); hipFree(w.ws); return err; };
-  if ((e = hipMalloc(&dInv, rpad * sizeof(double))) != hipSuccess) return fail(e);
-  if ((e = hipMalloc(&dC, GM_T * rpad * sizeof(double))) != hipSuccess) return fail(e);
-  if ((e = hipMalloc(&dG, GM_T * GM_T * sizeof(double))) != hipSuccess) return fail(e);
-  if ((e = hipMalloc(&dLi, GM_T * GM_T * sizeof(double))) != hipSuccess) return fail(e);
-  if ((e = hipMalloc(&w.ws, w.bytes)) != hipSuccess) return fail(e);
+  if ((e = dInv.alloc(rpad)) != hipSuccess) return e;
+  if ((e = dC.alloc(GM_T * rpad)) != hipSuccess) return e;
+  if ((e = dG.alloc(GM_T * GM_T)) != hipSuccess) return e;
+  if ((e = dLi.alloc(GM_T * GM_T)) != hipSuccess) return e;
+  if ((e = dWs.alloc(w.bytes / sizeof(double))) != hipSuccess) return e;
+  w.ws = dWs;
   for (size_t i0 = 0; i0 < nrows; i0 += GM_T) {
     const size_t p = nrows - i0 < (size_t)GM_T ? nrows - i0 : (size_t)GM_T;
     double* W = Gt + i0 * d;
@@ -351,7 +352,7 @@ inline hipError_t gso_blocked(hipStream_t st, double* Gt, size_t nrows, size_t d
   }
   e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  return fail(e);
+  return e;
 }
 
 }  // namespace psf

@@ -1,6 +1,6 @@
-// psf_hip_util.hpp -- what the host side of every HIP translation unit shares: the error macro, the device check, the compute-unit count, an
-// owning device buffer for allocations that live for one call, the dynamic-LDS limit of a kernel, and the dispatch of a runtime integer to a
-// template argument.
+// psf_hip_util.hpp -- what the host side of every HIP translation unit shares: the error macro, the device check, the compute-unit count, the
+// owners of device arrays, pinned arrays, streams and events (every hipFree, hipHostFree, hipStreamDestroy and hipEventDestroy of a handle's or a call's resources is
+// here), the dynamic-LDS limit of a kernel, and the dispatch of a runtime integer to a template argument.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -10,6 +10,7 @@
 #include <utility>
 #include <vector>
 #include "../../include/psf_mi355x.h"
+#include "psf_owned.hpp"
 
 #define HIP_TRY(expr)                                                                  \
   do {                                                                                 \
@@ -55,23 +56,27 @@ inline psf_status raise_lds_once(const void* kern, int device, size_t smem) {
   return PSF_OK;
 }
 
-// device memory that lives for one call: freed on every exit of the scope.  The operations return the runtime's code, for HIP_TRY.
+// What a handle or a call holds, released when its owner dies (psf_owned.hpp): members in reverse order of declaration, after the destructor's body.
+// DevArr / PinArr: alloc(count, slack_bytes) and grow(need, slack_bytes) return the runtime's code, for HIP_TRY; Stream / Event: hipEventCreate(ev.put()).
+// A raw pointer, stream or event in a struct beside these is NOT owned by it.
+inline hipError_t dev_acquire(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+inline hipError_t pin_acquire(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+template <class T> using DevArr = OwnedArr<T, dev_acquire, hipFree>;
+template <class T> using PinArr = OwnedArr<T, pin_acquire, hipHostFree>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+
+// untyped device memory that lives for one call: freed on every exit of the scope.  The operations return the runtime's code, for HIP_TRY.
 class DevBuf {
  public:
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
-  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { (void)hipFree(p_); p_ = o.p_; o.p_ = nullptr; } return *this; }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { (void)hipFree(p_); }
-  hipError_t alloc(size_t bytes) { (void)hipFree(p_); p_ = nullptr; return hipMalloc(&p_, bytes); }
+  hipError_t alloc(size_t bytes) { return p_.alloc(bytes); }
   hipError_t upload(const void* src, size_t bytes) { return hipMemcpy(p_, src, bytes, hipMemcpyHostToDevice); }
   hipError_t download(void* dst, size_t bytes) const { return hipMemcpy(dst, p_, bytes, hipMemcpyDeviceToHost); }
   hipError_t zero(size_t bytes) { return hipMemset(p_, 0, bytes); }
-  template <class T> T* as() const { return static_cast<T*>(p_); }
+  template <class T> T* as() const { return reinterpret_cast<T*>(p_.get()); }
 
  private:
-  void* p_ = nullptr;
+  DevArr<unsigned char> p_;
 };
 
 // a runtime integer as a template argument: f(ic<V>{}) for the V of the list that equals v; false when none does

@@ -25,19 +25,17 @@ namespace psf {
 struct HostPipe {
   static constexpr int NW = 8;                // at most this many worker threads per call (each: its own pinned chunk buffers, copies + widening of chunks c = w mod nw)
   int nw = 4;                                 // workers in use (PSF_HOST_WORKERS)
-  int32_t* dE32[2] = {nullptr, nullptr};      // device: narrowed rows of the call in flight, two calls deep
-  size_t cap_entries[2] = {0, 0};             // entries dE32[slot] holds
+  DevArr<int32_t> dE32[2];                    // device: narrowed rows of the call in flight, two calls deep (grown to the call's entries)
   bool slot_ready[2] = {false, false};        // the slot's flags, events, pinned chunk buffers and signals exist
   bool common_ready = false;                  // streams, overflow word, transport
-  int32_t* hbuf[2][NW][2] = {};               // pinned chunk buffers [call slot][worker][double buffer]: two calls in flight never share one
-  hipEvent_t evC[2][NW][2] = {};              // chunk landed in its pinned buffer
+  PinArr<int32_t> hbuf[2][NW][2];             // pinned chunk buffers [call slot][worker][double buffer]: two calls in flight never share one
+  Event evC[2][NW][2];                        // chunk landed in its pinned buffer
   size_t chunk_entries = 0;
-  hipEvent_t evSlice[2][4] = {};              // slice j of call slot s has been narrowed (compute stream)
-  int* hFlags[2] = {nullptr, nullptr};        // pinned: [0] sampler failure, [1] unused, [2] int32 overflow of a row entry
-  int* dOvf = nullptr;                        // device: overflow flag of the narrowing kernel
-  uint64_t* hU[2] = {nullptr, nullptr};       // pinned staging of the targets (a copy from pageable memory would block the caller behind the stream)
-  uint64_t* dU2[2] = {nullptr, nullptr};      // device copy of the targets per call in flight (filled by k_copy_words at the head of the call)
-  size_t u_cap[2] = {0, 0};
+  Event evSlice[2][4];                        // slice j of call slot s has been narrowed (compute stream)
+  PinArr<int> hFlags[2];                      // pinned: [0] sampler failure, [1] unused, [2] int32 overflow of a row entry
+  DevArr<int> dOvf;                           // device: overflow flag of the narrowing kernel
+  PinArr<uint64_t> hU[2];                     // pinned staging of the targets (a copy from pageable memory would block the caller behind the stream)
+  DevArr<uint64_t> dU2[2];                    // device copy of the targets per call in flight (filled by k_copy_words at the head of the call); grown with hU
   std::vector<std::thread> workers[2];
   bool busy[2] = {false, false};
   std::atomic<int> status[2] = {{0}, {0}};     // psf_status of the call in each slot (written by its workers)
@@ -47,17 +45,19 @@ struct HostPipe {
   struct Done { uint64_t seq; int status; bool used; } done[8] = {};      // the last joined calls and their statuses (hp_wait_ticket)
   int copy_mode = 1;                          // how a chunk crosses PCIe: 1 = SDMA engine through the HSA runtime (psf_sdma.hpp), 0 = hipMemcpyAsync (PSF_HOST_COPY)
   SdmaCopy sdma;
-  hsa_signal_t sigC[2][NW][2] = {};           // mode 1: chunk landed in its pinned buffer
+  hsa_signal_t sigC[2][NW][2] = {};           // mode 1: chunk landed in its pinned buffer (HSA signals: dropped by the destructor, in front of sdma.close())
   hsa_signal_t sigU = {};                     // mode 1: the call's targets have reached the device
-  hipStream_t copy = nullptr;                 // D2H stream (high priority)
-  hipStream_t compute = nullptr;              // stream of the asynchronous calls' kernels (normal priority)
+  Stream copy;                                // D2H stream (high priority)
+  Stream compute;                             // stream of the asynchronous calls' kernels (normal priority)
   std::thread hp_warm;                        // the prewarm worker (hp_ensure beside a key's factorisation); joined by whoever touches the transport next
   // small host-pointer calls (one preimage is the reference's call): u, e and the flags travel through ONE pinned buffer by kernels in stream order, one
   // synchronisation per call -- the straight form (hipMemcpy in, flags out twice, hipMemcpy out: five blocking runtime calls) cost ~70 us around 47 us of kernels
-  uint8_t* sio_pin = nullptr; size_t sio_cap = 0;
-  uint64_t* sio_du = nullptr; int64_t* sio_de = nullptr; size_t sio_du_cap = 0, sio_de_cap = 0;      // device side for handles without their own (PSFGPV / ring)
-  int32_t* sio_d32 = nullptr; size_t sio_d32_cap = 0;         // narrowed rows of a PSFGPV / ring batch on their way to the host
-  hipEvent_t sio_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // pieces 0..3 of such a batch have landed; [4]: its flags have
+  PinArr<uint8_t> sio_pin;
+  DevArr<uint64_t> sio_du; DevArr<int64_t> sio_de;            // device side for handles without their own (PSFGPV / ring)
+  DevArr<int32_t> sio_d32;                                    // narrowed rows of a PSFGPV / ring batch on their way to the host
+  Event sio_ev[5];                                            // pieces 0..3 of such a batch have landed; [4]: its flags have
+  void quiesce();                             // joins the prewarm worker and the workers of both call slots: in front of every release of what their calls read
+  ~HostPipe();
 };
 
 constexpr size_t SIO_MAX_BYTES = (size_t)1 << 20;           // calls whose u + e fit this take the one-buffer form (at 4 MB the runtime's copies are faster again: 1.27 vs 1.17 ms at C3, 16 preimages)
@@ -83,14 +83,6 @@ __global__ void k_host_flags_send(const int* __restrict__ fail, const int* __res
 }
 }  // extern "C"
 
-// a cached device buffer of at least `need` elements (+ slack_bytes): kept when large enough, else freed and allocated anew (the contents are not carried over)
-template <class T> static psf_status grow_dev(T*& p, size_t& cap, size_t need, size_t slack_bytes = 0) {
-  if (need <= cap) return PSF_OK;
-  hipFree(p); p = nullptr; cap = 0;
-  HIP_TRY(hipMalloc(&p, need * sizeof(T) + slack_bytes));
-  cap = need;
-  return PSF_OK;
-}
 // k_narrow_rows over `count` entries on `st`, a pair of entries per lane
 static inline void launch_narrow_rows(hipStream_t st, const int64_t* src, int32_t* dst, size_t count, int* ovf) {
   const size_t g = (count / 2 + 1 + 255) / 256;
@@ -98,17 +90,15 @@ static inline void launch_narrow_rows(hipStream_t st, const int64_t* src, int32_
 }
 
 static psf_status sio_ensure(HostPipe& hp, size_t bytes) {
-  if (bytes <= hp.sio_cap) return PSF_OK;
-  if (hp.sio_pin) { hipHostFree(hp.sio_pin); hp.sio_pin = nullptr; hp.sio_cap = 0; }
-  const size_t cap = round_up(bytes, (size_t)64 << 10);
-  HIP_TRY(hipHostMalloc(&hp.sio_pin, cap, hipHostMallocDefault));
-  hp.sio_cap = cap;
+  if (bytes <= hp.sio_pin.cap()) return PSF_OK;
+  HIP_TRY(hp.sio_pin.alloc(round_up(bytes, (size_t)64 << 10)));
   return PSF_OK;
 }
 // device targets and rows for a handle without its own (PSFGPV / ring): hp.sio_du, hp.sio_de
 static psf_status sio_dev_rows(HostPipe& hp, size_t nu, size_t ne) {
-  const psf_status rc = grow_dev(hp.sio_du, hp.sio_du_cap, nu);
-  return rc != PSF_OK ? rc : grow_dev(hp.sio_de, hp.sio_de_cap, ne);
+  HIP_TRY(hp.sio_du.grow(nu));
+  HIP_TRY(hp.sio_de.grow(ne));
+  return PSF_OK;
 }
 static inline unsigned sio_grid(size_t words) { const size_t g = (words / 2 + 255) / 256; return (unsigned)(g < 1 ? 1 : g > 64 ? 64 : g); }
 // u -> pinned -> d_u (kernel); [the caller's launches]; d_e -> pinned, flags -> pinned (kernels); one synchronisation; pinned -> e.  `flags_out` receives
@@ -118,7 +108,7 @@ static psf_status sio_call(HostPipe& hp, size_t nu, size_t ne, const uint64_t* u
   const size_t ub = round_up(nu * 8, 64), eb = round_up(ne * 8, 64);
   psf_status rc = sio_ensure(hp, ub + eb + 64);
   if (rc != PSF_OK) return rc;
-  uint64_t* hu = reinterpret_cast<uint64_t*>(hp.sio_pin);
+  uint64_t* hu = reinterpret_cast<uint64_t*>(hp.sio_pin.get());
   int64_t* he = reinterpret_cast<int64_t*>(hp.sio_pin + ub);
   int* hf = reinterpret_cast<int*>(hp.sio_pin + ub + eb);
   std::memcpy(hu, u, nu * 8);
@@ -134,7 +124,7 @@ static psf_status sio_call(HostPipe& hp, size_t nu, size_t ne, const uint64_t* u
   return PSF_OK;
 }
 
-// A batch of a type that keeps no device rows of its own (PSFGPV / ring), as sio_call: cached device buffers (no hipMalloc / hipFree per call), u through the pinned
+// A batch of a type that keeps no device rows of its own (PSFGPV / ring), as sio_call: cached device buffers (no allocation per call), u through the pinned
 // buffer, `run(d_u, d_e)` on the null stream, the rows narrowed to int32 on the device (every entry of a preimage fits by far; k_narrow_rows raises a flag otherwise
 // and the int64 rows are copied instead), the flags first, then the rows in NT pieces into pinned memory with an event behind each: thread i widens piece i with
 // streaming stores as soon as it has landed, while the later pieces are still crossing PCIe.  The straight form (two pageable copies around two allocations) took
@@ -143,11 +133,12 @@ static psf_status sio_batch(HostPipe& hp, int device, size_t nu, size_t ne, cons
                             const std::function<psf_status(uint64_t*, int64_t*)>& run) {
   constexpr int NT = 4;
   psf_status rc = sio_dev_rows(hp, nu, ne);
-  if (rc == PSF_OK) rc = grow_dev(hp.sio_d32, hp.sio_d32_cap, ne, 2 * sizeof(int));
-  const size_t ub = round_up(nu * 8, 64), eb = round_up(ne * 4, 64);
-  if (rc == PSF_OK) rc = sio_ensure(hp, ub + eb + 64);
   if (rc != PSF_OK) return rc;
-  uint64_t* hu = reinterpret_cast<uint64_t*>(hp.sio_pin);
+  HIP_TRY(hp.sio_d32.grow(ne, 2 * sizeof(int)));
+  const size_t ub = round_up(nu * 8, 64), eb = round_up(ne * 4, 64);
+  rc = sio_ensure(hp, ub + eb + 64);
+  if (rc != PSF_OK) return rc;
+  uint64_t* hu = reinterpret_cast<uint64_t*>(hp.sio_pin.get());
   int32_t* he = reinterpret_cast<int32_t*>(hp.sio_pin + ub);
   int* hf = reinterpret_cast<int*>(hp.sio_pin + ub + eb);
   int* d_ovf = reinterpret_cast<int*>(hp.sio_d32 + ne);                    // overflow word of the narrowing, behind the rows
@@ -159,7 +150,7 @@ static psf_status sio_batch(HostPipe& hp, int device, size_t nu, size_t ne, cons
   launch_narrow_rows(nullptr, hp.sio_de, hp.sio_d32, ne, d_ovf);
   hipLaunchKernelGGL(k_sio_flags, dim3(1), dim3(64), 0, nullptr, fa, fc, nc, hf);
   HIP_TRY(hipMemcpyAsync(hf + 12, d_ovf, sizeof(int), hipMemcpyDeviceToHost, nullptr));
-  if (!hp.sio_ev[0]) for (auto& ev : hp.sio_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  if (!hp.sio_ev[0]) for (auto& ev : hp.sio_ev) HIP_TRY(hipEventCreateWithFlags(ev.put(), hipEventDisableTiming));
   HIP_TRY(hipEventRecord(hp.sio_ev[NT], nullptr));                       // flags and overflow word are in pinned memory
   const size_t per = host_piece_len(ne, NT);
   for (int i = 0; i < NT; ++i) {
@@ -231,38 +222,17 @@ static psf_status hp_wait_ticket(HostPipe& hp, uint64_t ticket) {
   return (d.used && d.seq == ticket) ? (psf_status)d.status : PSF_ERR_PARAM;
 }
 
-// everything the transport holds (the device of its handle is current): the calls in flight are joined first
-static void hp_release(HostPipe& hp) {
-  if (hp.hp_warm.joinable()) hp.hp_warm.join();
-  for (int s = 0; s < 2; ++s) hp_join(hp, s);
-  for (int s = 0; s < 2; ++s) {
-    hipFree(hp.dE32[s]); hp.dE32[s] = nullptr;
-    if (hp.hFlags[s]) { hipHostFree(hp.hFlags[s]); hp.hFlags[s] = nullptr; }
-    for (auto& ev : hp.evSlice[s]) if (ev) { hipEventDestroy(ev); ev = nullptr; }
-  }
-  for (int s = 0; s < 2; ++s)
-    for (int w = 0; w < HostPipe::NW; ++w)
-      for (int k = 0; k < 2; ++k) {
-        if (hp.hbuf[s][w][k]) { hipHostFree(hp.hbuf[s][w][k]); hp.hbuf[s][w][k] = nullptr; }
-        if (hp.evC[s][w][k]) { hipEventDestroy(hp.evC[s][w][k]); hp.evC[s][w][k] = nullptr; }
-        if (hp.sigC[s][w][k].handle) { hp.sdma.drop_signal(hp.sigC[s][w][k]); hp.sigC[s][w][k].handle = 0; }
-      }
-  if (hp.sigU.handle) { hp.sdma.drop_signal(hp.sigU); hp.sigU.handle = 0; }
-  hp.sdma.close();
-  hipFree(hp.dOvf); hp.dOvf = nullptr;
-  for (int s = 0; s < 2; ++s) {
-    if (hp.hU[s]) { hipHostFree(hp.hU[s]); hp.hU[s] = nullptr; }
-    hipFree(hp.dU2[s]); hp.dU2[s] = nullptr;
-  }
-  hp.u_cap[0] = hp.u_cap[1] = 0;
-  if (hp.copy) { hipStreamDestroy(hp.copy); hp.copy = nullptr; }
-  if (hp.compute) { hipStreamDestroy(hp.compute); hp.compute = nullptr; }
-  hp.cap_entries[0] = hp.cap_entries[1] = 0; hp.chunk_entries = 0;
-  hp.slot_ready[0] = hp.slot_ready[1] = false; hp.common_ready = false;
-  if (hp.sio_pin) { hipHostFree(hp.sio_pin); hp.sio_pin = nullptr; hp.sio_cap = 0; }
-  hipFree(hp.sio_du); hipFree(hp.sio_de); hipFree(hp.sio_d32);
-  hp.sio_du = nullptr; hp.sio_de = nullptr; hp.sio_d32 = nullptr; hp.sio_du_cap = hp.sio_de_cap = hp.sio_d32_cap = 0;
-  for (auto& ev : hp.sio_ev) if (ev) { hipEventDestroy(ev); ev = nullptr; }
+// the calls in flight are joined; nothing of the transport is read or written by another thread afterwards
+inline void HostPipe::quiesce() {
+  if (hp_warm.joinable()) hp_warm.join();
+  for (int s = 0; s < 2; ++s) hp_join(*this, s);
+}
+// (the device of the handle is current)  The signals are dropped and the DMA path is closed here, in front of the members: the streams are destroyed after sdma.close()
+inline HostPipe::~HostPipe() {
+  quiesce();
+  for (auto& slot : sigC) for (auto& wk : slot) for (auto& sg : wk) if (sg.handle) sdma.drop_signal(sg);
+  if (sigU.handle) sdma.drop_signal(sigU);
+  sdma.close();
 }
 
 // streams, transport and the rings of call slot `slot` (which the caller has joined) on `device`.  Everything is allocated on first use and per slot: a caller that
@@ -277,10 +247,10 @@ static psf_status hp_ensure(HostPipe& hp, int device, int slot, size_t entries, 
       HIP_TRY(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
       int pc = hi_prio, pk = (lo_prio + hi_prio) / 2;
       if (const char* env = psf_exp_env("PSF_HOST_PRIO")) { if (std::atoi(env) == 0) pc = pk; else if (std::atoi(env) == 2) { pc = pk; pk = hi_prio; } }      // experiments: 0 = equal, 2 = compute high
-      if (!hp.copy) HIP_TRY(hipStreamCreateWithPriority(&hp.copy, hipStreamNonBlocking, pc));
-      if (!hp.compute) HIP_TRY(hipStreamCreateWithPriority(&hp.compute, hipStreamNonBlocking, pk));
+      if (!hp.copy) HIP_TRY(hipStreamCreateWithPriority(hp.copy.put(), hipStreamNonBlocking, pc));
+      if (!hp.compute) HIP_TRY(hipStreamCreateWithPriority(hp.compute.put(), hipStreamNonBlocking, pk));
     }
-    if (!hp.dOvf) HIP_TRY(hipMalloc(&hp.dOvf, 2 * sizeof(int)));
+    if (!hp.dOvf) HIP_TRY(hp.dOvf.alloc(2));
     hp.chunk_entries = (size_t)2 << 20;                                  // 8 MiB of int32 per chunk
     if (const char* env = std::getenv("PSF_HOST_WORKERS")) { const int v = std::atoi(env); if (v >= 1 && v <= NW) hp.nw = v; }
     if (const char* env = psf_exp_env("PSF_HOST_CHUNK_MB")) { const long v = std::atol(env); if (v >= 1 && v <= 256) hp.chunk_entries = (size_t)v << 18; }
@@ -296,25 +266,21 @@ static psf_status hp_ensure(HostPipe& hp, int device, int slot, size_t entries, 
     hp.common_ready = true;
   }
   if (!hp.slot_ready[slot]) {                                 // (every piece behind its own test: a call that failed half-way is completed, not repeated, by the next)
-    if (!hp.hFlags[slot]) HIP_TRY(hipHostMalloc(&hp.hFlags[slot], 4 * sizeof(int), hipHostMallocDefault));
-    for (auto& ev : hp.evSlice[slot]) if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (!hp.hFlags[slot]) HIP_TRY(hp.hFlags[slot].alloc(4));
+    for (auto& ev : hp.evSlice[slot]) if (!ev) HIP_TRY(hipEventCreateWithFlags(ev.put(), hipEventDisableTiming));
     for (int w = 0; w < hp.nw; ++w)
       for (int k = 0; k < 2; ++k) {
-        if (!hp.hbuf[slot][w][k]) HIP_TRY(hipHostMalloc(&hp.hbuf[slot][w][k], hp.chunk_entries * sizeof(int32_t), hipHostMallocDefault));
-        if (!hp.evC[slot][w][k]) HIP_TRY(hipEventCreateWithFlags(&hp.evC[slot][w][k], hipEventDisableTiming));
+        if (!hp.hbuf[slot][w][k]) HIP_TRY(hp.hbuf[slot][w][k].alloc(hp.chunk_entries));
+        if (!hp.evC[slot][w][k]) HIP_TRY(hipEventCreateWithFlags(hp.evC[slot][w][k].put(), hipEventDisableTiming));
         if (hp.copy_mode == 1 && !hp.sigC[slot][w][k].handle && !hp.sdma.make_signal(&hp.sigC[slot][w][k])) return PSF_ERR_HIP;
       }
     hp.slot_ready[slot] = true;
   }
-  const psf_status rc = grow_dev(hp.dE32[slot], hp.cap_entries[slot], entries);
-  if (rc != PSF_OK) return rc;
-  if (u_words > hp.u_cap[slot]) {
-    if (hp.hU[slot]) hipHostFree(hp.hU[slot]);
-    hp.hU[slot] = nullptr; hipFree(hp.dU2[slot]); hp.dU2[slot] = nullptr;
-    hp.u_cap[slot] = 0;
-    HIP_TRY(hipHostMalloc(&hp.hU[slot], u_words * sizeof(uint64_t), hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&hp.dU2[slot], u_words * sizeof(uint64_t)));
-    hp.u_cap[slot] = u_words;
+  HIP_TRY(hp.dE32[slot].grow(entries));
+  if (u_words > hp.dU2[slot].cap()) {                         // the pair grows together: both released, then both allocated (dU2 last: its capacity stands for the pair)
+    hp.hU[slot].reset(); hp.dU2[slot].reset();
+    HIP_TRY(hp.hU[slot].alloc(u_words));
+    HIP_TRY(hp.dU2[slot].alloc(u_words));
   }
   return PSF_OK;
 }
@@ -323,7 +289,7 @@ static psf_status hp_ensure(HostPipe& hp, int device, int slot, size_t entries, 
 struct HostCall {
   int device; size_t n, m;            // the handle's device; words of a target, entries of a row
   int* dFail;                         // the handle's four failure words
-  int64_t* const* rows;               // where the handle keeps the device rows of its batch (read after `resize`, which may move them)
+  const DevArr<int64_t>* rows;        // where the handle keeps the device rows of its batch (read after `resize`, which may move them)
   const int* extra_flags;             // see k_host_flags_send
   bool regrows;                       // `resize` will reallocate the batch buffers: nothing may be in flight then
   bool defer_u;                       // the targets are uploaded when the pipeline asks for them (PSFPerturbation: behind the product); otherwise at the head of the call

@@ -7,43 +7,46 @@
 #include "psf_hip_util.hpp"
 // Everything one batch of the nearest plane writes: a lane.  Lane 0 serves every call; samp_p_dev_many runs the odd batches of a launch-per-block walk on lane 1
 // (allocated by the first such many-call of two or more batches), so that one batch's solve, projection and recombination overlap the other lane's walk.
-struct NpLane {
-  size_t bcap = 0, ld = 0;
-  double* dTm = nullptr;              // running projections, dpad x ld
-  double* dZf = nullptr;              // z as f64, chunk stream (ld / 128) x nkb
-  int8_t* dZ8 = nullptr; size_t zplane = 0;          // three digit planes of z, [dpad / 16][ld][16] each
-  unsigned char* dZocc = nullptr;     // which 128 x 128 tiles of z digits 1 and 2 hold anything: [2][ld / 128][nrb] (k_np_occ_z, per call)
-  double* dC0p = nullptr;             // -sol on the pivots, chunk stream (ld / 128) x nkc
-  uint64_t* dSol = nullptr;           // n x ld
-  double* dC1 = nullptr;              // two-pass walk: -e1, chunk stream (ld / 128) x nkd
-  int64_t* dE1 = nullptr;             // two-pass walk: e1, bcap x dim
-  unsigned* dWalk = nullptr;          // k_np_walk: [group][block] counters of published z | [group][block] flags of completed rows | abort word
-  size_t walk_words = 0;
-  int* dFlags = nullptr;              // [0] sampler failure [1] second digit of some z in use [2] third digit [3] |z| beyond three digits; [4..7]: the same for the second pass;
+// (its per-batch buffers are a struct of their own, so that ensure_np_batch releases them in one assignment, in this order; bcap = 0: the next call starts over)
+struct NpBatch {
+  size_t bcap = 0;
+  DevArr<double> dTm;                 // running projections, dpad x ld
+  DevArr<double> dZf;                 // z as f64, chunk stream (ld / 128) x nkb
+  DevArr<int8_t> dZ8;                 // three digit planes of z, [dpad / 16][ld][16] each
+  DevArr<double> dC0p;                // -sol on the pivots, chunk stream (ld / 128) x nkc
+  DevArr<uint64_t> dSol;              // n x ld
+  DevArr<double> dC1;                 // two-pass walk: -e1, chunk stream (ld / 128) x nkd
+  DevArr<int64_t> dE1;                // two-pass walk: e1, bcap x dim
+  DevArr<unsigned> dWalk;             // k_np_walk: [group][block] counters of published z | [group][block] flags of completed rows | abort word
+  DevArr<unsigned char> dZocc;        // which 128 x 128 tiles of z digits 1 and 2 hold anything: [2][ld / 128][nrb] (k_np_occ_z, per call)
+};
+struct NpLane : NpBatch {
+  size_t ld = 0, zplane = 0, walk_words = 0;
+  DevArr<int> dFlags;                 // [0] sampler failure [1] second digit of some z in use [2] third digit [3] |z| beyond three digits; [4..7]: the same for the second pass;
                                       // [8..9] a 64-bit count of walks re-run by k_np_walk_solo (never cleared)
-  int* dFail = nullptr;               // failure words of the base handle the call clears (psfp_last_status reads them): lane 0 only
+  int* dFail = nullptr;               // NOT owned: the failure words of the base handle the call clears (psfp_last_status reads them): lane 0 only
 };
 
 struct psfgpv_handle {
-  psfp_handle* base = nullptr;
+  psfp_handle* base = nullptr;        // NOT owned by this struct: made by psfp_create, released by psfp_destroy (psfgpv_destroy)
   double s = 0;
   size_t n = 0, m = 0, dim = 0;       // dim = lattice dimension walked by the nearest plane (= m here)
-  int32_t* dSt = nullptr;             // dim x dim, row i = basis vector i
-  double* dGt = nullptr;              // dim x dim, row i = b~_i
-  double* dNorm2 = nullptr;
-  SampleZParams* dSz = nullptr;
-  uint64_t* dT = nullptr;             // n x n solve operator, transposed
-  uint32_t* dPiv = nullptr;           // n pivot columns
+  DevArr<int32_t> dSt;                // dim x dim, row i = basis vector i
+  DevArr<double> dGt;                 // dim x dim, row i = b~_i
+  DevArr<double> dNorm2;
+  DevArr<SampleZParams> dSz;
+  DevArr<uint64_t> dT;                // n x n solve operator, transposed
+  DevArr<uint32_t> dPiv;              // n pivot columns
   // blocked nearest plane (psf_np_kernels.hpp): per key
   size_t nblk = 0, dpad = 0, nrb = 0, nkc = 0, nkb = 0;   // 64-row blocks; dim padded to 128; 128-row blocks; K chunks of the pivots; K chunks of dim
-  double* dGp = nullptr;              // bulk panels g[< 64 J][block J], fragment order
-  double* dGin = nullptr;             // in-block triangles, packed, nblk x NP_TRI
-  double* dGnx = nullptr;             // panels between neighbouring blocks, nblk x 64 x 64
-  NpRow* dRows = nullptr;             // per-row constants of the sampler's fast path (1 / ||b~_i||^2, SampleZ tables)
-  double* dBpiv = nullptr;            // b~_i on the pivot columns, fragment order
-  int8_t* dB8 = nullptr;              // two digit planes of the basis, transposed, dpad x dpad each
+  DevArr<double> dGp;                 // bulk panels g[< 64 J][block J], fragment order
+  DevArr<double> dGin;                // in-block triangles, packed, nblk x NP_TRI
+  DevArr<double> dGnx;                // panels between neighbouring blocks, nblk x 64 x 64
+  DevArr<NpRow> dRows;                // per-row constants of the sampler's fast path (1 / ||b~_i||^2, SampleZ tables)
+  DevArr<double> dBpiv;               // b~_i on the pivot columns, fragment order
+  DevArr<int8_t> dB8;                 // two digit planes of the basis, transposed, dpad x dpad each
   bool basis_hi = false, basis_generic = false;
-  unsigned char* dBocc = nullptr;     // which 128 x 128 tiles of the basis digit planes hold anything: [2][nrb][nrb] (k_np_occ_basis, per key)
+  DevArr<unsigned char> dBocc;        // which 128 x 128 tiles of the basis digit planes hold anything: [2][nrb][nrb] (k_np_occ_basis, per key)
   int np_combine = 1;                 // PSF_NP_COMBINE: 1 / unset = one fused launch over the occupied tiles (k_np_combine8_fused), 0 = one launch per digit pair
   // per batch: lane 0 for every call, lane 1 beside it for samp_p_dev_many
   NpLane ln[2];
@@ -51,7 +54,7 @@ struct psfgpv_handle {
   // two-pass walk for large moduli (q sqrt(n) > 2^13 s): the first pass only finds a short coset representative e1, the second samples around it
   bool two_pass = false;
   size_t nkd = 0;                     // K chunks of all d coordinates
-  double* dBfull = nullptr;           // b~_i on every coordinate, fragment order (A operand of the second projection)
+  DevArr<double> dBfull;              // b~_i on every coordinate, fragment order (A operand of the second projection)
   int np_walk = -1;                   // PSF_NP_WALK: 0 = one launch per block (k_np_step); 1 / unset = the whole walk in one launch (k_np_walk: updater workgroups, T in
                                       // registers) where it fits, launches otherwise; 3 = k_np_walk2 (helper waves update T in memory) for every batch that is resident
   int cus = 0;                        // compute units of the device
@@ -61,16 +64,16 @@ struct psfgpv_handle {
   int last_parts = 1;                 // column ranges the last call walked side by side (np_split)
   int split_delay_us = 0;             // the second half starts this much behind the first
   int np_split = 0;                   // experiments build: 0 never, 1 whenever the shape allows, 2 for large batches (>= 3072) only
-  hipStream_t sh[2] = {nullptr, nullptr};                  // non-blocking, equal priority: the lanes of samp_p_dev_many (created with lane 1); the experiments
+  Stream sh[2];                                            // non-blocking, equal priority: the lanes of samp_p_dev_many (created with lane 1); the experiments
                                                            // build also walks the two halves of a large batch side by side on them
-  hipEvent_t evFork = nullptr, evHalf[2] = {nullptr, nullptr};
+  Event evFork, evHalf[2];
   int np_g = 0;                       // PSF_NP_G: preimages per wave of the sampler (0 = by batch size)
   int np_immediate = -1;              // PSF_NP_IMMEDIATE: 1 = every block updates all the rows below it in the launch that follows, 0 = panel-deferred far update, -1 = by batch size
   bool has_key = false;
   bool timing = false;
   bool last_generic = false;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  hipStream_t last_stream = nullptr;
+  Event ev[3];
+  hipStream_t last_stream = nullptr;  // NOT owned
 };
 
 // Gram-Schmidt of the rows of dSt into dGt (MatQ::gso, gpv.rs:91), then ||b~_i||^2, the per-step sampler tables and the
@@ -182,32 +185,26 @@ static psf_status gpv_build_solver(psfgpv_handle* g) {
   return PSF_OK;
 }
 
-static void free_np_batch(NpLane& L) {
-  hipFree(L.dTm); hipFree(L.dZf); hipFree(L.dZ8); hipFree(L.dC0p); hipFree(L.dSol); hipFree(L.dC1); hipFree(L.dE1); hipFree(L.dWalk); hipFree(L.dZocc);
-  L.dZocc = nullptr;
-  L.dTm = L.dZf = L.dC0p = L.dC1 = nullptr; L.dZ8 = nullptr; L.dSol = nullptr; L.dE1 = nullptr; L.dWalk = nullptr;
-  L.bcap = 0;
-}
 // synchronises the device when it (re)allocates: never between the fork and the join of a many-call (psfgpv_samp_p_dev_many sizes both lanes first)
 static psf_status ensure_np_batch(psfgpv_handle* g, NpLane& L, size_t B) {
   if (B <= L.bcap) return PSF_OK;
   HIP_TRY(hipDeviceSynchronize());
-  free_np_batch(L);
+  static_cast<NpBatch&>(L) = NpBatch{};      // every buffer of the smaller batch is released before the first of the larger is allocated
   const size_t ld = round_up(B, TR_BN);
   L.ld = ld;
-  HIP_TRY(hipMalloc(&L.dTm, g->dpad * ld * sizeof(double)));
-  HIP_TRY(hipMalloc(&L.dZf, ld * g->nkb * 16 * sizeof(double)));
+  HIP_TRY(L.dTm.alloc(g->dpad * ld));
+  HIP_TRY(L.dZf.alloc(ld * g->nkb * 16));
   L.zplane = g->dpad * ld;
-  HIP_TRY(hipMalloc(&L.dZ8, 3 * L.zplane));
-  HIP_TRY(hipMalloc(&L.dZocc, 2 * (ld / 128) * g->nrb));
-  HIP_TRY(hipMalloc(&L.dC0p, ld * g->nkc * 16 * sizeof(double)));
-  HIP_TRY(hipMalloc(&L.dSol, g->n * ld * sizeof(uint64_t)));
+  HIP_TRY(L.dZ8.alloc(3 * L.zplane));
+  HIP_TRY(L.dZocc.alloc(2 * (ld / 128) * g->nrb));
+  HIP_TRY(L.dC0p.alloc(ld * g->nkc * 16));
+  HIP_TRY(L.dSol.alloc(g->n * ld));
   if (g->two_pass) {
-    HIP_TRY(hipMalloc(&L.dC1, ld * g->nkd * 16 * sizeof(double)));
-    HIP_TRY(hipMalloc(&L.dE1, B * g->dim * sizeof(int64_t)));
+    HIP_TRY(L.dC1.alloc(ld * g->nkd * 16));
+    HIP_TRY(L.dE1.alloc(B * g->dim));
   }
   L.walk_words = round_up(2 * (ld / NP_GW) * g->nblk + 4, 4);
-  HIP_TRY(hipMalloc(&L.dWalk, L.walk_words * sizeof(unsigned)));
+  HIP_TRY(L.dWalk.alloc(L.walk_words));
   HIP_TRY(hipMemset(L.dTm, 0, g->dpad * ld * sizeof(double)));
   HIP_TRY(hipMemset(L.dZf, 0, ld * g->nkb * 16 * sizeof(double)));      // padding rows / columns of the operands stay zero for good
   HIP_TRY(hipMemset(L.dZ8, 0, 3 * L.zplane));
@@ -454,27 +451,27 @@ static psf_status psfgpv_init(psfgpv_handle* g) {
   g->nrb = g->dpad / 128;
   g->nkc = round_up(g->n, 16) / 16;
   g->nkb = round_up(d, NP_NB) / 16;
-  HIP_TRY(hipMalloc(&g->dSt, d * d * sizeof(int32_t)));
-  HIP_TRY(hipMalloc(&g->dGt, d * d * sizeof(double)));
-  HIP_TRY(hipMalloc(&g->dNorm2, d * sizeof(double)));
-  HIP_TRY(hipMalloc(&g->dSz, d * sizeof(SampleZParams)));
-  HIP_TRY(hipMalloc(&g->dT, g->n * g->n * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc(&g->dPiv, g->n * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc(&g->dGp, (np_panel_base(g->nblk) + 1) * TR_CHUNK * sizeof(double)));
-  HIP_TRY(hipMalloc(&g->dGin, g->nblk * NP_TRI * sizeof(double)));
-  HIP_TRY(hipMalloc(&g->dGnx, g->nblk * NP_NB * NP_NB * sizeof(double)));
-  HIP_TRY(hipMalloc(&g->dRows, g->nblk * NP_NB * sizeof(NpRow)));
-  HIP_TRY(hipMalloc(&g->dBpiv, g->nrb * g->nkc * TR_CHUNK * sizeof(double)));
-  HIP_TRY(hipMalloc(&g->dB8, 2 * g->dpad * g->dpad));
-  HIP_TRY(hipMalloc(&g->dBocc, 2 * g->nrb * g->nrb));
-  HIP_TRY(hipMalloc(&g->ln[0].dFlags, 12 * sizeof(int)));                 // [0..7] per call (two passes), [8..9] a 64-bit count of walks re-run by k_np_walk_solo (never cleared)
+  HIP_TRY(g->dSt.alloc(d * d));
+  HIP_TRY(g->dGt.alloc(d * d));
+  HIP_TRY(g->dNorm2.alloc(d));
+  HIP_TRY(g->dSz.alloc(d));
+  HIP_TRY(g->dT.alloc(g->n * g->n));
+  HIP_TRY(g->dPiv.alloc(g->n));
+  HIP_TRY(g->dGp.alloc((np_panel_base(g->nblk) + 1) * TR_CHUNK));
+  HIP_TRY(g->dGin.alloc(g->nblk * NP_TRI));
+  HIP_TRY(g->dGnx.alloc(g->nblk * NP_NB * NP_NB));
+  HIP_TRY(g->dRows.alloc(g->nblk * NP_NB));
+  HIP_TRY(g->dBpiv.alloc(g->nrb * g->nkc * TR_CHUNK));
+  HIP_TRY(g->dB8.alloc(2 * g->dpad * g->dpad));
+  HIP_TRY(g->dBocc.alloc(2 * g->nrb * g->nrb));
+  HIP_TRY(g->ln[0].dFlags.alloc(12));                 // [0..7] per call (two passes), [8..9] a 64-bit count of walks re-run by k_np_walk_solo (never cleared)
   HIP_TRY(hipMemset(g->ln[0].dFlags, 0, 12 * sizeof(int)));
   g->ln[0].dFail = g->base->dFail;
   // large moduli: q sqrt(n) > 2^13 s (relative centre error of a single pass above 2^-40, see include/psf_mi355x.h "Precision of the centres"); PSF_NP_TWO_PASS=0/1 forces
   g->two_pass = (double)g->base->q * std::sqrt((double)g->n) > g->s * 8192.0;
   { const char* ev = psf_exp_env("PSF_NP_TWO_PASS"); if (ev) g->two_pass = atoi(ev) != 0; }
   g->nkd = round_up(d, 16) / 16;
-  if (g->two_pass) HIP_TRY(hipMalloc(&g->dBfull, g->nrb * g->nkd * TR_CHUNK * sizeof(double)));
+  if (g->two_pass) HIP_TRY(g->dBfull.alloc(g->nrb * g->nkd * TR_CHUNK));
   { const char* ev = psf_exp_env("PSF_NP_G"); g->np_g = ev ? atoi(ev) : 0; }
   { const char* ev = psf_exp_env("PSF_NP_IMMEDIATE"); g->np_immediate = ev ? (atoi(ev) != 0 ? 1 : 0) : -1; }
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_np_project), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TR_CHUNK * sizeof(double)));
@@ -504,11 +501,11 @@ static psf_status psfgpv_init(psfgpv_handle* g) {
   if (const char* e = psf_exp_env("PSF_NP_WALK_SPINS")) { const long v = std::atol(e); if (v >= 1) g->walk_spins = (unsigned)v; }
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_np_combine8_fused), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 768));
   if (const char* e = psf_exp_env("PSF_NP_COMBINE")) g->np_combine = std::atoi(e);
-  for (auto& e : g->ev) HIP_TRY(hipEventCreate(&e));
+  for (auto& e : g->ev) HIP_TRY(hipEventCreate(e.put()));
 #ifdef PSF_EXPERIMENTS      /* the two-halves walk (measured neutral: not in the release library) */
-  for (auto& sx : g->sh) HIP_TRY(hipStreamCreateWithFlags(&sx, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreateWithFlags(&g->evFork, hipEventDisableTiming));
-  for (auto& e : g->evHalf) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& sx : g->sh) HIP_TRY(hipStreamCreateWithFlags(sx.put(), hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(g->evFork.put(), hipEventDisableTiming));
+  for (auto& e : g->evHalf) HIP_TRY(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
 #endif
   if (const char* e = psf_exp_env("PSF_NP_SPLIT")) { const int v = std::atoi(e); if (v >= 0 && v <= 2) g->np_split = v; }
   if (const char* e = psf_exp_env("PSF_NP_SPLIT_DELAY")) { const int v = std::atoi(e); if (v >= 0 && v <= 1000) g->split_delay_us = v; }
@@ -517,16 +514,11 @@ static psf_status psfgpv_init(psfgpv_handle* g) {
 
 void psfgpv_destroy(psfgpv_handle* g) {
   if (!g) return;
-  hipSetDevice(g->base->prm.device);
-  for (auto& L : g->ln) { free_np_batch(L); hipFree(L.dFlags); }
-  hipFree(g->dSt); hipFree(g->dGt); hipFree(g->dNorm2); hipFree(g->dSz); hipFree(g->dT); hipFree(g->dPiv);
-  hipFree(g->dGp); hipFree(g->dGin); hipFree(g->dGnx); hipFree(g->dRows); hipFree(g->dBpiv); hipFree(g->dB8); hipFree(g->dBocc); hipFree(g->dBfull);
-  for (auto& e : g->ev) if (e) hipEventDestroy(e);
-  for (auto& sx : g->sh) if (sx) hipStreamDestroy(sx);
-  if (g->evFork) hipEventDestroy(g->evFork);
-  for (auto& e : g->evHalf) if (e) hipEventDestroy(e);
-  psfp_destroy(g->base);
+  psfp_handle* const base = g->base;
+  hipSetDevice(base->prm.device);
+  base->hp.quiesce();      // the base handle's transport first: the kernels of its asynchronous calls read the lanes and the key operands released next
   delete g;
+  psfp_destroy(base);
 }
 
 size_t psfgpv_m(const psfgpv_handle* g) { return g ? g->m : 0; }
@@ -699,13 +691,13 @@ static psf_status gpv_batch(psfgpv_handle* g, NpLane& L, hipStream_t st, uint64_
 static psf_status gpv_ensure_lane1(psfgpv_handle* g) {
   NpLane& L = g->ln[1];
   if (!L.dFlags) {
-    HIP_TRY(hipMalloc(&L.dFlags, 12 * sizeof(int)));
+    HIP_TRY(L.dFlags.alloc(12));
     HIP_TRY(hipMemset(L.dFlags, 0, 12 * sizeof(int)));
     HIP_TRY(hipDeviceSynchronize());
   }
-  for (auto& sx : g->sh) if (!sx) HIP_TRY(hipStreamCreateWithFlags(&sx, hipStreamNonBlocking));
-  if (!g->evFork) HIP_TRY(hipEventCreateWithFlags(&g->evFork, hipEventDisableTiming));
-  for (auto& e : g->evHalf) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& sx : g->sh) if (!sx) HIP_TRY(hipStreamCreateWithFlags(sx.put(), hipStreamNonBlocking));
+  if (!g->evFork) HIP_TRY(hipEventCreateWithFlags(g->evFork.put(), hipEventDisableTiming));
+  for (auto& e : g->evHalf) if (!e) HIP_TRY(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
   return PSF_OK;
 }
 
@@ -947,7 +939,7 @@ struct psfring_handle {
   double s_td = 0;
   std::vector<uint64_t> a;             // (k+2) x n
   std::vector<int64_t> r, e;           // k x n
-  uint32_t* dHat = nullptr;            // NTT images of the k+2 polynomials of a (psf_ntt_api.hpp), when (q, n) has a wave kernel
+  DevArr<uint32_t> dHat;               // NTT images of the k+2 polynomials of a (psf_ntt_api.hpp), when (q, n) has a wave kernel
   bool fa_ntt = false;                 // f_a as k+2 R_q products (gpv_ring.rs:243-247) instead of the embedded matrix product
 };
 
@@ -977,7 +969,7 @@ static psf_status ring_install(psfring_handle* h) {
   if (ntt_route(h->gp.q, n) == 2 && ((size_t)K * n + 4 * n) * sizeof(uint32_t) <= 64 * 1024) {
     // (the key is installed and usable at this point: a failure below only means that f_a keeps the matrix-product route, it is not an error of the call)
     DevBuf da;
-    psf_status rf = (h->dHat || hipMalloc(&h->dHat, K * n * sizeof(uint32_t)) == hipSuccess) ? PSF_OK : PSF_ERR_HIP;
+    psf_status rf = (h->dHat || h->dHat.alloc(K * n) == hipSuccess) ? PSF_OK : PSF_ERR_HIP;
     if (rf == PSF_OK && (da.alloc(K * n * sizeof(uint64_t)) != hipSuccess || da.upload(h->a.data(), K * n * sizeof(uint64_t)) != hipSuccess)) rf = PSF_ERR_HIP;
     if (rf == PSF_OK) rf = ntt_forward_dev(b->prm.device, h->gp.q, n, K, da.as<uint64_t>(), 64, h->dHat, nullptr);
     if (rf == PSF_OK && hipDeviceSynchronize() != hipSuccess) rf = PSF_ERR_HIP;
@@ -1007,9 +999,11 @@ psf_status psfring_create(const psfring_params* prm, psfring_handle** out) {
 
 void psfring_destroy(psfring_handle* h) {
   if (!h) return;
-  if (h->dHat) hipFree(h->dHat);
-  psfgpv_destroy(h->g);
+  hipSetDevice(h->g->base->prm.device);
+  h->g->base->hp.quiesce();      // the base handle's transport first, before a key operand is released
+  psfgpv_handle* const g = h->g;
   delete h;
+  psfgpv_destroy(g);
 }
 
 // MatQ::gso (gpv.rs:88-91) as a free function: rows of an integer matrix -> their Gram-Schmidt vectors

@@ -50,9 +50,24 @@ static inline unsigned grid_for(size_t total, unsigned block = 256, unsigned cap
 // half-replaced key or share dP / dX / dV / the failure words with the new call.
 #define PSFP_QUIESCE(h) do { const psf_status rw__ = psfp_wait(h); if (rw__ != PSF_OK) return rw__; } while (0)
 
-struct TimingSlot { std::string name; hipEvent_t e0, e1; };
+struct TimingSlot { std::string name; Event e0, e1; };
 
-struct psfp_handle {
+// The work buffers of a batch: a struct of their own, so that ensure_batch releases them in one assignment before it allocates the larger ones
+// (released in this order).  Bcap = 0: nothing usable, the next call starts over.
+struct psfp_batch {
+  DevArr<double> dDt, dX; DevArr<int32_t> dP;
+  DevArr<int8_t> dP8;                         // three digit planes of P, [K_pad/16][ld][16] each
+  DevArr<uint64_t> dV;
+  DevArr<int8_t> dZlo, dZhi;
+  DevArr<int8_t> dD8;                         // five digit planes of d_2 2^32 (structured mode), [ldr/16][ld][16] each
+  DevArr<int32_t> dPf; DevArr<int8_t> dP8f;   // scratch of f_a (kept apart from the samp_p intermediates)
+  DevArr<uint64_t> dPart;                     // per-split residues of the int8-MFMA Z_q product
+  DevArr<uint64_t> dU; DevArr<int64_t> dE; DevArr<uint8_t> dOk;
+  size_t Bcap = 0;
+};
+
+struct psfp_handle : psfp_batch {
+  ~psfp_handle() { hp.quiesce(); }            // transport first: the prewarm thread and both call slots' workers are joined before any member is released
   psfp_params prm;
   size_t n, k, mb, w, m;
   uint64_t q, two64, two31;
@@ -62,49 +77,43 @@ struct psfp_handle {
   bool has_pub = false;      // A installed (f_a, check_domain, samp_d work; samp_p needs has_key)
   bool has_R = false;        // R installed (compute_sqrt_sigma_2 can complete the key; samp_p also needs has_pub)
   // key material
-  uint64_t* dA = nullptr;      // n x m
-  int8_t* dR = nullptr;        // mb x ldr
+  DevArr<uint64_t> dA;         // n x m
+  DevArr<int8_t> dR;           // mb x ldr
   size_t ldr = 0;
-  double* dLt = nullptr;       // chunk stream of sqrt(Sigma_2) (structured mode: of L_1, the m_bar x m_bar block)
+  DevArr<double> dLt;          // chunk stream of sqrt(Sigma_2) (structured mode: of L_1, the m_bar x m_bar block)
   size_t M_pad = 0, nbi = 0, nkb = 0;
   // structured sqrt(Sigma_2) (PSFP_FLAG_STRUCTURED_SQRT): x_top = L_1 d_1 - g R d_2, x_bot = h d_2
   bool structured = false;
   size_t mL = 0, nbiL = 0;     // order of the stored triangular factor (m, or m_bar) and its row blocks
-  int8_t* dR8 = nullptr;       // R tile-packed (k_pack_R8: 4 KiB tiles of 64 rows x 64 columns, contiguous) for k_recombine_mfma_big and k_rd2_mfma, mb_pad x ldr
+  DevArr<int8_t> dR8;          // R tile-packed (k_pack_R8: 4 KiB tiles of 64 rows x 64 columns, contiguous) for k_recombine_mfma_big and k_rd2_mfma, mb_pad x ldr
   bool r8_valid = false;       // dR8 follows dR (ensure_R8)
   bool r8_pending = false;     // the pack has been enqueued on r8_stream and is not known to have completed: other streams wait for evR8
-  hipEvent_t evR8 = nullptr; hipStream_t r8_stream = nullptr;
+  Event evR8; hipStream_t r8_stream = nullptr;      // r8_stream: not owned (the stream of the call that packed)
   // compact copies of the key for calls with a handful of preimages, where reading A and R once IS the time of their stages (psf_stream_kernels.hpp):
   // R as two bits per entry (k_recombine_small2; only a {-1, 0, 1} trapdoor has one), A as 32-bit words (k_syndrome_small32; q <= 2^32)
-  uint32_t* dR2 = nullptr; uint32_t* dA32 = nullptr; int* dR2bad = nullptr; int* hR2bad = nullptr; hipEvent_t evSmall = nullptr;
-  uint32_t* dA32T = nullptr;   // A transposed, [coordinate][row], 32-bit: the fused tail of k_trmm_stream_fused (q <= 2^32, n a multiple of 8)
-  uint64_t* dPartF = nullptr; size_t partF_cap = 0;      // its partial residues, [task][row][preimage]
+  DevArr<uint32_t> dR2, dA32; DevArr<int> dR2bad; PinArr<int> hR2bad; Event evSmall;
+  DevArr<uint32_t> dA32T;      // A transposed, [coordinate][row], 32-bit: the fused tail of k_trmm_stream_fused (q <= 2^32, n a multiple of 8)
+  DevArr<uint64_t> dPartF;     // its partial residues, [task][row][preimage] (grown to the call's tasks)
   int small_state = 0;         // 0: stale (the key changed); 1: being built (evSmall); 2: usable; 3: usable, R is not ternary (A32 only)
   double g_const = 0, h_const = 0;
   // gadget tables
-  int32_t* dRng = nullptr;
-  int32_t* dSk = nullptr; double* dGso = nullptr; double* dNorm2 = nullptr; SampleZParams* dSz = nullptr;
-  uint64_t* dGvec = nullptr;
-  int8_t* dA8 = nullptr; int NA = 0; size_t n_pad = 0, K_pad = 0;   // balanced base-256 digit planes of A
+  DevArr<int32_t> dRng;
+  DevArr<int32_t> dSk; DevArr<double> dGso, dNorm2; DevArr<SampleZParams> dSz;
+  DevArr<uint64_t> dGvec;
+  DevArr<int8_t> dA8; int NA = 0; size_t n_pad = 0, K_pad = 0;   // balanced base-256 digit planes of A
   ZqConsts zc;
   std::vector<int64_t> hSk; std::vector<double> hGso;
   SampleZParams szR, szSR;
-  uint32_t* dSzTab = nullptr; uint32_t szF = 0;      // table screen of the rounding sampler (psf_rng.hpp, k_perturb_round_tab); szF = 0: none (wide words, or the table would not fit)
-  // batch work buffers
-  size_t Bcap = 0, ld = 0;
-  double* dDt = nullptr; double* dX = nullptr; int32_t* dP = nullptr; uint64_t* dV = nullptr;
-  int8_t* dZlo = nullptr; int8_t* dZhi = nullptr; size_t mb_pad = 0;
-  int8_t* dP8 = nullptr;                      // three digit planes of P, [K_pad/16][ld][16] each
-  uint64_t* dU = nullptr; int64_t* dE = nullptr; uint8_t* dOk = nullptr;
-  int* dFail = nullptr;                       // four words: [0] sampler failure, [1] some |z| > 127, [2] some |p| >= 2^15 (run_samp_p)
-  int8_t* dD8 = nullptr;                      // five digit planes of d_2 2^32 (structured mode), [ldr/16][ld][16] each
-  int32_t* dPf = nullptr; int8_t* dP8f = nullptr;   // scratch of f_a (kept apart from the samp_p intermediates)
-  uint64_t* dPart = nullptr; int zq_split_cap = 1;   // per-split residues of the int8-MFMA Z_q product
+  DevArr<uint32_t> dSzTab; uint32_t szF = 0;      // table screen of the rounding sampler (psf_rng.hpp, k_perturb_round_tab); szF = 0: none (wide words, or the table would not fit)
+  // batch work buffers: psfp_batch
+  size_t ld = 0, mb_pad = 0;
+  DevArr<int> dFail;                          // four words: [0] sampler failure, [1] some |z| > 127, [2] some |p| >= 2^15 (run_samp_p)
+  int zq_split_cap = 1;                       // K splits dPart has room for
   bool gadget_queue = true;   // task-queue gadget sampler (PSF_GADGET_QUEUE=0: lock-step kernel)
   HostPipe hp;                // host-pointer calls (psfp_samp_p / psfp_samp_p_async and their PSFGPV / ring forms): psf_hostpipe.hpp
   uint32_t normals_ncf = 0;   // layout of dDt after the last samp_p: 0 = chunk stream, else the compact stream with this many column fragments
-  hipStream_t last_stream = nullptr;
-  hipStream_t side = nullptr; hipEvent_t evSide = nullptr;      // psfp_trap_gen: A is computed on this low-priority stream beside the factorisation of Sigma_2
+  hipStream_t last_stream = nullptr;      // not owned (the caller's, or hp.compute)
+  Stream side; Event evSide;      // psfp_trap_gen: A is computed on this low-priority stream beside the factorisation of Sigma_2
   // timing
   bool timing = false;
   std::vector<TimingSlot> slots;
@@ -123,10 +132,10 @@ static void ensure_small_copies(psfp_handle* h, hipStream_t st) {
   }
   const size_t ng = h->ldr / 16;
   if (!h->dR2) {
-    if (hipMalloc(&h->dR2, h->mb * ng * sizeof(uint32_t)) != hipSuccess || hipMalloc(&h->dR2bad, sizeof(int)) != hipSuccess ||
-        hipHostMalloc(&h->hR2bad, sizeof(int)) != hipSuccess || hipEventCreateWithFlags(&h->evSmall, hipEventDisableTiming) != hipSuccess) { h->small_state = 4; return; }
-    if (h->q <= (1ull << 32) && hipMalloc(&h->dA32, h->n * h->m * sizeof(uint32_t)) != hipSuccess) { h->small_state = 4; return; }
-    if (h->q <= (1ull << 32) && h->n % 8 == 0 && hipMalloc(&h->dA32T, h->n * h->m * sizeof(uint32_t)) != hipSuccess) { h->dA32T = nullptr; (void)hipGetLastError(); }
+    if (h->dR2.alloc(h->mb * ng) != hipSuccess || h->dR2bad.alloc(1) != hipSuccess ||
+        h->hR2bad.alloc(1) != hipSuccess || hipEventCreateWithFlags(h->evSmall.put(), hipEventDisableTiming) != hipSuccess) { h->small_state = 4; return; }
+    if (h->q <= (1ull << 32) && h->dA32.alloc(h->n * h->m) != hipSuccess) { h->small_state = 4; return; }
+    if (h->q <= (1ull << 32) && h->n % 8 == 0 && h->dA32T.alloc(h->n * h->m) != hipSuccess) (void)hipGetLastError();
   }
   hipMemsetAsync(h->dR2bad, 0, sizeof(int), st);
   hipLaunchKernelGGL(k_pack_R2, dim3(grid_for(h->mb * ng, 256, 256 * 32)), dim3(256), 0, st, h->dR, h->ldr, h->mb, h->dR2, h->dR2bad);
@@ -146,7 +155,7 @@ static void ensure_R8(psfp_handle* h, hipStream_t st) {
     hipLaunchKernelGGL(k_pack_R8, dim3(grid_for(h->mb_pad * h->ldr, 256, 256 * 64)), dim3(256), 0, st, h->dR, h->ldr, h->mb, h->w, h->mb_pad, h->ldr, h->dR8);
     h->r8_valid = true;
     h->r8_pending = false;
-    if (!h->evR8 && hipEventCreateWithFlags(&h->evR8, hipEventDisableTiming) != hipSuccess) { h->evR8 = nullptr; hipStreamSynchronize(st); return; }
+    if (!h->evR8 && hipEventCreateWithFlags(h->evR8.put(), hipEventDisableTiming) != hipSuccess) { h->evR8.detach(); hipStreamSynchronize(st); return; }
     if (hipEventRecord(h->evR8, st) != hipSuccess) { hipStreamSynchronize(st); return; }
     h->r8_pending = true; h->r8_stream = st;
     return;
@@ -157,14 +166,6 @@ static void ensure_R8(psfp_handle* h, hipStream_t st) {
 }
 
 static size_t gadget_lds_bytes(size_t k) { return k * k * 8 + k * 8 + k * sizeof(SampleZParams) + k * k * 4 + k * 256 * 4; }
-
-static void free_batch(psfp_handle* h) {
-  hipFree(h->dDt); hipFree(h->dX); hipFree(h->dP); hipFree(h->dP8); hipFree(h->dV); hipFree(h->dZlo); hipFree(h->dZhi); hipFree(h->dD8);
-  h->dDt = h->dX = nullptr; h->dP = nullptr; h->dP8 = nullptr; h->dV = nullptr; h->dZlo = h->dZhi = nullptr; h->dD8 = nullptr;
-  hipFree(h->dPf); hipFree(h->dP8f); hipFree(h->dPart); hipFree(h->dU); hipFree(h->dE); hipFree(h->dOk);
-  h->dPf = nullptr; h->dP8f = nullptr; h->dPart = nullptr; h->dU = nullptr; h->dE = nullptr; h->dOk = nullptr;
-  h->Bcap = 0;
-}
 
 // K splits of the Z_q product for `ncols` preimages: at most 256 K-steps each (int32 exactness of the digit-class sums), and enough workgroups to
 // fill the chip -- a single call (one preimage) has 8 row tiles x 1 column tile, so its K range is cut as finely as 4 K-steps per split.  The
@@ -192,32 +193,32 @@ static int zq_split_cap_for(const psfp_handle* h, size_t ld) {
 static psf_status ensure_batch(psfp_handle* h, size_t B) {
   if (B <= h->Bcap) return PSF_OK;
   HIP_TRY(hipDeviceSynchronize());
-  free_batch(h);
+  static_cast<psfp_batch&>(*h) = psfp_batch{};      // every buffer of the smaller batch is released before the first of the larger is allocated
   const size_t ld = round_up(B, TR_BN);
   h->ld = ld;
   if (!(h->prm.flags & PSFP_FLAG_NO_PERTURB)) {
-    HIP_TRY(hipMalloc(&h->dDt, (ld / TR_BN * h->nkb * TR_CHUNK + TS_SLACK_DOUBLES) * sizeof(double)));   // slack: k_trmm_stream reads past the diagonal
-    HIP_TRY(hipMalloc(&h->dX, h->M_pad * ld * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->dP, h->M_pad * ld * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&h->dP8, 3 * h->K_pad * ld));
-    HIP_TRY(hipMalloc(&h->dV, h->n * ld * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc(&h->dZlo, h->ldr * ld + RS_SLACK_SLOTS * 128 * ld));      // [ldr/16][ld][16] (+ the slots k_recombine_wg's ring reads past the last K group)
-    HIP_TRY(hipMalloc(&h->dZhi, h->ldr * ld + RS_SLACK_SLOTS * 128 * ld));
+    HIP_TRY(h->dDt.alloc(ld / TR_BN * h->nkb * TR_CHUNK + TS_SLACK_DOUBLES));   // slack: k_trmm_stream reads past the diagonal
+    HIP_TRY(h->dX.alloc(h->M_pad * ld));
+    HIP_TRY(h->dP.alloc(h->M_pad * ld));
+    HIP_TRY(h->dP8.alloc(3 * h->K_pad * ld));
+    HIP_TRY(h->dV.alloc(h->n * ld));
+    HIP_TRY(h->dZlo.alloc(h->ldr * ld + RS_SLACK_SLOTS * 128 * ld));      // [ldr/16][ld][16] (+ the slots k_recombine_wg's ring reads past the last K group)
+    HIP_TRY(h->dZhi.alloc(h->ldr * ld + RS_SLACK_SLOTS * 128 * ld));
     HIP_TRY(hipMemset(h->dZlo, 0, h->ldr * ld));
     HIP_TRY(hipMemset(h->dZhi, 0, h->ldr * ld));
     HIP_TRY(hipMemset(h->dP, 0, h->M_pad * ld * sizeof(int32_t)));
     if (h->structured) {
-      HIP_TRY(hipMalloc(&h->dD8, kFixPlanes * h->ldr * ld));
+      HIP_TRY(h->dD8.alloc(kFixPlanes * h->ldr * ld));
       HIP_TRY(hipMemset(h->dD8, 0, kFixPlanes * h->ldr * ld));
     }
   }
-  HIP_TRY(hipMalloc(&h->dPf, h->M_pad * ld * sizeof(int32_t)));
-  HIP_TRY(hipMalloc(&h->dP8f, 3 * h->K_pad * ld));
+  HIP_TRY(h->dPf.alloc(h->M_pad * ld));
+  HIP_TRY(h->dP8f.alloc(3 * h->K_pad * ld));
   h->zq_split_cap = zq_split_cap_for(h, ld);      // K splits of the Z_q product (zq_plan)
-  HIP_TRY(hipMalloc(&h->dPart, (size_t)h->zq_split_cap * h->n_pad * ld * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc(&h->dU, B * h->n * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc(&h->dE, B * h->m * sizeof(int64_t)));
-  HIP_TRY(hipMalloc(&h->dOk, B));
+  HIP_TRY(h->dPart.alloc((size_t)h->zq_split_cap * h->n_pad * ld));
+  HIP_TRY(h->dU.alloc(B * h->n));
+  HIP_TRY(h->dE.alloc(B * h->m));
+  HIP_TRY(h->dOk.alloc(B));
   // The clears above run on the null stream; the calls that follow may run on non-blocking streams (the host-pointer path's compute stream, a caller's stream), which do
   // not wait for it -- without this barrier a clear could land AFTER the first kernels had written the same buffer (found in round 5 by tools/host_vs_device_fuzz.py: one
   // whole-batch mismatch in 240 000 first calls, small keys whose product finishes within the clear of dP)
@@ -231,17 +232,13 @@ struct ScopedTimer {
   ScopedTimer(psfp_handle* h_, hipStream_t st_, const char* name) : h(h_), st(st_), on(h_->timing) {
     if (!on) return;
     TimingSlot s; s.name = name;
-    hipEventCreate(&s.e0); hipEventCreate(&s.e1);
+    hipEventCreate(s.e0.put()); hipEventCreate(s.e1.put());
     hipEventRecord(s.e0, st);
-    h->slots.push_back(s);
+    h->slots.push_back(std::move(s));
     idx = h->slots.size() - 1;
   }
   ~ScopedTimer() { if (on) hipEventRecord(h->slots[idx].e1, st); }
 };
-static void clear_slots(psfp_handle* h) {
-  for (auto& s : h->slots) { hipEventDestroy(s.e0); hipEventDestroy(s.e1); }
-  h->slots.clear();
-}
 
 #ifdef TRMM_CLOCK_PROBE
 extern "C" void psf_debug_trmm_clk(unsigned long long* out, int reset) {
@@ -413,31 +410,31 @@ static psf_status psfp_init(psfp_handle* h, const psfp_params* prm) {
     h->zc.inv_q = 1.0 / (double)gp.q;
     for (int c = 0; c < 12; ++c) { h->zc.pw[c] = pw; h->zc.pwd[c] = (double)pw; pw = mulmod_u64(pw, 256 % gp.q, gp.q); }
   }
-  HIP_TRY(hipMalloc(&h->dA8, (size_t)h->NA * h->n_pad * h->K_pad));
+  HIP_TRY(h->dA8.alloc((size_t)h->NA * h->n_pad * h->K_pad));
   h->szR = make_sample_z_params(prm->r);
   {
     std::vector<uint32_t> T;
     uint32_t F = 0;
     if (!(prm->flags & PSFP_FLAG_NO_PERTURB) && build_sz_table(h->szR, T, &F)) {
-      HIP_TRY(hipMalloc(&h->dSzTab, T.size() * sizeof(uint32_t)));
+      HIP_TRY(h->dSzTab.alloc(T.size()));
       HIP_TRY(hipMemcpy(h->dSzTab, T.data(), T.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
       h->szF = F;
     }
   }
   h->szSR = make_sample_z_params(prm->s * prm->r);                    // mp_perturbation.rs:266
-  HIP_TRY(hipMalloc(&h->dA, h->n * h->m * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc(&h->dR, h->mb_pad * h->ldr + 4096));      // (+ what k_recombine_wg's ring reads past the last row)
+  HIP_TRY(h->dA.alloc(h->n * h->m));
+  HIP_TRY(h->dR.alloc(h->mb_pad * h->ldr + 4096));      // (+ what k_recombine_wg's ring reads past the last row)
   HIP_TRY(hipMemset(h->dR, 0, h->mb_pad * h->ldr));
-  if (!(prm->flags & PSFP_FLAG_NO_PERTURB)) HIP_TRY(hipMalloc(&h->dLt, (tr_total_chunks(h->nbiL) * TR_CHUNK + TS_SLACK_DOUBLES) * sizeof(double)));
-  if (!(prm->flags & PSFP_FLAG_NO_PERTURB)) HIP_TRY(hipMalloc(&h->dR8, h->mb_pad * h->ldr));      // tile-packed copy of R: k_recombine_mfma_big, k_rd2_mfma
-  HIP_TRY(hipMalloc(&h->dFail, 4 * sizeof(int)));
+  if (!(prm->flags & PSFP_FLAG_NO_PERTURB)) HIP_TRY(h->dLt.alloc(tr_total_chunks(h->nbiL) * TR_CHUNK + TS_SLACK_DOUBLES));
+  if (!(prm->flags & PSFP_FLAG_NO_PERTURB)) HIP_TRY(h->dR8.alloc(h->mb_pad * h->ldr));      // tile-packed copy of R: k_recombine_mfma_big, k_rd2_mfma
+  HIP_TRY(h->dFail.alloc(4));
   HIP_TRY(hipMemset(h->dFail, 0, 4 * sizeof(int)));
   {
     int lo_prio = 0, hi_prio = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
-    HIP_TRY(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, lo_prio));
+    HIP_TRY(hipStreamCreateWithPriority(h->side.put(), hipStreamNonBlocking, lo_prio));
   }
-  HIP_TRY(hipEventCreateWithFlags(&h->evSide, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(h->evSide.put(), hipEventDisableTiming));
   // gadget part of the trapdoor: (S, S~) of mp_perturbation.rs:233-234, block form
   h->hSk = short_basis_gadget_block(gp);
   std::vector<double> norm2;
@@ -455,14 +452,14 @@ static psf_status psfp_init(psfp_handle* h, const psfp_params* prm) {
     }
     rng[col] = glo; rng[h->k + col] = ghi; rng[2 * h->k + col] = slo; rng[3 * h->k + col] = shi;
   }
-  HIP_TRY(hipMalloc(&h->dRng, rng.size() * sizeof(int32_t)));
+  HIP_TRY(h->dRng.alloc(rng.size()));
   HIP_TRY(hipMemcpy(h->dRng, rng.data(), rng.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   const auto gvec = gen_gadget_vec_mod(h->k, gp.base, gp.q);
-  HIP_TRY(hipMalloc(&h->dSk, sk32.size() * sizeof(int32_t)));
-  HIP_TRY(hipMalloc(&h->dGso, h->hGso.size() * sizeof(double)));
-  HIP_TRY(hipMalloc(&h->dNorm2, h->k * sizeof(double)));
-  HIP_TRY(hipMalloc(&h->dSz, h->k * sizeof(SampleZParams)));
-  HIP_TRY(hipMalloc(&h->dGvec, h->k * sizeof(uint64_t)));
+  HIP_TRY(h->dSk.alloc(sk32.size()));
+  HIP_TRY(h->dGso.alloc(h->hGso.size()));
+  HIP_TRY(h->dNorm2.alloc(h->k));
+  HIP_TRY(h->dSz.alloc(h->k));
+  HIP_TRY(h->dGvec.alloc(h->k));
   HIP_TRY(hipMemcpy(h->dSk, sk32.data(), sk32.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->dGso, h->hGso.data(), h->hGso.size() * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->dNorm2, norm2.data(), h->k * sizeof(double), hipMemcpyHostToDevice));
@@ -507,19 +504,6 @@ static void hp_prewarm(psfp_handle* h) {
 void psfp_destroy(psfp_handle* h) {
   if (!h) return;
   hipSetDevice(h->prm.device);
-  hp_release(h->hp);
-  free_batch(h);
-  clear_slots(h);
-  if (h->side) hipStreamDestroy(h->side);
-  if (h->evSide) hipEventDestroy(h->evSide);
-  hipFree(h->dA); hipFree(h->dR); hipFree(h->dLt); hipFree(h->dR8); hipFree(h->dR2); hipFree(h->dA32); hipFree(h->dR2bad); hipFree(h->dA32T); hipFree(h->dPartF);
-  if (h->hR2bad) hipHostFree(h->hR2bad);
-  if (h->evSmall) hipEventDestroy(h->evSmall);
-  if (h->evR8) hipEventDestroy(h->evR8);
-  hipFree(h->dFail);
-  hipFree(h->dA8); hipFree(h->dSzTab);
-  hipFree(h->dRng);
-  hipFree(h->dSk); hipFree(h->dGso); hipFree(h->dNorm2); hipFree(h->dSz); hipFree(h->dGvec);
   delete h;
 }
 
@@ -568,26 +552,21 @@ static psf_status build_sqrt_sigma2_stream(psfp_handle* h, double nf_r2, double 
     if (a > ws_doubles) ws_doubles = a;
     if (b > ws_doubles) ws_doubles = b;
   }
-  double *dPn[2] = {nullptr, nullptr}, *dLi = nullptr, *dWs = nullptr; int* dinfo = nullptr;
-  hipStream_t sm = nullptr, ss = nullptr, sd = nullptr;               // factorisation / Sigma_2 panels (one panel ahead) / the diagonal blocks' chain (look-ahead)
-  hipEvent_t evSig[2] = {nullptr, nullptr}, evPack[2] = {nullptr, nullptr}, evHead = nullptr, evDiag = nullptr;
+  DevArr<double> dPn[2], dLi, dWs; DevArr<int> dinfo;                 // (released on every return, in reverse: streams, events, buffers)
+  Event evSig[2], evPack[2], evHead, evDiag;
+  Stream sm, ss, sd;                                                  // factorisation / Sigma_2 panels (one panel ahead) / the diagonal blocks' chain (look-ahead)
   GemmWorkspace w, w2;                                                // the in-panel products have K = 128: never cut
   bool lookahead = true;
   if (const char* e = psf_exp_env("PSF_CHOL_LOOKAHEAD")) lookahead = std::atoi(e) != 0;
-  auto cleanup = [&]() {
-    for (hipStream_t st : {sm, ss, sd}) if (st) hipStreamDestroy(st);
-    for (hipEvent_t ev : {evSig[0], evSig[1], evPack[0], evPack[1], evHead, evDiag}) if (ev) hipEventDestroy(ev);
-    hipFree(dPn[0]); hipFree(dPn[1]); hipFree(dLi); hipFree(dWs); hipFree(dinfo);
-  };
   bool ok = gemm_prepare() == hipSuccess && prepare_chol_diag() &&
-            hipMalloc(&dPn[0], prow * PW * sizeof(double)) == hipSuccess && hipMalloc(&dPn[1], prow * PW * sizeof(double)) == hipSuccess &&
-            hipMalloc(&dLi, 2 * CH_NB * CH_NB * sizeof(double)) == hipSuccess && (!ws_doubles || hipMalloc(&dWs, ws_doubles * sizeof(double)) == hipSuccess) &&
-            hipMalloc(&dinfo, sizeof(int)) == hipSuccess && hipMemset(dinfo, 0, sizeof(int)) == hipSuccess &&
+            dPn[0].alloc(prow * PW) == hipSuccess && dPn[1].alloc(prow * PW) == hipSuccess &&
+            dLi.alloc(2 * CH_NB * CH_NB) == hipSuccess && (!ws_doubles || dWs.alloc(ws_doubles) == hipSuccess) &&
+            dinfo.alloc(1) == hipSuccess && hipMemset(dinfo, 0, sizeof(int)) == hipSuccess &&
             hipMemset(dPn[0], 0, prow * PW * sizeof(double)) == hipSuccess && hipMemset(dPn[1], 0, prow * PW * sizeof(double)) == hipSuccess;
-  for (hipStream_t* st : {&sm, &ss, &sd}) ok = ok && hipStreamCreateWithFlags(st, hipStreamNonBlocking) == hipSuccess;
-  for (hipEvent_t* ev : {&evSig[0], &evSig[1], &evPack[0], &evPack[1], &evHead, &evDiag}) ok = ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
-  if (!ok) { cleanup(); return PSF_ERR_HIP; }
-  if (hipStreamSynchronize(nullptr) != hipSuccess) { cleanup(); return PSF_ERR_HIP; }      // R, the dense Sigma_2 (and k_pack_R8) were produced on the default stream (not a device-wide wait: psfp_trap_gen computes A on a side stream meanwhile)
+  for (Stream* st : {&sm, &ss, &sd}) ok = ok && hipStreamCreateWithFlags(st->put(), hipStreamNonBlocking) == hipSuccess;
+  for (Event* ev : {&evSig[0], &evSig[1], &evPack[0], &evPack[1], &evHead, &evDiag}) ok = ok && hipEventCreateWithFlags(ev->put(), hipEventDisableTiming) == hipSuccess;
+  if (!ok) return PSF_ERR_HIP;
+  if (hipStreamSynchronize(nullptr) != hipSuccess) return PSF_ERR_HIP;      // R, the dense Sigma_2 (and k_pack_R8) were produced on the default stream (not a device-wide wait: psfp_trap_gen computes A on a side stream meanwhile)
   // Sigma_2 restricted to panel J (rows off.., columns off..off+255), dense with leading dimension 256; it does not depend on the factorisation, so it
   // is assembled one panel ahead on its own stream into the other of two panel buffers
   auto sigma_panel = [&](int J) {
@@ -673,7 +652,6 @@ static psf_status build_sqrt_sigma2_stream(psfp_handle* h, double nf_r2, double 
   if (ce == hipSuccess) ce = hipGetLastError();
   int info = -1;
   if (ce == hipSuccess) ce = hipMemcpy(&info, dinfo, sizeof(int), hipMemcpyDeviceToHost);
-  cleanup();
   if (ce != hipSuccess) return PSF_ERR_HIP;
   return info != 0 ? PSF_ERR_NOT_PD : PSF_OK;                         // mp_perturbation.rs:109-110
 }
@@ -1222,10 +1200,7 @@ static void prepare_samp_p(psfp_handle* h, hipStream_t st, SampPlan& p) {
   if (p.small_copies) ensure_small_copies(h, st);
   if (p.tail) {
     const size_t need = (size_t)p.tail_ntask * h->n * 2;
-    if (need > h->partF_cap) {
-      hipFree(h->dPartF); h->dPartF = nullptr; h->partF_cap = 0;
-      if (hipMalloc(&h->dPartF, need * sizeof(uint64_t)) == hipSuccess) h->partF_cap = need; else (void)hipGetLastError();
-    }
+    if (h->dPartF.grow(need) != hipSuccess) (void)hipGetLastError();
     p.tail = h->dPartF != nullptr;      // (no room: the syndrome stage takes the Z_q product)
   }
   if (p.r8) ensure_R8(h, st);
@@ -1430,7 +1405,7 @@ psf_status psfp_samp_p_dev(psfp_handle* h, uint64_t seed, uint64_t first_index, 
   PSFP_QUIESCE(h);
   psf_status rc = ensure_batch(h, B);
   if (rc != PSF_OK) return rc;
-  if (h->timing) clear_slots(h);       // once per public call: the slices of a host-pointer call add up in psfp_get_timing
+  if (h->timing) h->slots.clear();       // once per public call: the slices of a host-pointer call add up in psfp_get_timing
   return run_samp_p(h, seed, first_index, B, d_u, d_e, (hipStream_t)stream, SampCall{});
 }
 
@@ -1446,7 +1421,7 @@ psf_status psfp_samp_p_dev_many(psfp_handle* h, size_t count, const uint64_t* se
   PSFP_QUIESCE(h);
   psf_status rc = ensure_batch(h, B);
   if (rc != PSF_OK) return rc;
-  if (h->timing) clear_slots(h);
+  if (h->timing) h->slots.clear();
   hipStream_t st = (hipStream_t)stream;
   SampCall call;
   for (size_t i = 0; i < count && rc == PSF_OK; ++i) {
@@ -1467,7 +1442,7 @@ static HostCall host_call(psfp_handle* h, size_t B, const int* extra_flags, bool
 // its resize step: the batch buffers for B rows; the timing slots of the call before go (once per public call: the slices of a host-pointer call add up in psfp_get_timing)
 static psf_status host_resize(psfp_handle* h, size_t B) {
   const psf_status rc = ensure_batch(h, B);
-  if (rc == PSF_OK && h->timing) clear_slots(h);
+  if (rc == PSF_OK && h->timing) h->slots.clear();
   return rc;
 }
 
@@ -1521,7 +1496,7 @@ static psf_status samp_p_host(psfp_handle* h, uint64_t seed, uint64_t first_inde
     rc = ensure_batch(h, B);
     if (rc != PSF_OK) return rc;
     if (!call.whole_batch && B * (h->n + h->m) * 8 <= SIO_MAX_BYTES && !psf_exp_env("PSF_HOST_STRAIGHT")) {
-      if (h->timing) clear_slots(h);
+      if (h->timing) h->slots.clear();
       int fl[1] = {0};
       rc = sio_call(h->hp, B * h->n, B * h->m, u, e, h->dU, h->dE, h->dFail, nullptr, 0, fl,
                     [&]() { return run_samp_p(h, seed, first_index, B, h->dU, h->dE, nullptr, call); });
@@ -1529,7 +1504,7 @@ static psf_status samp_p_host(psfp_handle* h, uint64_t seed, uint64_t first_inde
       return fl[0] ? PSF_ERR_SAMPLER : PSF_OK;
     }
     HIP_TRY(hipMemcpy(h->dU, u, B * h->n * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (h->timing) clear_slots(h);
+    if (h->timing) h->slots.clear();
     rc = run_samp_p(h, seed, first_index, B, h->dU, h->dE, nullptr, call);
     if (rc != PSF_OK) return rc;
     rc = psfp_last_status(h);
@@ -1761,7 +1736,7 @@ psf_status psfp_get_last_plan(const psfp_handle* h, int* fields, size_t count) {
 psf_status psfp_enable_timing(psfp_handle* h, int on) {
   if (!h) return PSF_ERR_PARAM;
   h->timing = on != 0;
-  if (!on) clear_slots(h);
+  if (!on) h->slots.clear();
   return PSF_OK;
 }
 
