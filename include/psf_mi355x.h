@@ -344,6 +344,49 @@ psf_status psf_ntt_image_from_fips203_dev(int device, size_t count, const void* 
 psf_status psf_ntt_image_to_fips203_dev(int device, size_t count, const uint32_t* d_hat, void* d_fhat, int io_bits, void* stream);
 psf_status psf_ntt_image_from_fips203(int device, size_t count, const uint64_t* fhat, uint32_t* hat);
 psf_status psf_ntt_image_to_fips203(int device, size_t count, const uint32_t* hat, uint64_t* fhat);
+/* ML-KEM (FIPS 203), batched, bytes in and bytes out.  The library draws NO randomness here: d, z and m are the caller's 32-byte strings, and the
+ * algorithms offered are the "internal" ones -- ML-KEM.KeyGen_internal(d, z) (Algorithm 16), ML-KEM.Encaps_internal(ek, m) (Algorithm 17) and
+ * ML-KEM.Decaps_internal(dk, c) (Algorithm 18) -- which is what makes every output a function of the inputs that a test can compare.  A caller
+ * implements Algorithms 19 to 21 by drawing d, z and m from an approved random-bit generator and running the two input checks below first
+ * (INTEGRATION.md).  The value of a parameter set is its k; (eta1, eta2, du, dv) = (3, 2, 10, 4), (2, 2, 10, 4), (2, 2, 11, 5).
+ *   sizes in bytes:  ek 384 k + 32 (800 / 1184 / 1568), dk 768 k + 96 (1632 / 2400 / 3168), ct 32 (du k + dv) (768 / 1088 / 1568), ss 32.
+ * Batches are contiguous: instance c of a buffer is at base + c * size.  Type checks are implicit in these fixed sizes.
+ *   keygen   (rho, sigma) = G(d || byte(k)); (ek, dk_pke) = K-PKE.KeyGen; dk = dk_pke || ek || H(ek) || z.
+ *   encaps   (K, r) = G(m || H(ek)); c = K-PKE.Encrypt(ek, m, r).  ss = K.
+ *   decaps   m' = K-PKE.Decrypt(dk[0 : 384 k], c); (K', r') = G(m' || dk[768 k + 32 : 768 k + 64]); K_bar = J(dk[768 k + 64 : 768 k + 96] || c);
+ *            c' = K-PKE.Encrypt(dk[384 k : 768 k + 32], m', r'); ss = K' if c = c', else K_bar.  The comparison reads every byte of c and c', K_bar
+ *            is always computed, and the selection is mask arithmetic: nothing in this layer branches on secret data (SampleNTT's rejection loop
+ *            runs on the public rho only).
+ *   check_ek the modulus check of section 7.2: ok[c] = 1 exactly when every 12-bit field of ek_c[0 : 384 k] is below q, else 0.
+ *   check_dk the hash check of section 7.3: ok[c] = 1 exactly when H(dk_c[384 k : 768 k + 32]) = dk_c[768 k + 32 : 768 k + 64], else 0.
+ * psf_mlkem_workspace_bytes gives the bytes of d_ws an operation needs for `count` instances (op: keygen / encaps / decaps / check; 0 for check): a
+ * multiple of 256, monotone in count.  Secret intermediates (s, e, y, e1, e2, m', r', K', the images of the secret key) exist only there, and the
+ * last thing each entry point queues on `stream` sets those bytes of d_ws to zero.
+ * Device forms: ordered on `stream`, nothing allocated, never synchronising.  Byte buffers need no alignment; d_ws must be 256-byte aligned.
+ * d_fail is a device int (may be NULL, never cleared by the call), OR-ed with 1 when a SampleNTT reaches its cap of 8 blocks.
+ * PSF_ERR_PARAM, in this order: an unknown param (or op); a NULL data pointer with count > 0; a byte count that overflows size_t; d_ws NULL or
+ * misaligned, or ws_bytes below the required size; an output range that overlaps an input, another output or the workspace.  count = 0 is PSF_OK.
+ * More than 2^31 - 1 instances in one call is PSF_ERR_UNSUPPORTED.  Every check runs before the first HIP call; nothing is launched or written on an
+ * error.  A valid call without a device is PSF_ERR_HIP (no CPU fallback).
+ * Host forms: the same arguments without workspace, flag and stream; they allocate per call, run on the device and return PSF_ERR_SAMPLER if the
+ * flag was raised. */
+enum { PSF_MLKEM_512 = 2, PSF_MLKEM_768 = 3, PSF_MLKEM_1024 = 4 };
+enum { PSF_MLKEM_OP_KEYGEN = 0, PSF_MLKEM_OP_ENCAPS = 1, PSF_MLKEM_OP_DECAPS = 2, PSF_MLKEM_OP_CHECK = 3 };
+psf_status psf_mlkem_sizes(int param, size_t* ek, size_t* dk, size_t* ct, size_t* ss);
+psf_status psf_mlkem_workspace_bytes(int param, size_t count, int op, size_t* bytes);
+psf_status psf_mlkem_keygen_dev(int device, int param, size_t count, const uint8_t* d_d, const uint8_t* d_z, uint8_t* d_ek, uint8_t* d_dk, void* d_ws, size_t ws_bytes,
+                                int* d_fail, void* stream);
+psf_status psf_mlkem_encaps_dev(int device, int param, size_t count, const uint8_t* d_ek, const uint8_t* d_m, uint8_t* d_ss, uint8_t* d_ct, void* d_ws, size_t ws_bytes,
+                                int* d_fail, void* stream);
+psf_status psf_mlkem_decaps_dev(int device, int param, size_t count, const uint8_t* d_dk, const uint8_t* d_ct, uint8_t* d_ss, void* d_ws, size_t ws_bytes, int* d_fail,
+                                void* stream);
+psf_status psf_mlkem_check_ek_dev(int device, int param, size_t count, const uint8_t* d_ek, uint8_t* d_ok, void* stream);
+psf_status psf_mlkem_check_dk_dev(int device, int param, size_t count, const uint8_t* d_dk, uint8_t* d_ok, void* stream);
+psf_status psf_mlkem_keygen(int device, int param, size_t count, const uint8_t* d, const uint8_t* z, uint8_t* ek, uint8_t* dk);
+psf_status psf_mlkem_encaps(int device, int param, size_t count, const uint8_t* ek, const uint8_t* m, uint8_t* ss, uint8_t* ct);
+psf_status psf_mlkem_decaps(int device, int param, size_t count, const uint8_t* dk, const uint8_t* ct, uint8_t* ss);
+psf_status psf_mlkem_check_ek(int device, int param, size_t count, const uint8_t* ek, uint8_t* ok);
+psf_status psf_mlkem_check_dk(int device, int param, size_t count, const uint8_t* dk, uint8_t* ok);
 /* rot_minus_matrix (rotation_matrix.rs:85-96): mat[rows x cols] -> out[rows x rows*cols] */
 psf_status psf_rot_minus_matrix(const int64_t* mat, size_t rows, size_t cols, int64_t* out);
 

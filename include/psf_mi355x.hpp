@@ -95,6 +95,73 @@ inline void ntt_image_to_fips203_dev(int device, size_t count, const uint32_t* d
   check(psf_ntt_image_to_fips203_dev(device, count, d_hat, d_fhat, io_bits, stream), "ntt_image_to_fips203_dev");
 }
 
+// ---- ML-KEM, batched (psf_mlkem_*; sizes, the workspace and the rules in psf_mi355x.h).  `param` is PSF_MLKEM_512 / _768 / _1024 --------------------
+struct MlKemSizes { size_t ek, dk, ct, ss; };
+inline MlKemSizes mlkem_sizes(int param) {
+  MlKemSizes s{};
+  check(psf_mlkem_sizes(param, &s.ek, &s.dk, &s.ct, &s.ss), "mlkem_sizes");
+  return s;
+}
+inline size_t mlkem_workspace_bytes(int param, size_t count, int op) {
+  size_t bytes = 0;
+  check(psf_mlkem_workspace_bytes(param, count, op, &bytes), "mlkem_workspace_bytes");
+  return bytes;
+}
+inline void mlkem_keygen_dev(int device, int param, size_t count, const uint8_t* d_d, const uint8_t* d_z, uint8_t* d_ek, uint8_t* d_dk, void* d_ws, size_t ws_bytes,
+                             int* d_fail = nullptr, void* stream = nullptr) {
+  check(psf_mlkem_keygen_dev(device, param, count, d_d, d_z, d_ek, d_dk, d_ws, ws_bytes, d_fail, stream), "mlkem_keygen_dev");
+}
+inline void mlkem_encaps_dev(int device, int param, size_t count, const uint8_t* d_ek, const uint8_t* d_m, uint8_t* d_ss, uint8_t* d_ct, void* d_ws, size_t ws_bytes,
+                             int* d_fail = nullptr, void* stream = nullptr) {
+  check(psf_mlkem_encaps_dev(device, param, count, d_ek, d_m, d_ss, d_ct, d_ws, ws_bytes, d_fail, stream), "mlkem_encaps_dev");
+}
+inline void mlkem_decaps_dev(int device, int param, size_t count, const uint8_t* d_dk, const uint8_t* d_ct, uint8_t* d_ss, void* d_ws, size_t ws_bytes,
+                             int* d_fail = nullptr, void* stream = nullptr) {
+  check(psf_mlkem_decaps_dev(device, param, count, d_dk, d_ct, d_ss, d_ws, ws_bytes, d_fail, stream), "mlkem_decaps_dev");
+}
+inline void mlkem_check_ek_dev(int device, int param, size_t count, const uint8_t* d_ek, uint8_t* d_ok, void* stream = nullptr) {
+  check(psf_mlkem_check_ek_dev(device, param, count, d_ek, d_ok, stream), "mlkem_check_ek_dev");
+}
+inline void mlkem_check_dk_dev(int device, int param, size_t count, const uint8_t* d_dk, uint8_t* d_ok, void* stream = nullptr) {
+  check(psf_mlkem_check_dk_dev(device, param, count, d_dk, d_ok, stream), "mlkem_check_dk_dev");
+}
+// host buffers, packed: d and z 32 bytes per instance; returns (ek, dk)
+inline std::pair<std::vector<uint8_t>, std::vector<uint8_t>> mlkem_keygen(int device, int param, size_t count, const std::vector<uint8_t>& d, const std::vector<uint8_t>& z) {
+  const MlKemSizes s = mlkem_sizes(param);
+  if (d.size() != count * 32 || z.size() != count * 32) throw PsfError(PSF_ERR_PARAM, "mlkem_keygen");
+  std::vector<uint8_t> ek(count * s.ek), dk(count * s.dk);
+  check(psf_mlkem_keygen(device, param, count, d.data(), z.data(), ek.data(), dk.data()), "mlkem_keygen");
+  return {ek, dk};
+}
+// returns (shared secrets, ciphertexts)
+inline std::pair<std::vector<uint8_t>, std::vector<uint8_t>> mlkem_encaps(int device, int param, size_t count, const std::vector<uint8_t>& ek, const std::vector<uint8_t>& m) {
+  const MlKemSizes s = mlkem_sizes(param);
+  if (ek.size() != count * s.ek || m.size() != count * 32) throw PsfError(PSF_ERR_PARAM, "mlkem_encaps");
+  std::vector<uint8_t> ss(count * s.ss), ct(count * s.ct);
+  check(psf_mlkem_encaps(device, param, count, ek.data(), m.data(), ss.data(), ct.data()), "mlkem_encaps");
+  return {ss, ct};
+}
+inline std::vector<uint8_t> mlkem_decaps(int device, int param, size_t count, const std::vector<uint8_t>& dk, const std::vector<uint8_t>& ct) {
+  const MlKemSizes s = mlkem_sizes(param);
+  if (dk.size() != count * s.dk || ct.size() != count * s.ct) throw PsfError(PSF_ERR_PARAM, "mlkem_decaps");
+  std::vector<uint8_t> ss(count * s.ss);
+  check(psf_mlkem_decaps(device, param, count, dk.data(), ct.data(), ss.data()), "mlkem_decaps");
+  return ss;
+}
+// one byte per instance: 1 = passes
+inline std::vector<uint8_t> mlkem_check_ek(int device, int param, size_t count, const std::vector<uint8_t>& ek) {
+  if (ek.size() != count * mlkem_sizes(param).ek) throw PsfError(PSF_ERR_PARAM, "mlkem_check_ek");
+  std::vector<uint8_t> ok(count);
+  check(psf_mlkem_check_ek(device, param, count, ek.data(), ok.data()), "mlkem_check_ek");
+  return ok;
+}
+inline std::vector<uint8_t> mlkem_check_dk(int device, int param, size_t count, const std::vector<uint8_t>& dk) {
+  if (dk.size() != count * mlkem_sizes(param).dk) throw PsfError(PSF_ERR_PARAM, "mlkem_check_dk");
+  std::vector<uint8_t> ok(count);
+  check(psf_mlkem_check_dk(device, param, count, dk.data(), ok.data()), "mlkem_check_dk");
+  return ok;
+}
+
 // ---- PSFPerturbation (mp_perturbation.rs:57-62, :193-403) -------------------------------------------------------------
 class PSFPerturbation {
  public:
