@@ -1,20 +1,16 @@
 """Batched ML-KEM on the MI355X (tools_amd/mlkem.py, psf_mlkem_*) against the pure-Python model of tests/helpers/mlkem_model.py: KeyGen_internal,
 Encaps_internal and Decaps_internal byte for byte, implicit rejection alone and mixed with valid ciphertexts inside one wave, the two input checks
 per instance, and the buffer rules.  Every comparison is exact equality over every instance; every output sits between guard bytes at a pointer
-one byte past an aligned address; after every call the workspace is all zero and the sampler flag is what it was."""
-import functools
-import random
-
-import numpy as np
+one byte past an aligned address; after every call the workspace is all zero and the sampler flag is what it was.  The harness is
+tests/helpers/mlkem_gpu.py; the aligned paths, the position sweeps and the large batches are tests/test_gpu_mlkem_edges.py and _large.py."""
 import pytest
 
 from tests.helpers import fips203_kpke_model as M
 from tests.helpers import mlkem_model as R
+from tests.helpers.mlkem_gpu import NAMES, Scratch, _out, _put, _run_check, _take, dev_decaps, dev_encaps, dev_keygen, flip, model
 
 pytestmark = pytest.mark.gpu
 
-GUARD, FILL = 64, 0xA5
-NAMES = sorted(M.PARAMS)
 SHAPES = [(n, c) for c in (1, 3) for n in NAMES] + [("ML-KEM-768", 67), ("ML-KEM-512", 259)]
 
 
@@ -28,116 +24,6 @@ def K():
 def torch():
     import torch as t
     return t
-
-
-@functools.lru_cache(maxsize=None)
-def model(name, count):
-    """the model's run of `count` instances from a fixed seed: inputs, keys, ciphertexts and shared secrets (never modified by a test)"""
-    rng = random.Random(1009 * NAMES.index(name) + count)
-    d, z, m = ([rng.randbytes(32) for _ in range(count)] for _ in range(3))
-    keys = [R.keygen_internal(a, b, name) for a, b in zip(d, z)]
-    enc = [R.encaps_internal(ek, mm, name) for (ek, _), mm in zip(keys, m)]
-    for (_, dk), (key, c) in zip(keys[:2], enc[:2]):
-        assert R.decaps_internal(dk, c, name) == key
-    return {"d": d, "z": z, "m": m, "ek": [k[0] for k in keys], "dk": [k[1] for k in keys], "K": [e[0] for e in enc], "c": [e[1] for e in enc]}
-
-
-def _out(torch, nbytes, off=1):
-    buf = torch.full((GUARD + off + nbytes + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-    assert buf.data_ptr() % 16 == 0
-    return buf, buf.data_ptr() + GUARD + off
-
-
-def _take(torch, buf, nbytes, size, what, off=1):
-    """the items of `size` bytes a call wrote, after checking that the guard bytes on both sides are untouched"""
-    torch.cuda.synchronize()
-    host = buf.cpu().numpy()
-    lo = GUARD + off
-    assert (host[:lo] == FILL).all(), (what, "wrote before the output")
-    assert (host[lo + nbytes:] == FILL).all(), (what, "wrote beyond the output")
-    return [bytes(host[lo + i:lo + i + size]) for i in range(0, nbytes, size)]
-
-
-def _put(torch, items, off=1):
-    """the concatenation of `items` on the device, the first byte `off` bytes past a 16-byte boundary; returns (tensor, pointer)"""
-    data = np.frombuffer(b"".join(items), dtype=np.uint8)
-    buf = torch.zeros((16 + data.size + off,), dtype=torch.uint8, device="cuda")
-    buf[off:off + data.size] = torch.from_numpy(data.copy())
-    assert buf.data_ptr() % 16 == 0
-    return buf, buf.data_ptr() + off
-
-
-class Scratch:
-    """the workspace of one call, filled with a non-zero byte, and a sampler flag that starts at `flag`"""
-
-    def __init__(self, torch, K, name, count, op, flag=0):
-        self.torch, self.bytes = torch, K.workspace_bytes(name, count, op)
-        assert self.bytes % 256 == 0 and self.bytes > 0
-        self.ws = torch.full((self.bytes + 256,), 0x5A, dtype=torch.uint8, device="cuda")
-        self.ptr = (self.ws.data_ptr() + 255) // 256 * 256
-        self.start = flag
-        self.flag = torch.full((1,), flag, dtype=torch.int32, device="cuda")
-
-    def check(self, what):
-        self.torch.cuda.synchronize()
-        lo = self.ptr - self.ws.data_ptr()
-        host = self.ws.cpu().numpy()
-        assert not host[lo:lo + self.bytes].any(), (what, "the workspace is not all zero after the call")
-        assert (host[:lo] == 0x5A).all() and (host[lo + self.bytes:] == 0x5A).all(), (what, "wrote outside the workspace")
-        assert int(self.flag.item()) == self.start, (what, "the sampler flag changed")
-
-
-def dev_keygen(torch, K, name, d, z, flag=0):
-    count, sz = len(d), R.sizes(name)
-    (bd, pd), (bz, pz) = _put(torch, d), _put(torch, z)                    # the tensors live until the call has run
-    bek, pek = _out(torch, count * sz["ek"])
-    bdk, pdk = _out(torch, count * sz["dk"])
-    sc = Scratch(torch, K, name, count, "keygen", flag)
-    torch.cuda.synchronize()
-    K.keygen_dev(name, count, pd, pz, pek, pdk, sc.ptr, sc.bytes, d_fail=sc.flag.data_ptr())
-    ek = _take(torch, bek, count * sz["ek"], sz["ek"], (name, count, "ek"))
-    dk = _take(torch, bdk, count * sz["dk"], sz["dk"], (name, count, "dk"))
-    sc.check((name, count, "keygen"))
-    del bd, bz
-    return ek, dk, (bek, pek)
-
-
-def dev_encaps(torch, K, name, ek, m, flag=0, ek_ptr=None):
-    count, sz = len(m), R.sizes(name)
-    keep = None
-    if ek_ptr is None:
-        keep, ek_ptr = _put(torch, ek)
-    bm, pm = _put(torch, m)
-    bss, pss = _out(torch, count * 32)
-    bct, pct = _out(torch, count * sz["ct"])
-    sc = Scratch(torch, K, name, count, "encaps", flag)
-    torch.cuda.synchronize()
-    K.encaps_dev(name, count, ek_ptr, pm, pss, pct, sc.ptr, sc.bytes, d_fail=sc.flag.data_ptr())
-    ss = _take(torch, bss, count * 32, 32, (name, count, "ss"))
-    ct = _take(torch, bct, count * sz["ct"], sz["ct"], (name, count, "ct"))
-    sc.check((name, count, "encaps"))
-    del keep, bm
-    return ss, ct
-
-
-def dev_decaps(torch, K, name, dk, ct, flag=0):
-    count = len(dk)
-    bdk, pdk = _put(torch, dk)
-    bct, pct = _put(torch, ct)
-    bss, pss = _out(torch, count * 32)
-    sc = Scratch(torch, K, name, count, "decaps", flag)
-    torch.cuda.synchronize()
-    K.decaps_dev(name, count, pdk, pct, pss, sc.ptr, sc.bytes, d_fail=sc.flag.data_ptr())
-    ss = _take(torch, bss, count * 32, 32, (name, count, "decaps"))
-    sc.check((name, count, "decaps"))
-    del bdk, bct
-    return ss
-
-
-def flip(c, pos, bit=0):
-    b = bytearray(c)
-    b[pos] ^= 1 << bit
-    return bytes(b)
 
 
 # ---- the three algorithms ----------------------------------------------------------------------------------------------------------------------------
@@ -187,17 +73,6 @@ def test_decaps_of_a_mixed_batch_shares_waves_between_both_cases(K, torch):
 
 
 # ---- the input checks ----------------------------------------------------------------------------------------------------------------------------------
-
-def _run_check(torch, fn, name, items):
-    count = len(items)
-    bin_, pin = _put(torch, items)
-    bok, pok = _out(torch, count)
-    torch.cuda.synchronize()
-    fn(name, count, pin, pok)
-    ok = _take(torch, bok, count, 1, (name, fn.__name__))                 # the guard: bytes of d_ok beyond count are untouched
-    del bin_
-    return [b[0] for b in ok]
-
 
 def test_check_ek_per_instance(K, torch):
     name, count = "ML-KEM-768", 67
