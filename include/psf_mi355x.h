@@ -387,6 +387,85 @@ psf_status psf_mlkem_encaps(int device, int param, size_t count, const uint8_t* 
 psf_status psf_mlkem_decaps(int device, int param, size_t count, const uint8_t* dk, const uint8_t* ct, uint8_t* ss);
 psf_status psf_mlkem_check_ek(int device, int param, size_t count, const uint8_t* ek, uint8_t* ok);
 psf_status psf_mlkem_check_dk(int device, int param, size_t count, const uint8_t* dk, uint8_t* ok);
+/* ML-DSA (FIPS 204, August 2024), batched, bytes in and bytes out: ML-DSA.KeyGen_internal(xi) (Algorithm 6) and ML-DSA.Verify_internal(pk, M', sigma)
+ * (Algorithm 8) for ML-DSA-44, -65 and -87.  Signing is not offered.  The library draws NO randomness: xi is the caller's 32-byte string.  The value
+ * of a parameter set is its number; (k, l, eta, tau, lambda / 4, gamma1, gamma2, beta, omega) = (4, 4, 2, 39, 32, 2^17, (q - 1) / 88, 78, 80),
+ * (6, 5, 4, 49, 48, 2^19, (q - 1) / 32, 196, 55), (8, 7, 2, 60, 64, 2^19, (q - 1) / 32, 120, 75); q = 8380417, n = 256, d = 13.
+ *   sizes in bytes:  pk 32 + 320 k (1312 / 1952 / 2592), sk 128 + 32 ((k + l) bitlen(2 eta) + 13 k) (2560 / 4032 / 4896),
+ *                    sig lambda / 4 + 32 l (1 + bitlen(gamma1 - 1)) + omega + k (2420 / 3309 / 4627).
+ *   keygen   (rho, rho', K) = H(xi || byte(k) || byte(l), 128); A_hat = ExpandA(rho); (s1, s2) = ExpandS(rho'); t = NTT^-1(A_hat o NTT(s1)) + s2;
+ *            (t1, t0) = Power2Round(t); pk = pkEncode(rho, t1); tr = H(pk, 64); sk = skEncode(rho, K, tr, s1, s2, t0).  xi, pk and sk are contiguous:
+ *            instance c at base + c * size.  rho', s1, s2, t, t0 and the images of A_hat exist only in d_ws (K goes straight into sk), and the last
+ *            thing the call queues on `stream` sets those bytes of d_ws to zero.
+ *   verify   Algorithm 8.  Key c is at d_pk + c * pk_stride; pk_stride = 0 means one key for all instances (A_hat and tr are then formed once),
+ *            otherwise pk_stride >= the pk size.  Messages have one length per call: instance c's msg_len bytes are at d_msg + c * msg_stride.
+ *            msg_kind = PSF_MLDSA_MSG_BYTES: the bytes are M' and mu = H(tr || M', 64) -- the caller formats M' = 0 || |ctx| || ctx || M for
+ *            Algorithm 3; PSF_MLDSA_MSG_MU: msg_len must be 64, the bytes are mu itself, and tr is not computed.  Signatures are contiguous.
+ *            d_ok[c] is 1 or 0.  d_why (may be NULL) gets an OR of
+ *              PSF_MLDSA_WHY_HINT  HintBitUnpack returns bottom: a count byte below the running index or above omega, indices inside one polynomial
+ *                                  not strictly increasing, or a non-zero byte after the last index;
+ *              PSF_MLDSA_WHY_NORM  ||z||_inf >= gamma1 - beta, evaluated from the signature bytes whatever the hint says;
+ *              PSF_MLDSA_WHY_HASH  c~' != c~; also set whenever WHY_HINT is, and no w1' is formed from a malformed hint;
+ *            and ok = (why == 0).  Nothing in verification is secret: its workspace is NOT cleared and needs no clearing.
+ * psf_mldsa_workspace_bytes gives the bytes of d_ws an operation needs for `count` instances (op: keygen / verify): a multiple of 256, monotone in
+ * count; the verify size serves every pk_stride.  d_ws holds: keygen rho' | images of A_hat | s1 | s2 | t; verify tr | mu | the why words | the hint
+ * masks | images of A_hat | z | t1 2^d | c | w'.  Polynomials are 64-bit words there (2 KiB each), images 1 KiB.
+ * Device forms: ordered on `stream`, nothing allocated, never synchronising.  Byte buffers need no alignment; d_ws must be 256-byte aligned.
+ * d_fail is a device int (may be NULL, never cleared by the call), OR-ed with 1 when a sampler reaches its cap of 8 blocks; the sampler then leaves
+ * zeros for what is missing.  With acceptance rate p per candidate a cap is reached when fewer than 256 (SampleInBall: tau) of the candidates of 8
+ * blocks are accepted, bounded by exp(-m D(256 / m || p)): RejNTTPoly (m = 448 candidates of 3 bytes, p = q / 2^23) below 2^-1479; RejBoundedPoly
+ * (m = 2176 half bytes) below 2^-6566 at p = 15 / 16 (eta = 2) and below 2^-1365 at p = 9 / 16 (eta = 4); SampleInBall (1080 bytes for at most 64
+ * draws, draw i accepted with (i + 1) / 256 >= 3 / 4) below 2^-1708.
+ * PSF_ERR_PARAM, in this order: an unknown param, op or msg_kind; a NULL data pointer with count > 0 (d_msg may be NULL when msg_len = 0, d_why
+ * always); a stride below its length (except pk_stride = 0), or PSF_MLDSA_MSG_MU with msg_len != 64; a byte count that overflows size_t; d_ws NULL or
+ * misaligned, or ws_bytes below the required size; an output range that overlaps an input, another output or the workspace.  Then
+ * PSF_ERR_UNSUPPORTED for more than 2^31 - 1 instances.  count = 0 is PSF_OK.  Every check runs before the first HIP call; nothing is launched or
+ * written on an error.  A valid call without a device is PSF_ERR_HIP (no CPU fallback).
+ * Host forms: the same arguments without workspace, flag and stream; they allocate per call, run on the device and return PSF_ERR_SAMPLER if the
+ * flag was raised. */
+enum { PSF_MLDSA_44 = 44, PSF_MLDSA_65 = 65, PSF_MLDSA_87 = 87 };
+enum { PSF_MLDSA_OP_KEYGEN = 0, PSF_MLDSA_OP_VERIFY = 1 };
+enum { PSF_MLDSA_MSG_BYTES = 0, PSF_MLDSA_MSG_MU = 1 };
+enum { PSF_MLDSA_WHY_HINT = 1, PSF_MLDSA_WHY_NORM = 2, PSF_MLDSA_WHY_HASH = 4 };
+psf_status psf_mldsa_sizes(int param, size_t* pk, size_t* sk, size_t* sig);
+psf_status psf_mldsa_workspace_bytes(int param, size_t count, int op, size_t* bytes);
+psf_status psf_mldsa_keygen_dev(int device, int param, size_t count, const uint8_t* d_xi, uint8_t* d_pk, uint8_t* d_sk, void* d_ws, size_t ws_bytes, int* d_fail,
+                                void* stream);
+psf_status psf_mldsa_verify_dev(int device, int param, size_t count, const uint8_t* d_pk, size_t pk_stride, const uint8_t* d_msg, size_t msg_len, size_t msg_stride,
+                                int msg_kind, const uint8_t* d_sig, uint8_t* d_ok, uint8_t* d_why, void* d_ws, size_t ws_bytes, int* d_fail, void* stream);
+psf_status psf_mldsa_keygen(int device, int param, size_t count, const uint8_t* xi, uint8_t* pk, uint8_t* sk);
+psf_status psf_mldsa_verify(int device, int param, size_t count, const uint8_t* pk, size_t pk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
+                            int msg_kind, const uint8_t* sig, uint8_t* ok, uint8_t* why);
+/* The stages of ML-DSA as entry points of their own: 64-bit words, one polynomial of 256 coefficients per lane, polynomials contiguous.
+ *   sample_ntt      RejNTTPoly (Algorithm 30): coefficients in [0, q) in FIPS 204's NTT-domain order.  k = l = 0, the raw form: input c is the 34
+ *                   bytes at d_seed + c * seed_stride, output polynomial c.  Otherwise (1 <= k, l <= 255) input c is a 32-byte rho_c and the output is
+ *                   count * k * l polynomials; polynomial (c, r, s), row-major, is RejNTTPoly(rho_c || byte(s) || byte(r)): A_hat of ExpandA, operand A
+ *                   of batch c with rows = k and inner = l once psf_ntt_image_from_fips204_dev has made images of it.
+ *   sample_bounded  RejBoundedPoly (Algorithm 31): polynomial (c, t), t < per_seed, is RejBoundedPoly(seed_c || le16(first_nonce + t)) from the
+ *                   64-byte seed at d_seed + c * seed_stride; signed coefficients in [-eta, eta].  first_nonce + per_seed <= 65536.
+ *   sample_in_ball  SampleInBall (Algorithm 29) of the ctilde_len bytes at d_ctilde + c * ctilde_stride, 1 <= tau <= 64: coefficients in {-1, 0, 1}.
+ *   image_from      reads `count` polynomials as Algorithm 41 (NTT) leaves them, any 64-bit value read mod q, and writes images (count * 256 32-bit
+ *                   words) that every negacyclic *_hat_dev product accepts at (8380417, 256).  A fixed permutation and a change of scale, as its
+ *                   FIPS 203 twin is.  There is no `to` direction: no ML-DSA key or signature holds an NTT-domain value.
+ * d_fail and the cap of 8 blocks are those of the ML-DSA entry points above.
+ * PSF_ERR_PARAM, in this order: k or l above 255, or exactly one of them 0; eta = 0; first_nonce + per_seed > 65536; tau outside [1, 64]; a stride
+ * smaller than the seed; a NULL seed or output pointer with count > 0; a byte count that overflows size_t; an output range that overlaps the seeds.
+ * Then PSF_ERR_UNSUPPORTED: eta other than 2 or 4.  count = 0 (or per_seed = 0) is PSF_OK.  Every check runs before the first HIP call; nothing is
+ * launched or written on an error.  A valid call without a device is PSF_ERR_HIP.  Device forms: ordered on `stream`, nothing allocated, never
+ * synchronising; seeds need no alignment, the output that of its word.  Host forms: allocate per call, run on the device, PSF_ERR_SAMPLER if the
+ * flag was raised. */
+psf_status psf_sample_ntt_fips204_dev(int device, size_t count, uint32_t k, uint32_t l, const uint8_t* d_seed, size_t seed_stride, uint64_t* d_out, int* d_fail,
+                                      void* stream);
+psf_status psf_sample_bounded_fips204_dev(int device, size_t count, uint32_t eta, const uint8_t* d_seed, size_t seed_stride, uint32_t first_nonce, uint32_t per_seed,
+                                          int64_t* d_out, int* d_fail, void* stream);
+psf_status psf_sample_in_ball_fips204_dev(int device, size_t count, uint32_t tau, const uint8_t* d_ctilde, size_t ctilde_len, size_t ctilde_stride, int64_t* d_out,
+                                          int* d_fail, void* stream);
+psf_status psf_ntt_image_from_fips204_dev(int device, size_t count, const uint64_t* d_fhat, uint32_t* d_hat, void* stream);
+psf_status psf_sample_ntt_fips204(int device, size_t count, uint32_t k, uint32_t l, const uint8_t* seed, size_t seed_stride, uint64_t* out);
+psf_status psf_sample_bounded_fips204(int device, size_t count, uint32_t eta, const uint8_t* seed, size_t seed_stride, uint32_t first_nonce, uint32_t per_seed,
+                                      int64_t* out);
+psf_status psf_sample_in_ball_fips204(int device, size_t count, uint32_t tau, const uint8_t* ctilde, size_t ctilde_len, size_t ctilde_stride, int64_t* out);
+psf_status psf_ntt_image_from_fips204(int device, size_t count, const uint64_t* fhat, uint32_t* hat);
 /* rot_minus_matrix (rotation_matrix.rs:85-96): mat[rows x cols] -> out[rows x rows*cols] */
 psf_status psf_rot_minus_matrix(const int64_t* mat, size_t rows, size_t cols, int64_t* out);
 

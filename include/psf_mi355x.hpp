@@ -162,6 +162,87 @@ inline std::vector<uint8_t> mlkem_check_dk(int device, int param, size_t count, 
   return ok;
 }
 
+// ---- FIPS 204 stages and ML-DSA, batched (psf_*_fips204*, psf_mldsa_*; sizes, the workspace and the rules in psf_mi355x.h).  `param` is PSF_MLDSA_44 / _65 / _87
+inline void sample_ntt_fips204_dev(int device, size_t count, uint32_t k, uint32_t l, const uint8_t* d_seed, size_t seed_stride, uint64_t* d_out, int* d_fail = nullptr,
+                                   void* stream = nullptr) {
+  check(psf_sample_ntt_fips204_dev(device, count, k, l, d_seed, seed_stride, d_out, d_fail, stream), "sample_ntt_fips204_dev");
+}
+inline void sample_bounded_fips204_dev(int device, size_t count, uint32_t eta, const uint8_t* d_seed, size_t seed_stride, uint32_t first_nonce, uint32_t per_seed,
+                                       int64_t* d_out, int* d_fail = nullptr, void* stream = nullptr) {
+  check(psf_sample_bounded_fips204_dev(device, count, eta, d_seed, seed_stride, first_nonce, per_seed, d_out, d_fail, stream), "sample_bounded_fips204_dev");
+}
+inline void sample_in_ball_fips204_dev(int device, size_t count, uint32_t tau, const uint8_t* d_ctilde, size_t ctilde_len, size_t ctilde_stride, int64_t* d_out,
+                                       int* d_fail = nullptr, void* stream = nullptr) {
+  check(psf_sample_in_ball_fips204_dev(device, count, tau, d_ctilde, ctilde_len, ctilde_stride, d_out, d_fail, stream), "sample_in_ball_fips204_dev");
+}
+inline void ntt_image_from_fips204_dev(int device, size_t count, const uint64_t* d_fhat, uint32_t* d_hat, void* stream = nullptr) {
+  check(psf_ntt_image_from_fips204_dev(device, count, d_fhat, d_hat, stream), "ntt_image_from_fips204_dev");
+}
+// host forms: packed seeds in, 256 words per polynomial out
+inline std::vector<uint64_t> sample_ntt_fips204(int device, size_t count, uint32_t k, uint32_t l, const std::vector<uint8_t>& seed) {
+  if (seed.size() != count * (k ? 32 : 34)) throw PsfError(PSF_ERR_PARAM, "sample_ntt_fips204");
+  std::vector<uint64_t> out(count * (k ? (size_t)k * l : 1) * 256);
+  check(psf_sample_ntt_fips204(device, count, k, l, seed.data(), k ? 32 : 34, out.data()), "sample_ntt_fips204");
+  return out;
+}
+inline std::vector<int64_t> sample_bounded_fips204(int device, size_t count, uint32_t eta, const std::vector<uint8_t>& seed, uint32_t first_nonce, uint32_t per_seed) {
+  if (seed.size() != count * 64) throw PsfError(PSF_ERR_PARAM, "sample_bounded_fips204");
+  std::vector<int64_t> out(count * per_seed * 256);
+  check(psf_sample_bounded_fips204(device, count, eta, seed.data(), 64, first_nonce, per_seed, out.data()), "sample_bounded_fips204");
+  return out;
+}
+inline std::vector<int64_t> sample_in_ball_fips204(int device, size_t count, uint32_t tau, const std::vector<uint8_t>& ctilde, size_t ctilde_len) {
+  if (ctilde.size() != count * ctilde_len) throw PsfError(PSF_ERR_PARAM, "sample_in_ball_fips204");
+  std::vector<int64_t> out(count * 256);
+  check(psf_sample_in_ball_fips204(device, count, tau, ctilde.data(), ctilde_len, ctilde_len, out.data()), "sample_in_ball_fips204");
+  return out;
+}
+inline std::vector<uint32_t> ntt_image_from_fips204(int device, size_t count, const std::vector<uint64_t>& fhat) {
+  if (fhat.size() != count * 256) throw PsfError(PSF_ERR_PARAM, "ntt_image_from_fips204");
+  std::vector<uint32_t> hat(count * 256);
+  check(psf_ntt_image_from_fips204(device, count, fhat.data(), hat.data()), "ntt_image_from_fips204");
+  return hat;
+}
+struct MlDsaSizes { size_t pk, sk, sig; };
+inline MlDsaSizes mldsa_sizes(int param) {
+  MlDsaSizes s{};
+  check(psf_mldsa_sizes(param, &s.pk, &s.sk, &s.sig), "mldsa_sizes");
+  return s;
+}
+inline size_t mldsa_workspace_bytes(int param, size_t count, int op) {
+  size_t bytes = 0;
+  check(psf_mldsa_workspace_bytes(param, count, op, &bytes), "mldsa_workspace_bytes");
+  return bytes;
+}
+inline void mldsa_keygen_dev(int device, int param, size_t count, const uint8_t* d_xi, uint8_t* d_pk, uint8_t* d_sk, void* d_ws, size_t ws_bytes, int* d_fail = nullptr,
+                             void* stream = nullptr) {
+  check(psf_mldsa_keygen_dev(device, param, count, d_xi, d_pk, d_sk, d_ws, ws_bytes, d_fail, stream), "mldsa_keygen_dev");
+}
+// pk_stride = 0: one key for all; msg_kind PSF_MLDSA_MSG_BYTES (M') or PSF_MLDSA_MSG_MU (msg_len = 64); d_why may be NULL
+inline void mldsa_verify_dev(int device, int param, size_t count, const uint8_t* d_pk, size_t pk_stride, const uint8_t* d_msg, size_t msg_len, size_t msg_stride,
+                             int msg_kind, const uint8_t* d_sig, uint8_t* d_ok, uint8_t* d_why, void* d_ws, size_t ws_bytes, int* d_fail = nullptr, void* stream = nullptr) {
+  check(psf_mldsa_verify_dev(device, param, count, d_pk, pk_stride, d_msg, msg_len, msg_stride, msg_kind, d_sig, d_ok, d_why, d_ws, ws_bytes, d_fail, stream),
+        "mldsa_verify_dev");
+}
+// host buffers, packed: xi 32 bytes per instance; returns (pk, sk)
+inline std::pair<std::vector<uint8_t>, std::vector<uint8_t>> mldsa_keygen(int device, int param, size_t count, const std::vector<uint8_t>& xi) {
+  const MlDsaSizes s = mldsa_sizes(param);
+  if (xi.size() != count * 32) throw PsfError(PSF_ERR_PARAM, "mldsa_keygen");
+  std::vector<uint8_t> pk(count * s.pk), sk(count * s.sk);
+  check(psf_mldsa_keygen(device, param, count, xi.data(), pk.data(), sk.data()), "mldsa_keygen");
+  return {pk, sk};
+}
+// pk: one key (for all) or count keys, packed; msg: count messages of msg_len bytes, packed; returns (ok, why), one byte per instance each
+inline std::pair<std::vector<uint8_t>, std::vector<uint8_t>> mldsa_verify(int device, int param, size_t count, const std::vector<uint8_t>& pk, const std::vector<uint8_t>& msg,
+                                                                          size_t msg_len, int msg_kind, const std::vector<uint8_t>& sig) {
+  const MlDsaSizes s = mldsa_sizes(param);
+  const bool one = pk.size() == s.pk && count != 1;
+  if ((!one && pk.size() != count * s.pk) || msg.size() != count * msg_len || sig.size() != count * s.sig) throw PsfError(PSF_ERR_PARAM, "mldsa_verify");
+  std::vector<uint8_t> ok(count), why(count);
+  check(psf_mldsa_verify(device, param, count, pk.data(), one ? 0 : s.pk, msg.data(), msg_len, msg_len, msg_kind, sig.data(), ok.data(), why.data()), "mldsa_verify");
+  return {ok, why};
+}
+
 // ---- PSFPerturbation (mp_perturbation.rs:57-62, :193-403) -------------------------------------------------------------
 class PSFPerturbation {
  public:

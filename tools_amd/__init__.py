@@ -5,7 +5,8 @@ GadgetParameters.init_default, PSFPerturbation / PSFGPV / PSFGPVRing with
 trap_gen / samp_d / samp_p / f_a / check_domain; compression (LossyCompressionFIPS203), encodings (utils::common_encodings),
 rq (MatPolynomialRingZq matrix products, and the products of the cyclic ring X^n - 1), sample (uniform, centred-binomial and
 discrete-Gaussian fills), fips203 (SHA3 / SHAKE, the byte-exact samplers of FIPS 203 and its NTT-domain representation) and mlkem (batched
-ML-KEM KeyGen / Encaps / Decaps and the input checks, bytes in and bytes out).
+ML-KEM KeyGen / Encaps / Decaps and the input checks, bytes in and bytes out), fips204 (the byte-exact samplers of FIPS 204 and its NTT-domain
+order) and mldsa (batched ML-DSA KeyGen and Verify).
 Everything computes on the GPU through the C ABI.
 """
 from ._ffi import PsfError, LIB_PATH  # noqa: F401
@@ -19,3 +20,5 @@ from . import rq  # noqa: F401
 from . import sample  # noqa: F401
 from . import fips203  # noqa: F401
 from . import mlkem  # noqa: F401
+from . import fips204  # noqa: F401
+from . import mldsa  # noqa: F401
