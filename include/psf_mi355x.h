@@ -388,7 +388,7 @@ psf_status psf_mlkem_decaps(int device, int param, size_t count, const uint8_t* 
 psf_status psf_mlkem_check_ek(int device, int param, size_t count, const uint8_t* ek, uint8_t* ok);
 psf_status psf_mlkem_check_dk(int device, int param, size_t count, const uint8_t* dk, uint8_t* ok);
 /* ML-DSA (FIPS 204, August 2024), batched, bytes in and bytes out: ML-DSA.KeyGen_internal(xi) (Algorithm 6) and ML-DSA.Verify_internal(pk, M', sigma)
- * (Algorithm 8) for ML-DSA-44, -65 and -87.  Signing is not offered.  The library draws NO randomness: xi is the caller's 32-byte string.  The value
+ * (Algorithm 8) for ML-DSA-44, -65 and -87; signing (Algorithm 7) is psf_mldsa_sign_* below.  The library draws NO randomness: xi is the caller's 32-byte string.  The value
  * of a parameter set is its number; (k, l, eta, tau, lambda / 4, gamma1, gamma2, beta, omega) = (4, 4, 2, 39, 32, 2^17, (q - 1) / 88, 78, 80),
  * (6, 5, 4, 49, 48, 2^19, (q - 1) / 32, 196, 55), (8, 7, 2, 60, 64, 2^19, (q - 1) / 32, 120, 75); q = 8380417, n = 256, d = 13.
  *   sizes in bytes:  pk 32 + 320 k (1312 / 1952 / 2592), sk 128 + 32 ((k + l) bitlen(2 eta) + 13 k) (2560 / 4032 / 4896),
@@ -436,6 +436,47 @@ psf_status psf_mldsa_verify_dev(int device, int param, size_t count, const uint8
 psf_status psf_mldsa_keygen(int device, int param, size_t count, const uint8_t* xi, uint8_t* pk, uint8_t* sk);
 psf_status psf_mldsa_verify(int device, int param, size_t count, const uint8_t* pk, size_t pk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
                             int msg_kind, const uint8_t* sig, uint8_t* ok, uint8_t* why);
+/* ML-DSA.Sign_internal(sk, M', rnd) (Algorithm 7), batched: sigma_c for `count` instances, one key for all (sk_stride = 0) or key c at
+ * d_sk + c * sk_stride (sk_stride >= the sk size).  The rejection loop is three device calls, none of which synchronises, and one number that the
+ * caller carries between them:
+ *   begin   fills slot j of the workspace with instance j: the images of s1, s2, t0 (skDecode, NTT) and of A_hat = ExpandA(rho); mu = H(tr || M', 64)
+ *           with tr read from sk (msg_kind, msg_len and msg_stride as in verify; PSF_MLDSA_MSG_MU: the 64 message bytes are mu);
+ *           rho'' = H(K || rnd || mu, 64) with rnd the 32 bytes at d_rnd + 32 c, or 32 zero bytes when d_rnd is NULL (the deterministic variant; the
+ *           library draws no randomness); kappa = 0.  It writes `count` to the device word *d_live.
+ *   round   one attempt for the instances in the first m = min(active, *d_live) slots: y = ExpandMask(rho'', kappa), kappa += l, w = A y,
+ *           c~ = H(mu || w1Encode(HighBits(w)), lambda / 4), c = SampleInBall(c~), z = y + c s1, r = w - c s2, and the four tests ||z|| >= gamma1 - beta,
+ *           ||LowBits(r)|| >= gamma2 - beta, ||c t0|| >= gamma2, more than omega ones in MakeHint(-c t0, r + c t0).  An accepted instance gets
+ *           sigEncode(c~, z mod+- q, h) at d_sig + index * sig size and its number of attempts at d_rounds[index] (d_rounds may be NULL), and leaves
+ *           the live set; a rejected one writes nothing outside the workspace.  Then the live slots are made dense again, [0, new_live): holes of
+ *           the new prefix are filled from live slots beyond it, and new_live is written to *d_live.  `active` is a host value in [0, count] that
+ *           sizes the launches; the kernels read *d_live and skip slots at or beyond it, so any `active` is safe: a smaller one than *d_live leaves
+ *           some instances unattempted in this round, a larger one costs product work on dead slots.  A signature is a function of (sk, mu, rnd)
+ *           alone: not of the schedule of `active`, the batch or the slot.  An instance whose counter is used up (kappa + l > 2^16 before an
+ *           attempt; probability below 0.8^9000) is retired unsigned and d_fail is OR-ed with 2.
+ *   end     sets every byte of the workspace to zero: everything in it but A_hat is secret.  Call it whether or not every instance was signed.
+ * The caller reads *d_live (4 bytes) when it chooses to, passes it as the next `active`, and stops at 0.  count, sk_stride, d_ws and d_live are the
+ * same in every call of one signing.
+ * psf_mldsa_sign_workspace_bytes: the bytes of d_ws for `count` instances, a multiple of 256, monotone in count, smaller for sk_stride = 0.  d_ws
+ * holds the images of A_hat (k l KiB) | s1_hat | s2_hat | t0_hat (l + 2 k KiB) -- per slot, or once when sk_stride = 0 -- then per slot mu | rho'' |
+ * kappa | index, the control words, and the per-round scratch y | w (then r) | c | z | c t0 | c~ | flags | holes | sources (64-bit words, 2 KiB a
+ * polynomial), which is never moved.
+ * PSF_ERR_PARAM, in this order: an unknown param or msg_kind (host form: max_rounds < 1 or max_rounds * l > 65536); a NULL d_sk, d_msg (unless
+ * msg_len = 0), d_sig or d_live with count > 0 (d_rnd and d_rounds may be NULL); sk_stride neither 0 nor >= the sk size, msg_stride < msg_len,
+ * PSF_MLDSA_MSG_MU with msg_len != 64, active > count; a byte count that overflows size_t; d_ws NULL, misaligned (256) or ws_bytes too small; d_live
+ * or d_rounds not 4-byte aligned; an output (d_live, d_sig, d_rounds) that overlaps an input, another output or the workspace.  Then
+ * PSF_ERR_UNSUPPORTED above 2^31 - 1 instances.  count = 0 is PSF_OK.  Every check runs before the first HIP call; a valid call without a device is
+ * PSF_ERR_HIP.  d_fail as above (1: a sampler cap; 2: a counter used up).
+ * Host form psf_mldsa_sign: allocates, zero-fills sig (and rounds, which may be NULL), runs begin, then rounds with active = the 4 bytes of d_live read
+ * back after each, until it is 0 or max_rounds rounds have run, then end.  PSF_ERR_SAMPLER if instances remain or the flag was raised: their sig
+ * stays zero and their rounds[c] is 0. */
+psf_status psf_mldsa_sign_workspace_bytes(int param, size_t count, size_t sk_stride, size_t* bytes);
+psf_status psf_mldsa_sign_begin_dev(int device, int param, size_t count, const uint8_t* d_sk, size_t sk_stride, const uint8_t* d_msg, size_t msg_len,
+                                    size_t msg_stride, int msg_kind, const uint8_t* d_rnd, void* d_ws, size_t ws_bytes, uint32_t* d_live, int* d_fail, void* stream);
+psf_status psf_mldsa_sign_round_dev(int device, int param, size_t count, size_t sk_stride, size_t active, uint8_t* d_sig, uint32_t* d_rounds, void* d_ws,
+                                    size_t ws_bytes, uint32_t* d_live, int* d_fail, void* stream);
+psf_status psf_mldsa_sign_end_dev(int device, int param, size_t count, size_t sk_stride, void* d_ws, size_t ws_bytes, void* stream);
+psf_status psf_mldsa_sign(int device, int param, size_t count, const uint8_t* sk, size_t sk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
+                          int msg_kind, const uint8_t* rnd, uint8_t* sig, uint32_t max_rounds, uint32_t* rounds);
 /* The stages of ML-DSA as entry points of their own: 64-bit words, one polynomial of 256 coefficients per lane, polynomials contiguous.
  *   sample_ntt      RejNTTPoly (Algorithm 30): coefficients in [0, q) in FIPS 204's NTT-domain order.  k = l = 0, the raw form: input c is the 34
  *                   bytes at d_seed + c * seed_stride, output polynomial c.  Otherwise (1 <= k, l <= 255) input c is a 32-byte rho_c and the output is

@@ -242,6 +242,38 @@ inline std::pair<std::vector<uint8_t>, std::vector<uint8_t>> mldsa_verify(int de
   check(psf_mldsa_verify(device, param, count, pk.data(), one ? 0 : s.pk, msg.data(), msg_len, msg_len, msg_kind, sig.data(), ok.data(), why.data()), "mldsa_verify");
   return {ok, why};
 }
+// signing: begin, then rounds with `active` = the value last read from *d_live until it is 0, then end (psf_mi355x.h); sk_stride = 0: one key for all
+inline size_t mldsa_sign_workspace_bytes(int param, size_t count, size_t sk_stride) {
+  size_t bytes = 0;
+  check(psf_mldsa_sign_workspace_bytes(param, count, sk_stride, &bytes), "mldsa_sign_workspace_bytes");
+  return bytes;
+}
+inline void mldsa_sign_begin_dev(int device, int param, size_t count, const uint8_t* d_sk, size_t sk_stride, const uint8_t* d_msg, size_t msg_len, size_t msg_stride,
+                                 int msg_kind, const uint8_t* d_rnd, void* d_ws, size_t ws_bytes, uint32_t* d_live, int* d_fail = nullptr, void* stream = nullptr) {
+  check(psf_mldsa_sign_begin_dev(device, param, count, d_sk, sk_stride, d_msg, msg_len, msg_stride, msg_kind, d_rnd, d_ws, ws_bytes, d_live, d_fail, stream),
+        "mldsa_sign_begin_dev");
+}
+inline void mldsa_sign_round_dev(int device, int param, size_t count, size_t sk_stride, size_t active, uint8_t* d_sig, uint32_t* d_rounds, void* d_ws, size_t ws_bytes,
+                                 uint32_t* d_live, int* d_fail = nullptr, void* stream = nullptr) {
+  check(psf_mldsa_sign_round_dev(device, param, count, sk_stride, active, d_sig, d_rounds, d_ws, ws_bytes, d_live, d_fail, stream), "mldsa_sign_round_dev");
+}
+inline void mldsa_sign_end_dev(int device, int param, size_t count, size_t sk_stride, void* d_ws, size_t ws_bytes, void* stream = nullptr) {
+  check(psf_mldsa_sign_end_dev(device, param, count, sk_stride, d_ws, ws_bytes, stream), "mldsa_sign_end_dev");
+}
+// sk: one key (for all) or count keys, packed; msg packed; rnd: empty (deterministic) or 32 bytes per instance; returns (sig, rounds); throws
+// PSF_ERR_SAMPLER when instances are unsigned after max_rounds rounds
+inline std::pair<std::vector<uint8_t>, std::vector<uint32_t>> mldsa_sign(int device, int param, size_t count, const std::vector<uint8_t>& sk, const std::vector<uint8_t>& msg,
+                                                                         size_t msg_len, int msg_kind, const std::vector<uint8_t>& rnd, uint32_t max_rounds = 1024) {
+  const MlDsaSizes s = mldsa_sizes(param);
+  const bool one = sk.size() == s.sk && count != 1;
+  if ((!one && sk.size() != count * s.sk) || msg.size() != count * msg_len || (!rnd.empty() && rnd.size() != count * 32)) throw PsfError(PSF_ERR_PARAM, "mldsa_sign");
+  std::vector<uint8_t> sig(count * s.sig);
+  std::vector<uint32_t> rounds(count);
+  check(psf_mldsa_sign(device, param, count, sk.data(), one ? 0 : s.sk, msg.data(), msg_len, msg_len, msg_kind, rnd.empty() ? nullptr : rnd.data(), sig.data(), max_rounds,
+                       rounds.data()),
+        "mldsa_sign");
+  return {sig, rounds};
+}
 
 // ---- PSFPerturbation (mp_perturbation.rs:57-62, :193-403) -------------------------------------------------------------
 class PSFPerturbation {

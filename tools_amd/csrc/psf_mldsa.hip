@@ -19,6 +19,7 @@
 #include "psf_hip_util.hpp"
 #include "psf_host.hpp"
 #include "psf_keccak_core.hpp"
+#include "psf_mldsa_api.hpp"
 #include "psf_mldsa_core.hpp"
 #include "psf_ntt_api.hpp"
 #include "psf_ntt_core.hpp"
@@ -27,18 +28,6 @@ namespace psf {
 namespace dsa {
 
 using kc::kDomShake;
-
-__device__ __forceinline__ void zero_state(uint64_t (&s)[25]) {
-#pragma unroll
-  for (int i = 0; i < 25; ++i) s[i] = 0;
-}
-// words s[first ... first + COUNT - 1] of a state as 8 COUNT bytes at p
-template <int FIRST, int COUNT> __device__ __forceinline__ void put_words(const uint64_t (&s)[25], uint8_t* p) {
-  const kc::PtrWriter wr{p, (uintptr_t)p % 8 == 0};
-#pragma unroll
-  for (int i = 0; i < COUNT; ++i) wr.put64(8 * i, s[FIRST + i]);
-}
-__device__ __forceinline__ bool aligned8(const void* p, size_t pitch) { return ((uintptr_t)p | pitch) % 8 == 0; }
 
 // ---- samplers ------------------------------------------------------------------------------------------------------------------------------------
 // One polynomial per lane, 64 consecutive polynomials per wave, four waves per workgroup, each wave on its own.  A lane past the end of the batch
@@ -134,10 +123,6 @@ __global__ __launch_bounds__(256) void k_ball(BallArgs a, const uint8_t* __restr
 }
 
 // ---- NTT images ----------------------------------------------------------------------------------------------------------------------------------
-// At (8380417, 256) the transform splits completely and the wave kernels compute in canonical 32-bit residues: an image word is f at one of the 256
-// odd powers of a 512th root of unity, as a FIPS 204 NTT-domain coefficient is.  What differs is which point sits where: image_map() matches the
-// points of the library's plan with those of Algorithm 41 (zeta = 1753).  The change of scale is the reduction of any 64-bit value to [0, q).
-struct ImageMap { bool ok = false; uint8_t word_of[256] = {}, fips_of[256] = {}; };
 struct ImgArgs { uint8_t src[256]; };
 
 __global__ __launch_bounds__(256) void k_image_from(ImgArgs m, const uint64_t* __restrict__ fhat, uint32_t* __restrict__ hat, size_t count) {
@@ -146,23 +131,6 @@ __global__ __launch_bounds__(256) void k_image_from(ImgArgs m, const uint64_t* _
 }
 
 // ---- hashes ----------------------------------------------------------------------------------------------------------------------------------------
-// na bytes of a, then nb bytes of b.  fast: both start at multiples of 8 and so is na.
-struct CatReader {
-  const uint8_t* a;
-  const uint8_t* b;
-  size_t na, nb;
-  bool fast;
-  PSF_KC_FN uint8_t byte(size_t pos) const { return pos < na ? a[pos] : b[pos - na]; }
-  PSF_KC_FN uint64_t le64(size_t pos) const {
-    uint64_t w = 0;
-    if (fast && pos + 8 <= na) { __builtin_memcpy(&w, __builtin_assume_aligned(a + pos, 8), 8); return w; }
-    if (fast && pos >= na) { __builtin_memcpy(&w, __builtin_assume_aligned(b + (pos - na), 8), 8); return w; }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) w |= (uint64_t)byte(pos + k) << (8 * k);
-    return w;
-  }
-};
-
 // KeyGen: (rho, rho', K) = H(xi_c || k || l, 128): rho to pk_c and sk_c, K to sk_c + 32, rho' to the workspace
 struct SeedArgs { size_t count, pk_len, sk_len; uint32_t k, l; const uint8_t* xi; uint8_t* pk; uint8_t* sk; uint8_t* rho_p; };
 __global__ __launch_bounds__(256) void k_seed(SeedArgs a) {
@@ -215,13 +183,6 @@ __global__ __launch_bounds__(256) void k_hint(HintArgs a) {
 }
 
 // ---- the polynomial glue ---------------------------------------------------------------------------------------------------------------------------
-// A segment: `polys` polynomials per item, item c's bytes at bytes + c pitch (32 bits bytes per polynomial), its 64-bit words at words + c polys 256.
-// A thread moves 8 values = `bits` bytes: 64 bytes of words (four vectors, the workspace is 256-byte aligned) and `bits` single bytes (no alignment
-// asked of keys and signatures); neighbouring threads touch neighbouring bytes.
-enum { MAP_PLAIN = 0, MAP_T1_SHIFT = 1, MAP_NORM = 2, MAP_T1 = 3, MAP_T0 = 4 };
-// unpack: PLAIN the value of the field; T1_SHIFT the value times 2^d; NORM the value, and flags[c] |= NORM when |value| >= bound
-// pack: PLAIN the field of the value; T1 / T0 the field of the high / low part of Power2Round(word)
-struct Seg { const uint8_t* bytes; int64_t* words; size_t pitch, count; uint32_t polys; int bits; int32_t top; int map; };
 struct SegArgs { Seg seg[4]; uint32_t* flags; int32_t bound; };
 
 __global__ __launch_bounds__(256) void k_unpack(SegArgs a) {
@@ -278,34 +239,7 @@ __global__ __launch_bounds__(256) void k_pack(SegArgs a) {
 }
 
 // ---- the verification tail -------------------------------------------------------------------------------------------------------------------------
-// The message mu || w1Encode(UseHint(h, w')) of one instance as the sponge reads it: 64 bytes of mu, then fields of BITS bits made on the fly from
-// the words of w' and the bits of h.  Its length is a multiple of 8, so the sponge asks for whole words only.
-template <uint32_t G2> struct W1Reader {
-  static constexpr int BITS = G2 == kGamma2Low ? 6 : 4;
-  const uint8_t* mu;
-  bool mu_aligned;
-  const uint64_t* w;
-  const uint8_t* h;
-  size_t fields;
-  PSF_KC_FN uint64_t field(size_t f) const {
-    if (f >= fields) return 0;
-    return use_hint<G2>((h[f >> 3] >> (f & 7)) & 1u, (uint32_t)w[f]);
-  }
-  PSF_KC_FN uint64_t le64(size_t pos) const {
-    if (pos < 64) return kc::PtrReader{mu, mu_aligned}.le64(pos);
-    const size_t bit = (pos - 64) * 8, f0 = bit / BITS;
-    const int skew = (int)(bit - f0 * BITS);                              // bits of field f0 that belong to the byte before
-    uint64_t acc = field(f0) >> skew;
-#pragma clang loop unroll(disable)                                        // kept rolled: the sponge unrolls its 17 words around this, and the state stays in registers
-    for (int t = 1; t <= 64 / BITS + 1; ++t) {                            // 6-bit fields at skew 4: the twelfth field starts at bit 62
-      const int sh = t * BITS - skew;
-      if (sh < 64) acc |= field(f0 + t) << sh;
-    }
-    return acc;
-  }
-  PSF_KC_FN uint8_t byte(size_t pos) const { return pos < 64 ? mu[pos] : 0; }      // the length is a multiple of 8: the sponge reads whole words, never this
-};
-
+// W1Reader (psf_mldsa_api.hpp) feeds mu || w1Encode(UseHint(h, w')) to the sponge.
 struct TailArgs {
   size_t count, sig_len, mu_pitch;
   uint32_t k, cb;
@@ -336,10 +270,6 @@ template <uint32_t G2> __global__ __launch_bounds__(256) void k_verify_tail(Tail
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------------
-constexpr unsigned kMaxGrid = 0x7fffffffu;
-typedef unsigned __int128 u128;
-
-struct Set { uint32_t k, l, eta, tau, cb, omega; int32_t gamma1, gamma2, beta; int zbits; size_t pk, sk, sig; };
 bool set_of(int param, Set* s) {
   switch (param) {
     case PSF_MLDSA_44: *s = {4, 4, 2, 39, 32, 80, 1 << 17, (int32_t)kGamma2Low, 78, 18, 0, 0, 0}; break;
@@ -392,19 +322,6 @@ const ImageMap& image_map() {
   return m;
 }
 
-// The workspace of an operation: sections in a fixed order, each rounded up to 256 bytes.  A polynomial of 64-bit words takes 2048 bytes, an image
-// 1024 bytes.
-struct Layout {
-  size_t total = 0;
-  bool ok = true;
-  size_t take(u128 bytes) {
-    const size_t at = total;
-    const u128 end = (u128)total + ((bytes + 255) / 256) * 256;
-    if (end > (u128)SIZE_MAX) { ok = false; return 0; }
-    total = (size_t)end;
-    return at;
-  }
-};
 struct KeygenWs { size_t rho_p, a_hat, s1, s2, t, total; bool ok; };
 struct VerifyWs { size_t tr, mu, flags, h, a_hat, z, t1, c, w, total; bool ok; };
 KeygenWs keygen_ws(const Set& s, size_t count) {
@@ -460,37 +377,35 @@ bool overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
   return pa < pb + nb && pb < pa + na;
 }
-// a buffer of a call: `count` items of `len` bytes at `stride`; ok_null: may be NULL (an empty message, d_why)
-struct Buf { const void* p; size_t len, stride; bool out, ok_null; size_t span; };
 // the header's order after `param`, `op`, `msg_kind` and count = 0: NULL pointers, [strides: the caller], byte counts, the workspace (device forms), overlaps
 psf_status check_null(const Buf* b, int nb) {
   for (int i = 0; i < nb; ++i)
     if (!b[i].p && !b[i].ok_null) return PSF_ERR_PARAM;
   return PSF_OK;
 }
-psf_status check_rest(const Set& s, size_t count, Buf* b, int nb, int op, bool dev, const void* ws, size_t ws_bytes, size_t* need) {
+psf_status check_spans(size_t count, Buf* b, int nb) {
   for (int i = 0; i < nb; ++i)
     if (!span_of(b[i].p, count, b[i].len, b[i].stride, &b[i].span)) return PSF_ERR_PARAM;
-  if (!ws_need(s, count, op, need)) return PSF_ERR_PARAM;
-  if (dev && (!ws || (uintptr_t)ws % 256 != 0 || ws_bytes < *need)) return PSF_ERR_PARAM;       // the host forms allocate their own
+  return PSF_OK;
+}
+psf_status check_ws(bool dev, const void* ws, size_t ws_bytes, size_t need) {
+  return dev && (!ws || (uintptr_t)ws % 256 != 0 || ws_bytes < need) ? PSF_ERR_PARAM : PSF_OK;       // the host forms allocate their own
+}
+psf_status check_overlaps(const Buf* b, int nb, bool dev, const void* ws, size_t need) {
   for (int i = 0; i < nb; ++i) {
     if (!b[i].out || !b[i].p) continue;
     for (int j = 0; j < nb; ++j)
       if (j != i && b[j].p && overlap(b[i].p, b[i].span, b[j].p, b[j].span)) return PSF_ERR_PARAM;
-    if (dev && overlap(b[i].p, b[i].span, ws, *need)) return PSF_ERR_PARAM;
+    if (dev && overlap(b[i].p, b[i].span, ws, need)) return PSF_ERR_PARAM;
   }
   return PSF_OK;
 }
-
-#define PSF_TRY(expr)                      \
-  do {                                     \
-    const psf_status rc__ = (expr);        \
-    if (rc__ != PSF_OK) return rc__;       \
-  } while (0)
-
-unsigned blocks_of(size_t items, size_t per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-bool grid_fits(size_t count) { return count <= kMaxGrid; }
-template <class T> T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<uint8_t*>(ws) + off); }
+psf_status check_rest(const Set& s, size_t count, Buf* b, int nb, int op, bool dev, const void* ws, size_t ws_bytes, size_t* need) {
+  PSF_TRY(check_spans(count, b, nb));
+  if (!ws_need(s, count, op, need)) return PSF_ERR_PARAM;
+  PSF_TRY(check_ws(dev, ws, ws_bytes, *need));
+  return check_overlaps(b, nb, dev, ws, *need);
+}
 
 // ---- launches of the stages (arguments checked by the caller; `device` is current) ------------------------------------------------------------------
 psf_status rej_ntt_launch(size_t total, uint32_t k, uint32_t l, const uint8_t* d_seed, size_t seed_stride, void* d_out, bool img, int* d_fail, hipStream_t st) {
@@ -555,10 +470,6 @@ psf_status launch_segs(bool pack, const Seg* segs, int nseg, uint32_t* flags, in
   HIP_TRY(hipGetLastError());
   return PSF_OK;
 }
-Seg seg_of(const uint8_t* bytes, int64_t* words, size_t pitch, size_t count, uint32_t polys, Packing p, int map) {
-  return Seg{bytes, words, pitch, count, polys, kPackTable[p].bits, kPackTable[p].top, map};
-}
-
 // ---- the two algorithms ----------------------------------------------------------------------------------------------------------------------------
 psf_status keygen_run(int device, const Set& s, size_t count, const uint8_t* xi, uint8_t* pk, uint8_t* sk, void* ws, const KeygenWs& w, int* fail, hipStream_t st) {
   const size_t k = s.k, l = s.l, eb = s.eta == 2 ? 3 : 4;

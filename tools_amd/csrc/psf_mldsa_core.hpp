@@ -1,9 +1,12 @@
 // psf_mldsa_core.hpp -- what FIPS 204 (ML-DSA, August 2024) adds to the sponge of psf_keccak_core.hpp: the parse loops of its three rejection
 // samplers (RejNTTPoly, Algorithm 30; RejBoundedPoly, Algorithm 31; SampleInBall, Algorithm 29), HintBitUnpack (Algorithm 21), Power2Round, Decompose
-// and UseHint (Algorithms 35, 36 and 40) for both values of gamma2, and the bit fields of its packings (Algorithms 16 to 19).
+// and UseHint (Algorithms 35, 36 and 40) for both values of gamma2, the bit fields of its packings (Algorithms 16 to 19), and what signing adds:
+// HighBits, LowBits and MakeHint (Algorithms 37 to 39), the norm tests of Algorithm 7, the parse of ExpandMask (Algorithm 34), HintBitPack
+// (Algorithm 20) and the rule for the two-byte counter.
 //
-// Written over the same back ends Ops as the sponge: the device kernels of psf_mldsa.hip use DevOps, and g++ compiles this same text over PlainOps
-// for tests/cpp/mldsa_host_check.cpp, which tests/test_mldsa_core_cpu.py compares with the Python model without a GPU.
+// Written over the same back ends Ops as the sponge: the device kernels of psf_mldsa.hip and psf_mldsa_sign.hip use DevOps, and g++ compiles this
+// same text over PlainOps for tests/cpp/mldsa_host_check.cpp and tests/cpp/mldsa_sign_host_check.cpp, which tests/test_mldsa_core_cpu.py and
+// tests/test_mldsa_sign_cpu.py compare with the Python model without a GPU.
 //
 // The parse loops follow sample_ntt_parse: one Keccak state per lane in registers, every index into the state a compile-time constant (the byte
 // positions of a block are unrolled), the lane's own progress in a counter, and one wave-level question per block ("is every lane done?") through
@@ -144,6 +147,87 @@ template <uint32_t G2> PSF_KC_FN uint32_t use_hint(uint32_t h, uint32_t r) {
   if (h == 0) return r1;
   if (r0 > 0) return r1 + 1 == m ? 0u : r1 + 1;
   return r1 == 0 ? m - 1 : r1 - 1;
+}
+
+// ---- what signing adds (Algorithm 7) -----------------------------------------------------------------------------------------------------------------
+// HighBits, LowBits (Algorithms 37 and 38) and MakeHint (Algorithm 39) on residues: MakeHint(z, r) = [HighBits(r) != HighBits(r + z)], called with
+// r and r + z mod q both at hand (signing has r = w - c s2 and r + z = r + c t0).  Selects and arithmetic only: nothing here branches on its data.
+template <uint32_t G2> PSF_KC_FN uint32_t high_bits(uint32_t r) {
+  uint32_t r1;
+  int32_t r0;
+  decompose<G2>(r, r1, r0);
+  return r1;
+}
+template <uint32_t G2> PSF_KC_FN int32_t low_bits(uint32_t r) {
+  uint32_t r1;
+  int32_t r0;
+  decompose<G2>(r, r1, r0);
+  return r0;
+}
+template <uint32_t G2> PSF_KC_FN uint32_t make_hint(uint32_t r, uint32_t r_plus_z) { return high_bits<G2>(r) != high_bits<G2>(r_plus_z) ? 1u : 0u; }
+// r in [0, q) as its representative in (-q / 2, q / 2], and the absolute value of that
+PSF_KC_FN int32_t centered(uint32_t r) { return (int32_t)r - (int32_t)(kQ & (0u - (uint32_t)(r > (kQ - 1) / 2))); }
+PSF_KC_FN uint32_t centered_abs(uint32_t r) {
+  const int32_t c = centered(r), m = c >> 31;
+  return (uint32_t)((c ^ m) - m);
+}
+// 1 when the residue's centred absolute value reaches the bound: the tests ||z|| >= gamma1 - beta and ||c t0|| >= gamma2 of Algorithm 7
+PSF_KC_FN uint32_t norm_reaches(uint32_t r, uint32_t bound) { return centered_abs(r) >= bound ? 1u : 0u; }
+// the same for a LowBits value: ||r0|| >= gamma2 - beta
+PSF_KC_FN uint32_t low_reaches(int32_t r0, uint32_t bound) {
+  const int32_t m = r0 >> 31;
+  return (uint32_t)((r0 ^ m) - m) >= bound ? 1u : 0u;
+}
+// The counter of ExpandMask is two bytes: an attempt at kappa draws the nonces kappa ... kappa + l - 1, so it may start only while
+// kappa + l <= 2^16.  true: the instance has used up its counter and is retired unsigned.
+PSF_KC_FN bool kappa_exhausted(uint32_t kappa, uint32_t l) { return kappa + l > 65536u; }
+
+// ExpandMask (Algorithm 34), one polynomial: s is the state after absorb<136>(rho'' || le16(kappa + r), 66 bytes, 0x1F); the first 32 BITS bytes of
+// the stream (576 for gamma1 = 2^17, 640 for 2^19: five blocks) are 256 fields of BITS bits and coefficient j = gamma1 - field: put(j, value).
+// Every position is a constant once the loops are unrolled: a field that straddles two words takes its low part from the word kept from before.
+template <int BITS, class Ops, class Put> PSF_KC_FN void expand_mask_parse(uint64_t (&s)[25], Put&& put) {
+  static_assert(BITS == 18 || BITS == 20, "gamma1 = 2^17 or 2^19");
+  constexpr int kWords = kc::kRateShake256 / 8, kTotal = 4 * BITS, kBlocks = (kTotal + kWords - 1) / kWords;       // 64-bit words of the stream
+  constexpr int32_t g1 = 1 << (BITS - 1);
+  uint64_t prev = 0;
+#pragma unroll
+  for (int blk = 0; blk < kBlocks; ++blk) {
+    if (blk) kc::f1600<Ops>(s);
+#pragma unroll
+    for (int i = 0; i < kWords; ++i) {
+      const int g = blk * kWords + i;
+      if (g < kTotal) {
+        const uint64_t cur = s[i];
+        // the fields that end inside word g: their last bit is in [64 g, 64 g + 63]
+        const int first = (64 * g) / BITS - 1, last = (64 * g + 64) / BITS - 1;
+#pragma unroll
+        for (int t = first; t <= last; ++t) {
+          const int start = t * BITS;
+          if (start + BITS > 64 * g && start + BITS <= 64 * g + 64 && t >= 0) {
+            uint64_t v;
+            if (start >= 64 * g) v = cur >> (start - 64 * g);
+            else v = (prev >> (start - 64 * (g - 1))) | (cur << (64 * g - start));
+            put((uint32_t)t, g1 - (int32_t)((uint32_t)v & ((1u << BITS) - 1)));
+          }
+        }
+        prev = cur;
+      }
+    }
+  }
+}
+
+// HintBitPack (Algorithm 20): mask(i, b) is the byte of the bits h[i][8 b ... 8 b + 7] (bit 0 first); put(pos, v) gets every one of the omega + k
+// bytes, zeros included.  The caller has checked that at most omega bits are set.
+template <class Mask, class Put> PSF_KC_FN void hint_bit_pack(Mask&& mask, uint32_t k, uint32_t omega, Put&& put) {
+  uint32_t index = 0;
+  for (uint32_t i = 0; i < k; ++i) {
+    for (uint32_t b = 0; b < kN / 8; ++b) {
+      uint32_t m = mask(i, b) & 255u;
+      for (; m != 0 && index < omega; m &= m - 1) put(index++, 8 * b + (uint32_t)__builtin_ctz(m));
+    }
+    put(omega + i, index);
+  }
+  for (; index < omega; ++index) put(index, 0u);
 }
 
 // ---- packings ---------------------------------------------------------------------------------------------------------------------------------------

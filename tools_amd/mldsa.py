@@ -4,10 +4,14 @@
   keygen_dev / verify_dev   ML-DSA.KeyGen_internal and ML-DSA.Verify_internal (Algorithms 6 and 8) over raw device pointers (e.g. torch
                `data_ptr()`), ordered on `stream`, nothing allocated; the caller supplies xi and the workspace
   keygen_internal / verify_internal   the host forms over lists of bytes (they run on the device too)
-  keygen / verify   ML-DSA.KeyGen (xi from os.urandom) and ML-DSA.Verify(pk, M, sigma, ctx) (Algorithm 3: M' = 0 || |ctx| || ctx || M).  They
-               exist in Python only; the library itself draws no randomness and formats no message.
+  sign_workspace_bytes / sign_begin_dev / sign_round_dev / sign_end_dev   ML-DSA.Sign_internal (Algorithm 7) over raw device pointers: begin, then
+               rounds with `active` = the value last read from the device word d_live until it is 0, then end
+  sign_internal   the host form of signing over lists of bytes: signatures and the number of attempts of each
+  keygen / sign / verify   ML-DSA.KeyGen (xi from os.urandom), ML-DSA.Sign(sk, M, ctx) (Algorithm 2: rnd from os.urandom, or 32 zero bytes with
+               deterministic=True) and ML-DSA.Verify(pk, M, sigma, ctx) (Algorithm 3), with M' = 0 || |ctx| || ctx || M.  They exist in Python only; the
+               library itself draws no randomness and formats no message.
 
-Signing is not offered.  A parameter set is named "ML-DSA-44", "ML-DSA-65" or "ML-DSA-87"; `why` is an OR of WHY_HINT, WHY_NORM and WHY_HASH."""
+A parameter set is named "ML-DSA-44", "ML-DSA-65" or "ML-DSA-87"; `why` is an OR of WHY_HINT, WHY_NORM and WHY_HASH."""
 import ctypes as C
 import os
 
@@ -35,6 +39,11 @@ def _lib():
         L.psf_mldsa_verify_dev.argtypes = [i, i, sz, vp, sz, vp, sz, sz, i, vp, vp, vp, vp, sz, vp, vp]
         L.psf_mldsa_keygen.argtypes = [i, i, sz, vp, vp, vp]
         L.psf_mldsa_verify.argtypes = [i, i, sz, vp, sz, vp, sz, sz, i, vp, vp, vp]
+        L.psf_mldsa_sign_workspace_bytes.argtypes = [i, sz, sz, C.POINTER(sz)]
+        L.psf_mldsa_sign_begin_dev.argtypes = [i, i, sz, vp, sz, vp, sz, sz, i, vp, vp, sz, vp, vp, vp]
+        L.psf_mldsa_sign_round_dev.argtypes = [i, i, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp]
+        L.psf_mldsa_sign_end_dev.argtypes = [i, i, sz, sz, vp, sz, vp]
+        L.psf_mldsa_sign.argtypes = [i, i, sz, vp, sz, vp, sz, sz, i, vp, vp, C.c_uint32, vp]
         _typed = True
     return L
 
@@ -75,6 +84,38 @@ def verify_dev(name, count, d_pk, d_msg, msg_len, d_sig, d_ok, d_ws, ws_bytes, d
         pk_stride = sizes(name)["pk"]
     check(_lib().psf_mldsa_verify_dev(device, _param(name), count, d_pk or 0, pk_stride, d_msg or 0, msg_len, msg_len if msg_stride is None else msg_stride, msg_kind,
                                       d_sig or 0, d_ok or 0, d_why or 0, d_ws or 0, ws_bytes, d_fail or 0, stream or 0), "mldsa.verify_dev")
+
+
+def sign_workspace_bytes(name, count, sk_stride=None):
+    """bytes of the 256-byte aligned device workspace of one signing of `count` instances; sk_stride 0: one key for all (the smaller layout),
+    None: the sk size (one key per instance)"""
+    out = C.c_size_t(0)
+    check(_lib().psf_mldsa_sign_workspace_bytes(_param(name), count, sizes(name)["sk"] if sk_stride is None else sk_stride, C.byref(out)), "mldsa.sign_workspace_bytes")
+    return int(out.value)
+
+
+def sign_begin_dev(name, count, d_sk, d_msg, msg_len, d_ws, ws_bytes, d_live, d_rnd=None, sk_stride=None, msg_stride=None, msg_kind=MSG_BYTES, d_fail=None, device=0,
+                   stream=None):
+    """psf_mldsa_sign_begin_dev: slot j of the workspace gets instance j, *d_live = count.  d_rnd None: the deterministic variant"""
+    if sk_stride is None:
+        sk_stride = sizes(name)["sk"]
+    check(_lib().psf_mldsa_sign_begin_dev(device, _param(name), count, d_sk or 0, sk_stride, d_msg or 0, msg_len, msg_len if msg_stride is None else msg_stride, msg_kind,
+                                          d_rnd or 0, d_ws or 0, ws_bytes, d_live or 0, d_fail or 0, stream or 0), "mldsa.sign_begin_dev")
+
+
+def sign_round_dev(name, count, active, d_sig, d_ws, ws_bytes, d_live, d_rounds=None, sk_stride=None, d_fail=None, device=0, stream=None):
+    """psf_mldsa_sign_round_dev: one attempt for the first min(active, *d_live) slots; accepted instances get their signature and leave"""
+    if sk_stride is None:
+        sk_stride = sizes(name)["sk"]
+    check(_lib().psf_mldsa_sign_round_dev(device, _param(name), count, sk_stride, active, d_sig or 0, d_rounds or 0, d_ws or 0, ws_bytes, d_live or 0, d_fail or 0,
+                                          stream or 0), "mldsa.sign_round_dev")
+
+
+def sign_end_dev(name, count, d_ws, ws_bytes, sk_stride=None, device=0, stream=None):
+    """psf_mldsa_sign_end_dev: every byte of the workspace to zero"""
+    if sk_stride is None:
+        sk_stride = sizes(name)["sk"]
+    check(_lib().psf_mldsa_sign_end_dev(device, _param(name), count, sk_stride, d_ws or 0, ws_bytes, stream or 0), "mldsa.sign_end_dev")
 
 
 # ---- host forms ------------------------------------------------------------------------------------------------------------------------------------
@@ -121,11 +162,41 @@ def verify_internal(name, pks, msgs, sigs, msg_kind=MSG_BYTES, device=0, why=Fal
     return [(bool(a), int(b)) for a, b in zip(ok, wh)] if why else [bool(a) for a in ok]
 
 
-# ---- Algorithms 1 and 3: the external forms, in Python only ------------------------------------------------------------------------------------------
+def sign_internal(name, sks, msgs, rnds=None, msg_kind=MSG_BYTES, max_rounds=1024, device=0):
+    """([signature], [attempts]) for each (sk, M', rnd); `sks` is one key (bytes) for all or a list with one key per instance; the messages of one
+    call have one length; rnds None: the deterministic variant.  Raises PsfError(PSF_ERR_SAMPLER) when instances are unsigned after max_rounds."""
+    sz = sizes(name)
+    msgs = [bytes(m) for m in msgs]
+    lens = {len(m) for m in msgs}
+    if len(lens) > 1:
+        raise ValueError("mldsa.sign_internal: the messages of one call have one length")
+    msg_len = lens.pop() if lens else 0
+    msg = _rows(msgs, msg_len, "message")
+    one = isinstance(sks, (bytes, bytearray))
+    sk = _rows([sks] if one else sks, sz["sk"], "sk")
+    rnd = None if rnds is None else _rows(rnds, 32, "rnd")
+    if (not one and len(sk) != len(msg)) or (rnd is not None and len(rnd) != len(msg)):
+        raise ValueError("mldsa.sign_internal: as many keys and rnd strings as messages")
+    sig, rounds = np.zeros((len(msg), sz["sig"]), np.uint8), np.zeros(len(msg), np.uint32)
+    check(_lib().psf_mldsa_sign(device, _param(name), len(msg), _vp(sk), 0 if one else sz["sk"], _vp(msg), msg_len, msg_len, msg_kind, None if rnd is None else _vp(rnd),
+                                _vp(sig), max_rounds, _vp(rounds)), "mldsa.sign_internal")
+    return [bytes(a) for a in sig], [int(r) for r in rounds]
+
+
+# ---- Algorithms 1, 2 and 3: the external forms, in Python only ------------------------------------------------------------------------------------------
 
 def keygen(name, count, device=0, random=os.urandom):
     """ML-DSA.KeyGen for `count` fresh key pairs: xi from `random` (os.urandom), then keygen_internal"""
     return keygen_internal(name, [random(32) for _ in range(count)], device=device)
+
+
+def sign(name, sk, M, ctx=b"", random=os.urandom, deterministic=False, device=0):
+    """ML-DSA.Sign (Algorithm 2) of one message: rnd from `random` (os.urandom), or 32 zero bytes when deterministic; ValueError when ctx is longer
+    than 255 bytes"""
+    if len(ctx) > 255:
+        raise ValueError("mldsa.sign: ctx longer than 255 bytes")
+    rnd = None if deterministic else [random(32)]
+    return sign_internal(name, bytes(sk), [bytes([0, len(ctx)]) + bytes(ctx) + bytes(M)], rnd, device=device)[0][0]
 
 
 def verify(name, pk, M, sig, ctx=b"", device=0):
