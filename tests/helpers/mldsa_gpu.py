@@ -1,13 +1,53 @@
-"""The harness of the ML-DSA device tests (tests/test_gpu_mldsa.py, tests/test_gpu_fips204.py): buffers one byte past a 16-byte boundary with guard
-bytes around every output (the pieces of tests/helpers/mlkem_gpu.py), the workspace and sampler flag of a call with their checks, one function per
-device entry point that runs it and applies all of them, and the cached runs of the pure-Python model that the tests compare with.  The model's
-signer is slow, so its outputs are cached per (name, ...) and large batches are made by tiling a few distinct (key, message, signature) triples.
-Nothing here imports the library or torch: both are arguments."""
+"""The harness of the ML-DSA device tests (tests/test_gpu_mldsa*.py, tests/test_gpu_fips204.py): buffers at chosen byte offsets from a 16-byte
+boundary with guard bytes around every output (the pieces of tests/helpers/mlkem_gpu.py), the workspace and sampler flag of a call with their
+checks, one function per device entry point that runs it and applies all of them, and the cached runs of the pure-Python model that the tests
+compare with.  The model's signer is slow, so its outputs are cached per (name, ...) and large batches are made by tiling a few distinct (key,
+message, signature) triples.  Nothing here imports the library or torch: both are arguments.
+
+Offsets.  Every `dev_*` function (dev_sign of tests/helpers/mldsa_sign_gpu.py too) takes `offs`: None (every buffer one byte past a 16-byte
+boundary, the default of the suite), an int (that offset for every buffer) or a dict from `offsets()` with one entry per buffer: the inputs
+"in_xi", "in_pk", "in_sk", "in_msg", "in_sig", "in_rnd" and the outputs "out_pk", "out_sk", "out_sig", "out_ok", "out_why".
+
+Strides.  `pk_stride`, `sk_stride` and `msg_stride` lay the items of that input out at that pitch (`_put_pitched`); the bytes between two items
+are a non-zero pattern that starts at `gap`.  Outputs are packed: they have no gap bytes."""
 import functools
 import random
 
+import numpy as np
+
 from tests.helpers import mldsa_model as M
-from tests.helpers.mlkem_gpu import _out, _put, _take
+from tests.helpers.mlkem_gpu import _off, _out, _put, _take
+
+INPUTS = ("xi", "pk", "sk", "msg", "sig", "rnd")
+OUTPUTS = ("pk", "sk", "sig", "ok", "why")
+
+
+def offsets(inputs=1, outputs=1, **named):
+    """the `offs` dict with every input at `inputs`, every output at `outputs`, and the buffers in `named` (in_sk=0, out_sig=4, ...) at their own"""
+    offs = {"in_" + k: inputs for k in INPUTS}
+    offs.update({"out_" + k: outputs for k in OUTPUTS})
+    for key, value in named.items():
+        assert key in offs, key
+        offs[key] = value
+    return offs
+
+
+def pitched(items, stride, gap):
+    """the items of one size at a pitch of `stride` bytes as one bytes object; the bytes after each item (the last too) are gap, gap + 1, ... without zeros"""
+    size = len(items[0])
+    assert stride > size and all(len(x) == size for x in items) and 0 < gap < 256
+    rows = np.empty((len(items), stride), dtype=np.uint8)
+    rows[:, :size] = np.frombuffer(b"".join(items), dtype=np.uint8).reshape(len(items), size)
+    fill = (gap + np.arange(len(items) * (stride - size), dtype=np.int64)) % 255 + 1
+    rows[:, size:] = fill.astype(np.uint8).reshape(len(items), stride - size)
+    return rows.tobytes()
+
+
+def _put_pitched(torch, items, off=1, stride=None, gap=0xC3):
+    """_put with the items `stride` bytes apart (None or their size: packed)"""
+    if stride is None or stride == len(items[0]):
+        return _put(torch, items, off)
+    return _put(torch, [pitched(items, stride, gap)], off)
 
 NAMES = sorted(M.PARAMS)
 DISTINCT = 3
@@ -99,42 +139,46 @@ class Scratch:
         assert int(self.flag.item()) == self.start, (what, "the sampler flag changed")
 
 
-def dev_keygen(torch, D, name, xi, flag=0):
+def dev_keygen(torch, D, name, xi, flag=0, offs=None):
     count, sz = len(xi), M.sizes(name)
-    bxi, pxi = _put(torch, xi)
-    bpk, ppk = _out(torch, count * sz["pk"])
-    bsk, psk = _out(torch, count * sz["sk"])
+    o_pk, o_sk = _off(offs, "out_pk"), _off(offs, "out_sk")
+    bxi, pxi = _put(torch, xi, _off(offs, "in_xi"))
+    bpk, ppk = _out(torch, count * sz["pk"], o_pk)
+    bsk, psk = _out(torch, count * sz["sk"], o_sk)
     sc = Scratch(torch, D, name, count, "keygen", flag)
     torch.cuda.synchronize()
     D.keygen_dev(name, count, pxi, ppk, psk, sc.ptr, sc.bytes, d_fail=sc.flag.data_ptr())
-    pk = _take(torch, bpk, count * sz["pk"], sz["pk"], (name, count, "pk"))
-    sk = _take(torch, bsk, count * sz["sk"], sz["sk"], (name, count, "sk"))
+    pk = _take(torch, bpk, count * sz["pk"], sz["pk"], (name, count, "pk"), o_pk)
+    sk = _take(torch, bsk, count * sz["sk"], sz["sk"], (name, count, "sk"), o_sk)
     sc.check((name, count, "keygen"), cleared=True)
     del bxi
     return pk, sk, (bpk, ppk)
 
 
-def dev_verify(torch, D, name, pks, msgs, sigs, msg_kind=0, flag=0, pk_ptr=None, with_why=True):
-    """verify_dev over the instances; `pks`: a list with one key per instance, or bytes (one key for all: pk_stride = 0); returns (ok, why) as lists"""
+def dev_verify(torch, D, name, pks, msgs, sigs, msg_kind=0, flag=0, pk_ptr=None, with_why=True, offs=None, pk_stride=None, msg_stride=None, gap=0xC3):
+    """verify_dev over the instances; `pks`: a list with one key per instance, or bytes (one key for all: pk_stride = 0); `pk_stride` / `msg_stride`:
+    the pitch of the keys (of a list) / the messages, None: packed; returns (ok, why) as lists"""
     count, sz = len(sigs), M.sizes(name)
     one = isinstance(pks, bytes)
+    o_ok, o_why = _off(offs, "out_ok"), _off(offs, "out_why")
+    assert not (one and pk_stride) and not (pk_ptr is not None and pk_stride)
     keep = None
     if pk_ptr is None:
-        keep, pk_ptr = _put(torch, [pks] if one else pks)
+        keep, pk_ptr = _put_pitched(torch, [pks] if one else pks, _off(offs, "in_pk"), pk_stride, gap)
     msg_len = len(msgs[0])
     assert all(len(m) == msg_len for m in msgs)
-    bm, pm = _put(torch, msgs) if msg_len else (None, None)
-    bs, ps = _put(torch, sigs)
-    bok, pok = _out(torch, count)
-    bwhy, pwhy = _out(torch, count)
+    bm, pm = _put_pitched(torch, msgs, _off(offs, "in_msg"), msg_stride, gap ^ 0x5F) if msg_len else (None, None)
+    bs, ps = _put(torch, sigs, _off(offs, "in_sig"))
+    bok, pok = _out(torch, count, o_ok)
+    bwhy, pwhy = _out(torch, count, o_why)
     sc = Scratch(torch, D, name, count, "verify", flag)
     torch.cuda.synchronize()
-    D.verify_dev(name, count, pk_ptr, pm, msg_len, ps, pok, sc.ptr, sc.bytes, d_why=pwhy if with_why else None, pk_stride=0 if one else sz["pk"],
-                 msg_kind=msg_kind, d_fail=sc.flag.data_ptr())
-    ok = [b[0] for b in _take(torch, bok, count, 1, (name, count, "ok"))]
-    why = [b[0] for b in _take(torch, bwhy, count if with_why else 0, 1, (name, count, "why"))] if with_why else None
+    D.verify_dev(name, count, pk_ptr, pm, msg_len, ps, pok, sc.ptr, sc.bytes, d_why=pwhy if with_why else None,
+                 pk_stride=0 if one else (pk_stride or sz["pk"]), msg_stride=msg_stride, msg_kind=msg_kind, d_fail=sc.flag.data_ptr())
+    ok = [b[0] for b in _take(torch, bok, count, 1, (name, count, "ok"), o_ok)]
+    why = [b[0] for b in _take(torch, bwhy, count, 1, (name, count, "why"), o_why)] if with_why else None
     if not with_why:
-        _take(torch, bwhy, 0, 1, (name, count, "why"))                     # untouched when d_why is NULL
+        _take(torch, bwhy, 0, 1, (name, count, "why"), o_why)              # untouched when d_why is NULL
     sc.check((name, count, "verify"), cleared=False)
     del keep, bm, bs
     return ok, why

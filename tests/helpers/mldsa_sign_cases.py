@@ -4,8 +4,10 @@ by a search over instance(name, i) with the restated signer (tests/helpers/mldsa
 Per parameter set: an instance accepted at its first attempt; one that needs at least 16 attempts; and instances with an attempt in which exactly one
 of the tests fires: ||z|| alone, ||LowBits(r)|| alone, the hint count alone (the last fired alone in 11 / 1 / 2 of 4530 / 3627 / 2412 attempts).
 
-What is not searched for: ||c t0||_inf >= gamma2 fired in none of 10569 attempts of the model, so no instance exercises it.  That test is covered
-with crafted residues on both sides of gamma2 through tests/cpp/mldsa_sign_host_check.cpp instead."""
+What these keys cannot show: ||c t0||_inf >= gamma2 fired in none of 10569 attempts of the model under keys that KeyGen made.  It does fire under a
+well-formed ML-DSA-44 key whose t0 sits at the ends of its 13-bit fields: that instance is searched and checked in
+tests/helpers/mldsa_edge_cases.py (ct0_instance) and signed on the device by tests/test_gpu_mldsa_edges.py; for ML-DSA-65 and -87 no encodable t0
+reaches gamma2.  Crafted residues on both sides of gamma2 go through tests/cpp/mldsa_sign_host_check.cpp as well."""
 import functools
 import hashlib
 
