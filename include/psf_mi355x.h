@@ -507,6 +507,42 @@ psf_status psf_sample_bounded_fips204(int device, size_t count, uint32_t eta, co
                                       int64_t* out);
 psf_status psf_sample_in_ball_fips204(int device, size_t count, uint32_t tau, const uint8_t* ctilde, size_t ctilde_len, size_t ctilde_stride, int64_t* out);
 psf_status psf_ntt_image_from_fips204(int device, size_t count, const uint64_t* fhat, uint32_t* hat);
+/* SLH-DSA (FIPS 205, August 2024), batched, bytes in and bytes out: slh_keygen_internal(SK.seed, SK.prf, PK.seed) (Algorithm 18) and
+ * slh_verify_internal(M, SIG, PK) (Algorithm 20) for the six SHAKE parameter sets; signing and the SHA-2 sets are not here.  The library draws NO
+ * randomness: the three seeds are the caller's n-byte strings.  (n, h, d, h', a, k, m) = 128s (16, 63, 7, 9, 12, 14, 30), 128f (16, 66, 22, 3, 6, 33, 34),
+ * 192s (24, 63, 7, 9, 14, 17, 39), 192f (24, 66, 22, 3, 8, 33, 42), 256s (32, 64, 8, 8, 14, 22, 47), 256f (32, 68, 17, 4, 9, 35, 49); lg_w = 4,
+ * len = 2 n + 3.  The hash functions are those of section 11.1, all SHAKE256: H_msg = SHAKE256(R || PK.seed || PK.root || M, 8 m), PRF, F, H and
+ * T_l = SHAKE256(PK.seed || ADRS || ..., 8 n) with the uncompressed 32-byte ADRS.
+ *   sizes in bytes:  pk 2 n (32 / 48 / 64), sk 4 n (64 / 96 / 128), sig (1 + k (1 + a) + h + d len) n (7856 / 17088 / 16224 / 35664 / 29792 / 49856).
+ *   keygen   PK.root = xmss_node(SK.seed, 0, h', PK.seed, ADRS{layer d - 1, tree 0}); pk = PK.seed || PK.root, sk = SK.seed || SK.prf || PK.seed ||
+ *            PK.root.  The three inputs, pk and sk are contiguous: instance c at base + c * size.  The WOTS+ secret values and the chain intermediates
+ *            exist in registers only; every chain runs its 15 steps; no branch and no address depends on a secret.  d_ws receives the chain ends and
+ *            the leaves (public values), and the last thing the call queues on `stream` sets every byte of d_ws to zero.
+ *   verify   Algorithm 20.  Key c is at d_pk + c * pk_stride; pk_stride = 0 means one key for all instances, otherwise pk_stride >= 2 n.  Messages
+ *            have one length per call: instance c's msg_len bytes are at d_msg + c * msg_stride.  The bytes are the M of Algorithm 20 -- the caller
+ *            formats M' = 0 || |ctx| || ctx || M for Algorithm 24.  Signatures are contiguous, at the fixed size.  d_ok[c] is 1 or 0.  Nothing in
+ *            verification is secret: its workspace is NOT cleared and needs no clearing.
+ * psf_slhdsa_workspace_bytes gives the bytes of d_ws an operation needs for `count` instances (op: keygen / verify): a multiple of 256, monotone in
+ * count; the verify size serves every pk_stride.  d_ws holds: keygen the chain ends (2^h' len n bytes per instance) | the leaves (2^h' n); verify the
+ * first 64 bytes of H_msg | the k FORS roots | the current node (32 bytes) | the len chain ends of the current layer.
+ * Device forms: ordered on `stream`, nothing allocated, never synchronising.  Byte buffers need no alignment; d_ws must be 256-byte aligned.
+ * PSF_ERR_PARAM, in this order: an unknown param or op; a NULL data pointer with count > 0 (d_msg may be NULL when msg_len = 0); a stride below its
+ * length (except pk_stride = 0); a byte count that overflows size_t; d_ws NULL or misaligned, or ws_bytes below the required size; an output range
+ * that overlaps an input, another output or the workspace.  Then PSF_ERR_UNSUPPORTED for more than 2^31 - 1 instances.  count = 0 is PSF_OK.  Every
+ * check runs before the first HIP call; nothing is launched or written on an error.  A valid call without a device is PSF_ERR_HIP (no CPU fallback).
+ * Host forms: the same arguments without workspace and stream; they allocate per call and run on the device. */
+enum { PSF_SLHDSA_SHAKE_128S = 0, PSF_SLHDSA_SHAKE_128F = 1, PSF_SLHDSA_SHAKE_192S = 2, PSF_SLHDSA_SHAKE_192F = 3, PSF_SLHDSA_SHAKE_256S = 4,
+       PSF_SLHDSA_SHAKE_256F = 5 };
+enum { PSF_SLHDSA_OP_KEYGEN = 0, PSF_SLHDSA_OP_VERIFY = 1 };
+psf_status psf_slhdsa_sizes(int param, size_t* pk, size_t* sk, size_t* sig);
+psf_status psf_slhdsa_workspace_bytes(int param, size_t count, int op, size_t* bytes);
+psf_status psf_slhdsa_keygen_dev(int device, int param, size_t count, const uint8_t* d_sk_seed, const uint8_t* d_sk_prf, const uint8_t* d_pk_seed, uint8_t* d_pk,
+                                 uint8_t* d_sk, void* d_ws, size_t ws_bytes, void* stream);
+psf_status psf_slhdsa_verify_dev(int device, int param, size_t count, const uint8_t* d_pk, size_t pk_stride, const uint8_t* d_msg, size_t msg_len, size_t msg_stride,
+                                 const uint8_t* d_sig, uint8_t* d_ok, void* d_ws, size_t ws_bytes, void* stream);
+psf_status psf_slhdsa_keygen(int device, int param, size_t count, const uint8_t* sk_seed, const uint8_t* sk_prf, const uint8_t* pk_seed, uint8_t* pk, uint8_t* sk);
+psf_status psf_slhdsa_verify(int device, int param, size_t count, const uint8_t* pk, size_t pk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
+                             const uint8_t* sig, uint8_t* ok);
 /* rot_minus_matrix (rotation_matrix.rs:85-96): mat[rows x cols] -> out[rows x rows*cols] */
 psf_status psf_rot_minus_matrix(const int64_t* mat, size_t rows, size_t cols, int64_t* out);
 

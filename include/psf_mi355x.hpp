@@ -275,6 +275,48 @@ inline std::pair<std::vector<uint8_t>, std::vector<uint32_t>> mldsa_sign(int dev
   return {sig, rounds};
 }
 
+// ---- SLH-DSA, batched (psf_slhdsa_*; sizes, the workspace and the rules in psf_mi355x.h).  `param` is PSF_SLHDSA_SHAKE_128S ... _256F
+struct SlhDsaSizes { size_t pk, sk, sig; };
+inline SlhDsaSizes slhdsa_sizes(int param) {
+  SlhDsaSizes s{};
+  check(psf_slhdsa_sizes(param, &s.pk, &s.sk, &s.sig), "slhdsa_sizes");
+  return s;
+}
+inline size_t slhdsa_workspace_bytes(int param, size_t count, int op) {
+  size_t bytes = 0;
+  check(psf_slhdsa_workspace_bytes(param, count, op, &bytes), "slhdsa_workspace_bytes");
+  return bytes;
+}
+inline void slhdsa_keygen_dev(int device, int param, size_t count, const uint8_t* d_sk_seed, const uint8_t* d_sk_prf, const uint8_t* d_pk_seed, uint8_t* d_pk, uint8_t* d_sk,
+                              void* d_ws, size_t ws_bytes, void* stream = nullptr) {
+  check(psf_slhdsa_keygen_dev(device, param, count, d_sk_seed, d_sk_prf, d_pk_seed, d_pk, d_sk, d_ws, ws_bytes, stream), "slhdsa_keygen_dev");
+}
+// pk_stride = 0: one key for all
+inline void slhdsa_verify_dev(int device, int param, size_t count, const uint8_t* d_pk, size_t pk_stride, const uint8_t* d_msg, size_t msg_len, size_t msg_stride,
+                              const uint8_t* d_sig, uint8_t* d_ok, void* d_ws, size_t ws_bytes, void* stream = nullptr) {
+  check(psf_slhdsa_verify_dev(device, param, count, d_pk, pk_stride, d_msg, msg_len, msg_stride, d_sig, d_ok, d_ws, ws_bytes, stream), "slhdsa_verify_dev");
+}
+// host buffers, packed: n = pk / 2 bytes of each seed per instance; returns (pk, sk)
+inline std::pair<std::vector<uint8_t>, std::vector<uint8_t>> slhdsa_keygen(int device, int param, size_t count, const std::vector<uint8_t>& sk_seed,
+                                                                           const std::vector<uint8_t>& sk_prf, const std::vector<uint8_t>& pk_seed) {
+  const SlhDsaSizes s = slhdsa_sizes(param);
+  const size_t n = s.pk / 2;
+  if (sk_seed.size() != count * n || sk_prf.size() != count * n || pk_seed.size() != count * n) throw PsfError(PSF_ERR_PARAM, "slhdsa_keygen");
+  std::vector<uint8_t> pk(count * s.pk), sk(count * s.sk);
+  check(psf_slhdsa_keygen(device, param, count, sk_seed.data(), sk_prf.data(), pk_seed.data(), pk.data(), sk.data()), "slhdsa_keygen");
+  return {pk, sk};
+}
+// pk: one key (for all) or count keys, packed; msg: count messages of msg_len bytes, packed; returns ok, one byte per instance
+inline std::vector<uint8_t> slhdsa_verify(int device, int param, size_t count, const std::vector<uint8_t>& pk, const std::vector<uint8_t>& msg, size_t msg_len,
+                                          const std::vector<uint8_t>& sig) {
+  const SlhDsaSizes s = slhdsa_sizes(param);
+  const bool one = pk.size() == s.pk && count != 1;
+  if ((!one && pk.size() != count * s.pk) || msg.size() != count * msg_len || sig.size() != count * s.sig) throw PsfError(PSF_ERR_PARAM, "slhdsa_verify");
+  std::vector<uint8_t> ok(count);
+  check(psf_slhdsa_verify(device, param, count, pk.data(), one ? 0 : s.pk, msg.data(), msg_len, msg_len, sig.data(), ok.data()), "slhdsa_verify");
+  return ok;
+}
+
 // ---- PSFPerturbation (mp_perturbation.rs:57-62, :193-403) -------------------------------------------------------------
 class PSFPerturbation {
  public:
