@@ -508,8 +508,8 @@ psf_status psf_sample_bounded_fips204(int device, size_t count, uint32_t eta, co
 psf_status psf_sample_in_ball_fips204(int device, size_t count, uint32_t tau, const uint8_t* ctilde, size_t ctilde_len, size_t ctilde_stride, int64_t* out);
 psf_status psf_ntt_image_from_fips204(int device, size_t count, const uint64_t* fhat, uint32_t* hat);
 /* SLH-DSA (FIPS 205, August 2024), batched, bytes in and bytes out: slh_keygen_internal(SK.seed, SK.prf, PK.seed) (Algorithm 18) and
- * slh_verify_internal(M, SIG, PK) (Algorithm 20) for the six SHAKE parameter sets; signing and the SHA-2 sets are not here.  The library draws NO
- * randomness: the three seeds are the caller's n-byte strings.  (n, h, d, h', a, k, m) = 128s (16, 63, 7, 9, 12, 14, 30), 128f (16, 66, 22, 3, 6, 33, 34),
+ * slh_verify_internal(M, SIG, PK) (Algorithm 20) and slh_sign_internal(M, SK, addrnd) (Algorithm 19, below) for the six SHAKE parameter sets; the SHA-2
+ * sets and HashSLH-DSA are not here.  The library draws NO randomness: the three seeds and addrnd are the caller's n-byte strings.  (n, h, d, h', a, k, m) = 128s (16, 63, 7, 9, 12, 14, 30), 128f (16, 66, 22, 3, 6, 33, 34),
  * 192s (24, 63, 7, 9, 14, 17, 39), 192f (24, 66, 22, 3, 8, 33, 42), 256s (32, 64, 8, 8, 14, 22, 47), 256f (32, 68, 17, 4, 9, 35, 49); lg_w = 4,
  * len = 2 n + 3.  The hash functions are those of section 11.1, all SHAKE256: H_msg = SHAKE256(R || PK.seed || PK.root || M, 8 m), PRF, F, H and
  * T_l = SHAKE256(PK.seed || ADRS || ..., 8 n) with the uncompressed 32-byte ADRS.
@@ -530,7 +530,26 @@ psf_status psf_ntt_image_from_fips204(int device, size_t count, const uint64_t* 
  * length (except pk_stride = 0); a byte count that overflows size_t; d_ws NULL or misaligned, or ws_bytes below the required size; an output range
  * that overlaps an input, another output or the workspace.  Then PSF_ERR_UNSUPPORTED for more than 2^31 - 1 instances.  count = 0 is PSF_OK.  Every
  * check runs before the first HIP call; nothing is launched or written on an error.  A valid call without a device is PSF_ERR_HIP (no CPU fallback).
- * Host forms: the same arguments without workspace and stream; they allocate per call and run on the device. */
+ * Host forms: the same arguments without workspace and stream; they allocate per call and run on the device.
+ *   sign     Algorithm 19, byte-identical to the standard's pseudocode.  Key c is the 4 n bytes at d_sk + c * sk_stride; sk_stride = 0 means one key for
+ *            all instances, otherwise sk_stride >= 4 n.  Messages as in verify: one length per call, instance c's msg_len bytes at d_msg + c *
+ *            msg_stride, the bytes are the M of Algorithm 19 (the caller formats M' = 0 || |ctx| || ctx || M for Algorithm 22); d_msg may be NULL when
+ *            msg_len = 0.  d_addrnd is NULL -- the deterministic variant, opt_rand = PK.seed read from the key -- or n bytes per instance, contiguous:
+ *            instance c uses the n bytes at d_addrnd + c * n.  Signatures are contiguous at the fixed size.  A signature is a function of (sk, M,
+ *            addrnd) alone: not of the batch, the position in it or sk_stride.  No WOTS+ or FORS secret value and no chain intermediate is stored to
+ *            memory except the ones that ARE the signature; no branch, loop bound or address depends on a secret (indices and digits come from the
+ *            digest and from roots, which a verifier recomputes).
+ * psf_slhdsa_sign_workspace_bytes gives the bytes of d_ws for `count` instances: a multiple of 256, monotone in count, 0 for count = 0, the same for
+ * every sk_stride.  d_ws holds, each section rounded up to 256 bytes: the first 64 bytes of H_msg per instance | the FORS subtree roots (k 2^(a - 9) n
+ * bytes per instance when a > 9, else nothing) | the k FORS roots (k n) | the messages of the d layers (32 d) | the chain ends of all d trees
+ * (d 2^h' len n) | their leaves (d 2^h' n): public values only.  The device form is ordered on `stream`, allocates nothing and never synchronises;
+ * byte buffers need no alignment, d_ws must be 256-byte aligned; the last thing the call queues on `stream` sets every byte of d_ws to zero.
+ * PSF_ERR_PARAM, in this order: an unknown param (psf_slhdsa_sign_workspace_bytes: also a NULL `bytes`); a NULL d_sk, d_msg (unless msg_len = 0) or
+ * d_sig with count > 0; sk_stride neither 0 nor >= 4 n, or msg_stride < msg_len; a byte count that overflows size_t; d_ws NULL or misaligned, or
+ * ws_bytes too small; d_sig overlapping an input or the workspace.  Then PSF_ERR_UNSUPPORTED above 2^31 - 1 instances.  count = 0 is PSF_OK after the
+ * param check.  Every check runs before the first HIP call; nothing is launched or written on an error.  A valid call without a device is PSF_ERR_HIP.
+ * Host form psf_slhdsa_sign: the same arguments without workspace and stream; it allocates per call, runs on the device and zeroes its device copies
+ * of sk and addrnd before freeing them. */
 enum { PSF_SLHDSA_SHAKE_128S = 0, PSF_SLHDSA_SHAKE_128F = 1, PSF_SLHDSA_SHAKE_192S = 2, PSF_SLHDSA_SHAKE_192F = 3, PSF_SLHDSA_SHAKE_256S = 4,
        PSF_SLHDSA_SHAKE_256F = 5 };
 enum { PSF_SLHDSA_OP_KEYGEN = 0, PSF_SLHDSA_OP_VERIFY = 1 };
@@ -543,6 +562,11 @@ psf_status psf_slhdsa_verify_dev(int device, int param, size_t count, const uint
 psf_status psf_slhdsa_keygen(int device, int param, size_t count, const uint8_t* sk_seed, const uint8_t* sk_prf, const uint8_t* pk_seed, uint8_t* pk, uint8_t* sk);
 psf_status psf_slhdsa_verify(int device, int param, size_t count, const uint8_t* pk, size_t pk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
                              const uint8_t* sig, uint8_t* ok);
+psf_status psf_slhdsa_sign_workspace_bytes(int param, size_t count, size_t* bytes);
+psf_status psf_slhdsa_sign_dev(int device, int param, size_t count, const uint8_t* d_sk, size_t sk_stride, const uint8_t* d_msg, size_t msg_len, size_t msg_stride,
+                               const uint8_t* d_addrnd, uint8_t* d_sig, void* d_ws, size_t ws_bytes, void* stream);
+psf_status psf_slhdsa_sign(int device, int param, size_t count, const uint8_t* sk, size_t sk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
+                           const uint8_t* addrnd, uint8_t* sig);
 /* rot_minus_matrix (rotation_matrix.rs:85-96): mat[rows x cols] -> out[rows x rows*cols] */
 psf_status psf_rot_minus_matrix(const int64_t* mat, size_t rows, size_t cols, int64_t* out);
 

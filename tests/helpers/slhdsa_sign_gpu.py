@@ -1,0 +1,44 @@
+"""The harness of the SLH-DSA signing device tests (tests/test_gpu_slhdsa_sign.py), in the manner of tests/helpers/slhdsa_gpu.py: every buffer one byte
+past a 16-byte boundary, guard bytes around the signatures, a workspace filled with a non-zero byte that is all zero after the call, nothing written
+outside the workspace.  Nothing here imports the library or torch: both are arguments."""
+from tests.helpers import slhdsa_model as M
+from tests.helpers.mlkem_gpu import _out, _put, _take
+
+
+class SignScratch:
+    """the workspace of one signing call, filled with 0x5A"""
+
+    def __init__(self, torch, D, name, count):
+        self.torch, self.bytes = torch, D.sign_workspace_bytes(name, count)
+        assert self.bytes % 256 == 0 and self.bytes > 0
+        self.ws = torch.full((self.bytes + 256,), 0x5A, dtype=torch.uint8, device="cuda")
+        self.ptr = (self.ws.data_ptr() + 255) // 256 * 256
+
+    def check(self, what):
+        """every byte of the workspace zero, and nothing written outside it"""
+        self.torch.cuda.synchronize()
+        lo = self.ptr - self.ws.data_ptr()
+        assert not bool(self.ws[lo:lo + self.bytes].any().item()), (what, "the workspace is not all zero after the call")
+        assert bool((self.ws[:lo] == 0x5A).all().item()) and bool((self.ws[lo + self.bytes:] == 0x5A).all().item()), (what, "wrote outside the workspace")
+
+
+def dev_sign(torch, D, name, sks, msgs, addrnds=None):
+    """sign_dev over the instances; `sks`: a list with one key per instance, or bytes (one key for all: sk_stride = 0); addrnds None: the deterministic
+    variant (no pointer); an empty message has no pointer either; returns the signatures as a list of bytes"""
+    count, sz = len(msgs), M.sizes(name)
+    one = isinstance(sks, bytes)
+    assert one or len(sks) == count
+    bk, pk = _put(torch, [sks] if one else sks)
+    msg_len = len(msgs[0])
+    assert all(len(m) == msg_len for m in msgs)
+    bm, pm = _put(torch, msgs) if msg_len else (None, None)
+    br, pr = (None, None) if addrnds is None else _put(torch, addrnds)
+    assert addrnds is None or (len(addrnds) == count and all(len(r) == sz["pk"] // 2 for r in addrnds))
+    bs, ps = _out(torch, count * sz["sig"])
+    sc = SignScratch(torch, D, name, count)
+    torch.cuda.synchronize()
+    D.sign_dev(name, count, pk, pm, msg_len, pr, ps, sc.ptr, sc.bytes, sk_stride=0 if one else sz["sk"])
+    sigs = _take(torch, bs, count * sz["sig"], sz["sig"], (name, count, "sig"))
+    sc.check((name, count, "sign"))
+    del bk, bm, br
+    return sigs

@@ -16,6 +16,7 @@
 #include "psf_host.hpp"
 #include "psf_keccak_core.hpp"
 #include "psf_mldsa_api.hpp"
+#include "psf_slhdsa_api.hpp"
 #include "psf_slhdsa_core.hpp"
 
 namespace psf {
@@ -239,18 +240,6 @@ bool ws_need(const Params& p, size_t count, int op, size_t* need) {
   return ok;
 }
 
-// a stage of `lanes` lanes as launches of at most 2^31 - 1 workgroups of 256, args.first moving along
-template <class Args> psf_status launch_chunked(void (*kern)(Args), size_t lanes, Args a, hipStream_t st) {
-  const size_t blocks = (lanes + 255) / 256;
-  for (size_t b0 = 0; b0 < blocks; b0 += kMaxGrid) {
-    const size_t nb = blocks - b0 < kMaxGrid ? blocks - b0 : (size_t)kMaxGrid;
-    a.first = b0 * 256;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-  }
-  return PSF_OK;
-}
-
 template <int NW> psf_status keygen_run_nw(KgArgs a, hipStream_t st) {
   PSF_TRY(launch_chunked(k_kg_chains<NW>, a.count * a.leaves * a.len, a, st));
   PSF_TRY(launch_chunked(k_kg_leaf<NW>, a.count * a.leaves, a, st));
@@ -330,7 +319,6 @@ psf_status verify_check(int param, size_t count, const VerifyIn& in, uint8_t* ok
   return dsa::grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
 }
 
-// host rows of `len` bytes at `stride` -> packed device rows
 hipError_t upload_rows(void* d, const void* h, size_t count, size_t len, size_t stride) {
   if (count == 0 || len == 0) return hipSuccess;
   return stride == len ? hipMemcpy(d, h, count * len, hipMemcpyHostToDevice) : hipMemcpy2D(d, len, h, stride, len, count, hipMemcpyHostToDevice);
