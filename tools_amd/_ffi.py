@@ -6,6 +6,8 @@ compute entry point raises.  The oracle under oracle/ is never imported from her
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PSF_LIB") or os.path.join(_HERE, "lib", "libpsf_mi355x.so")   # PSF_LIB: another build of the same ABI (the experiments build, A/B builds)
 EXP_LIB_PATH = os.path.join(_HERE, "lib", "libpsf_mi355x_exp.so")                          # `make exp`: every PSF_* experiment switch alive (tests, tools/); never loaded by default
@@ -121,3 +123,17 @@ def _p(a, t):
 def check(status, where=""):
     if status != OK:
         raise PsfError(status, where)
+
+
+def _vp(a):
+    """The data of a numpy array as a void pointer; None (NULL) for no array or an empty one."""
+    return C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+
+
+def _rows(items, size, what, who):
+    """Byte strings of `size` bytes each as the rows of one packed uint8 array; `who` names the module in the error."""
+    items = [bytes(x) for x in items]
+    for x in items:
+        if len(x) != size:
+            raise ValueError(f"{who}: {what} of {len(x)} bytes, expected {size}")
+    return np.frombuffer(b"".join(items), dtype=np.uint8).reshape(len(items), size).copy()

@@ -5,13 +5,12 @@
 // Every map is one pass over a flat array of coefficients: memory-bound streams, 16-byte non-temporal loads and stores per lane.
 // Exact integer arithmetic without a division on the device: the host precomputes the constants of each call (DESIGN.md "Compression and
 // message encodings").
+#include "psf_call_host.hpp"
 #include "psf_hip_util.hpp"
 #include "psf_stream_host.hpp"
 
 namespace psf {
 namespace cmp {
-
-typedef unsigned __int128 u128;
 
 enum { OP_COMPRESS = 0, OP_DECOMPRESS = 1, OP_ENCODE = 2, OP_DECODE = 3 };
 
@@ -434,11 +433,6 @@ __global__ __launch_bounds__(256) void k_unpack(CmpArgs a, const uint8_t* __rest
 
 enum { BY_ENCODE = 0, BY_DECODE = 1, BY_COMPRESS_ENCODE = 2, BY_DECODE_DECOMPRESS = 3 };
 
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return na && nb && pa < pb + nb && pb < pa + na;
-}
-
 // argument checks of the eight byte-encoding entry points, every PSF_ERR_PARAM before every PSF_ERR_UNSUPPORTED; *nbytes = ceil(len d / 8)
 psf_status check_bytes(int kind, uint64_t q, uint32_t d, size_t len, const void* vals, const void* bytes, int io_bits, size_t* nbytes) {
   if (d < 1 || (io_bits != 16 && io_bits != 64)) return PSF_ERR_PARAM;
@@ -446,7 +440,7 @@ psf_status check_bytes(int kind, uint64_t q, uint32_t d, size_t len, const void*
   const size_t wb = (size_t)io_bits / 8;
   if (len > SIZE_MAX / d || len > SIZE_MAX / wb) return PSF_ERR_PARAM;
   *nbytes = len * d / 8 + (len * d % 8 != 0);
-  if (ranges_overlap(vals, len * wb, bytes, *nbytes)) return PSF_ERR_PARAM;
+  if (overlap(vals, len * wb, bytes, *nbytes)) return PSF_ERR_PARAM;
   if (kind == BY_DECODE && q == 1) return PSF_ERR_PARAM;
   if ((kind == BY_COMPRESS_ENCODE || kind == BY_DECODE_DECOMPRESS) && q < 2) return PSF_ERR_PARAM;
   if (d > 63 || (io_bits == 16 && d > 16)) return PSF_ERR_UNSUPPORTED;

@@ -3,6 +3,7 @@
 // between FIPS 203's NTT-domain representation and the images of psf_ntt_forward_dev at (3329, 256).
 // One Keccak state per LANE (psf_keccak_core.hpp): `count` independent messages, 25 lanes of 64 bits in registers, no LDS for the state and no
 // cross-lane traffic.  Every loop is bounded (message blocks, digest blocks, at most 8 blocks of SampleNTT) and no kernel waits on another workgroup.
+#include "psf_call.hpp"
 #include "psf_hip_util.hpp"
 #include "psf_stream_host.hpp"
 #include "psf_host.hpp"
@@ -115,23 +116,6 @@ template <int IO> __global__ __launch_bounds__(256) void k_image_to(ImgArgs m, c
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
-constexpr unsigned kMaxGrid = 0x7fffffffu;
-
-// `count` items of `len` bytes, item c at base + c stride: the bytes from the first of item 0 to the last of item count - 1.  false: stride < len or
-// the span (or its end address) does not fit size_t.
-bool span_of(const void* base, size_t count, size_t len, size_t stride, size_t* span) {
-  *span = 0;
-  if (stride < len) return false;
-  if (count == 0 || len == 0) return true;
-  if (count - 1 > (SIZE_MAX - len) / (stride ? stride : 1)) return false;
-  *span = (count - 1) * stride + len;
-  return *span <= SIZE_MAX - (uintptr_t)base;
-}
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  if (na == 0 || nb == 0) return false;
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + nb && pb < pa + na;
-}
 // the pointer, stride, overflow and overlap rules every entry point shares: input items (in may be NULL when in_len = 0), output items
 psf_status check_io(size_t count, const void* in, size_t in_len, size_t in_stride, const void* out, size_t out_len, size_t out_stride, size_t* in_span,
                     size_t* out_span) {
@@ -171,16 +155,6 @@ psf_status keccak_launch(int device, const FuncSpec& f, size_t count, const uint
   });
   HIP_TRY(hipGetLastError());
   return PSF_OK;
-}
-
-// host rows of `len` bytes at `stride` <-> packed device rows
-hipError_t upload_rows(void* d, const void* h, size_t count, size_t len, size_t stride) {
-  if (count == 0 || len == 0) return hipSuccess;
-  return stride == len ? hipMemcpy(d, h, count * len, hipMemcpyHostToDevice) : hipMemcpy2D(d, len, h, stride, len, count, hipMemcpyHostToDevice);
-}
-hipError_t download_rows(void* h, const void* d, size_t count, size_t len, size_t stride) {
-  if (count == 0 || len == 0) return hipSuccess;
-  return stride == len ? hipMemcpy(h, d, count * len, hipMemcpyDeviceToHost) : hipMemcpy2D(h, stride, d, len, len, count, hipMemcpyDeviceToHost);
 }
 
 // SampleNTT: the seed length by form, the number of polynomials, the checks
@@ -270,8 +244,7 @@ psf_status image_host(int device, size_t count, const void* fhat, const uint32_t
   if (overlap(fhat, count * kN * 8, hat, count * kN * 4)) return PSF_ERR_PARAM;
   if (!image_map().ok) return PSF_ERR_UNSUPPORTED;
   if (count == 0) return PSF_OK;
-  const psf_status ud = use_device(device);
-  if (ud != PSF_OK) return ud;
+  PSF_TRY(use_device(device));
   DevBuf df, dh;
   HIP_TRY(df.alloc(count * kN * 8));
   HIP_TRY(dh.alloc(count * kN * 4));
@@ -306,16 +279,13 @@ psf_status psf_keccak(int device, int func, size_t count, const uint8_t* in, siz
   size_t in_span = 0, out_span = 0;
   const psf_status rc = check_keccak(func, count, in, in_len, in_stride, out, out_len, out_stride, &f, &in_span, &out_span);
   if (rc != PSF_OK || count == 0) return rc;
-  const psf_status ud = use_device(device);
-  if (ud != PSF_OK) return ud;
-  DevBuf din, dout;                                                      // packed rows on the device
-  if (in_len) HIP_TRY(din.alloc(count * in_len));
-  HIP_TRY(dout.alloc(count * out_len));
-  HIP_TRY(upload_rows(din.as<void>(), in, count, in_len, in_stride));
-  const psf_status rl = keccak_launch(device, f, count, din.as<uint8_t>(), in_len, in_len, dout.as<uint8_t>(), out_len, out_len, nullptr);
-  if (rl != PSF_OK) return rl;
-  HIP_TRY(download_rows(out, dout.as<void>(), count, out_len, out_stride));
-  return PSF_OK;
+  PSF_TRY(use_device(device));
+  HostCall h;                                                            // packed rows on the device
+  const uint8_t* din = h.in(in, count, in_len, in_stride);
+  uint8_t* dout = h.out(count * out_len);
+  PSF_TRY(h.status());
+  PSF_TRY(keccak_launch(device, f, count, din, in_len, in_len, dout, out_len, out_len, nullptr));
+  return h.fetch(out, dout, count, out_len, out_stride);
 }
 
 psf_status psf_sample_ntt_fips203_dev(int device, size_t count, uint32_t k, const uint8_t* d_seed, size_t seed_stride, void* d_out, int* d_fail, int io_bits,
@@ -330,21 +300,16 @@ psf_status psf_sample_ntt_fips203(int device, size_t count, uint32_t k, const ui
   size_t total = 0, seed_span = 0;
   const psf_status rc = check_sample_ntt(count, k, seed, seed_stride, out, 64, &total, &seed_span);
   if (rc != PSF_OK || total == 0) return rc;
-  const psf_status ud = use_device(device);
-  if (ud != PSF_OK) return ud;
+  PSF_TRY(use_device(device));
   const size_t len = k ? 32 : 34, bytes = total * kN * sizeof(uint64_t);
-  DevBuf dseed, dout, dflag;
-  HIP_TRY(dseed.alloc(count * len));
-  HIP_TRY(dout.alloc(bytes));
-  HIP_TRY(dflag.alloc(sizeof(int)));
-  HIP_TRY(dflag.zero(sizeof(int)));
-  HIP_TRY(upload_rows(dseed.as<void>(), seed, count, len, seed_stride));
-  const psf_status rl = sample_ntt_launch(device, total, k, dseed.as<uint8_t>(), len, dout.as<void>(), dflag.as<int>(), 64, nullptr);
-  if (rl != PSF_OK) return rl;
-  HIP_TRY(dout.download(out, bytes));
-  int fl = 0;
-  HIP_TRY(dflag.download(&fl, sizeof(int)));
-  return fl ? PSF_ERR_SAMPLER : PSF_OK;
+  HostCall h;
+  const uint8_t* dseed = h.in(seed, count, len, seed_stride);
+  uint8_t* dout = h.out(bytes);
+  int* dflag = h.flag();
+  PSF_TRY(h.status());
+  PSF_TRY(sample_ntt_launch(device, total, k, dseed, len, dout, dflag, 64, nullptr));
+  PSF_TRY(h.fetch(out, dout, bytes));
+  return h.finish();
 }
 
 psf_status psf_sample_cbd_fips203_dev(int device, size_t count, uint32_t eta, const uint8_t* d_sigma, size_t sigma_stride, uint32_t first_nonce, uint32_t per_seed,
@@ -360,17 +325,14 @@ psf_status psf_sample_cbd_fips203(int device, size_t count, uint32_t eta, const 
   size_t total = 0, sigma_span = 0;
   const psf_status rc = check_sample_cbd(count, eta, sigma, sigma_stride, first_nonce, per_seed, out, 64, &total, &sigma_span);
   if (rc != PSF_OK || total == 0) return rc;
-  const psf_status ud = use_device(device);
-  if (ud != PSF_OK) return ud;
+  PSF_TRY(use_device(device));
   const size_t bytes = total * kN * sizeof(int64_t);
-  DevBuf dsigma, dout;
-  HIP_TRY(dsigma.alloc(count * 32));
-  HIP_TRY(dout.alloc(bytes));
-  HIP_TRY(upload_rows(dsigma.as<void>(), sigma, count, 32, sigma_stride));
-  const psf_status rl = sample_cbd_launch(device, total, eta, dsigma.as<uint8_t>(), 32, first_nonce, per_seed, dout.as<void>(), 64, nullptr);
-  if (rl != PSF_OK) return rl;
-  HIP_TRY(dout.download(out, bytes));
-  return PSF_OK;
+  HostCall h;
+  const uint8_t* dsigma = h.in(sigma, count, 32, sigma_stride);
+  uint8_t* dout = h.out(bytes);
+  PSF_TRY(h.status());
+  PSF_TRY(sample_cbd_launch(device, total, eta, dsigma, 32, first_nonce, per_seed, dout, 64, nullptr));
+  return h.fetch(out, dout, bytes);
 }
 
 psf_status psf_ntt_image_from_fips203_dev(int device, size_t count, const void* d_fhat, int io_bits, uint32_t* d_hat, void* stream) {

@@ -175,6 +175,19 @@ template <int RATE, class Ops, class Wr> PSF_KC_FN void squeeze(uint64_t (&s)[25
   }
 }
 
+// what the kernels with a state of their own do around absorb: the empty state, words of the state as bytes, the `aligned` of a reader over rows
+PSF_KC_FN void zero_state(uint64_t (&s)[25]) {
+#pragma unroll
+  for (int i = 0; i < 25; ++i) s[i] = 0;
+}
+// words s[first ... first + COUNT - 1] of a state as 8 COUNT bytes at p
+template <int FIRST, int COUNT> PSF_KC_FN void put_words(const uint64_t (&s)[25], uint8_t* p) {
+  const PtrWriter wr{p, (uintptr_t)p % 8 == 0};
+#pragma unroll
+  for (int i = 0; i < COUNT; ++i) wr.put64(8 * i, s[FIRST + i]);
+}
+PSF_KC_FN bool aligned8(const void* p, size_t pitch) { return ((uintptr_t)p | pitch) % 8 == 0; }
+
 template <int RATE, class Ops, class Rd, class Wr>
 PSF_KC_FN void hash(const Rd& rd, size_t in_len, uint32_t dom, const Wr& wr, size_t out_len) {
   uint64_t s[25];

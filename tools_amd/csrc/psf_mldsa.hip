@@ -16,6 +16,7 @@
 //   k_verify_tail  UseHint, w1Encode and SHAKE256(mu || w1) in one lane per instance, w1 never in memory; the comparison with c~; ok and why
 // One lane per unit of work and one Keccak state per lane throughout.  Everything secret of KeyGen lives in the caller's workspace, which the last
 // operation of the call clears; verification has no secret (DESIGN.md "ML-DSA").
+#include "psf_call.hpp"
 #include "psf_hip_util.hpp"
 #include "psf_host.hpp"
 #include "psf_keccak_core.hpp"
@@ -322,89 +323,37 @@ const ImageMap& image_map() {
   return m;
 }
 
-struct KeygenWs { size_t rho_p, a_hat, s1, s2, t, total; bool ok; };
-struct VerifyWs { size_t tr, mu, flags, h, a_hat, z, t1, c, w, total; bool ok; };
+// the workspaces: sections in a fixed order (Layout).  A polynomial of 64-bit words takes 2048 bytes, an image 1024 bytes.
+struct KeygenWs : Layout { size_t rho_p, a_hat, s1, s2, t; };
+struct VerifyWs : Layout { size_t tr, mu, flags, h, a_hat, z, t1, c, w; };
 KeygenWs keygen_ws(const Set& s, size_t count) {
-  Layout l;
   KeygenWs w;
   const u128 c = count, k = s.k, el = s.l;
-  w.rho_p = l.take(c * 64);
-  w.a_hat = l.take(c * k * el * 1024);
-  w.s1 = l.take(c * el * 2048);
-  w.s2 = l.take(c * k * 2048);
-  w.t = l.take(c * k * 2048);
-  w.total = l.total;
-  w.ok = l.ok;
+  w.rho_p = w.take(c * 64);
+  w.a_hat = w.take(c * k * el * 1024);
+  w.s1 = w.take(c * el * 2048);
+  w.s2 = w.take(c * k * 2048);
+  w.t = w.take(c * k * 2048);
   return w;
 }
 // sized for one key per instance; with one key for all, the sections of tr, the images and t1 are used for one instance only
 VerifyWs verify_ws(const Set& s, size_t count) {
-  Layout l;
   VerifyWs w;
   const u128 c = count, k = s.k, el = s.l;
-  w.tr = l.take(c * 64);
-  w.mu = l.take(c * 64);
-  w.flags = l.take(c * 4);
-  w.h = l.take(c * k * 32);
-  w.a_hat = l.take(c * k * el * 1024);
-  w.z = l.take(c * el * 2048);
-  w.t1 = l.take(c * k * 2048);
-  w.c = l.take(c * 2048);
-  w.w = l.take(c * k * 2048);
-  w.total = l.total;
-  w.ok = l.ok;
+  w.tr = w.take(c * 64);
+  w.mu = w.take(c * 64);
+  w.flags = w.take(c * 4);
+  w.h = w.take(c * k * 32);
+  w.a_hat = w.take(c * k * el * 1024);
+  w.z = w.take(c * el * 2048);
+  w.t1 = w.take(c * k * 2048);
+  w.c = w.take(c * 2048);
+  w.w = w.take(c * k * 2048);
   return w;
 }
-bool ws_need(const Set& s, size_t count, int op, size_t* need) {
-  bool ok = true;
-  *need = 0;
-  if (op == PSF_MLDSA_OP_KEYGEN) { const KeygenWs w = keygen_ws(s, count); ok = w.ok; *need = w.total; }
-  if (op == PSF_MLDSA_OP_VERIFY) { const VerifyWs w = verify_ws(s, count); ok = w.ok; *need = w.total; }
-  return ok;
-}
-
-// `count` items of `len` bytes, item c at base + c stride (stride 0: one item): the bytes from the first of item 0 to the last of the last item;
-// false: the span or its end address does not fit size_t
-bool span_of(const void* base, size_t count, size_t len, size_t stride, size_t* span) {
-  *span = 0;
-  if (count == 0 || len == 0) return true;
-  if (stride && count - 1 > (SIZE_MAX - len) / stride) return false;
-  *span = (count - 1) * stride + len;
-  return *span <= SIZE_MAX - (uintptr_t)base;
-}
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  if (na == 0 || nb == 0) return false;
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + nb && pb < pa + na;
-}
-// the header's order after `param`, `op`, `msg_kind` and count = 0: NULL pointers, [strides: the caller], byte counts, the workspace (device forms), overlaps
-psf_status check_null(const Buf* b, int nb) {
-  for (int i = 0; i < nb; ++i)
-    if (!b[i].p && !b[i].ok_null) return PSF_ERR_PARAM;
-  return PSF_OK;
-}
-psf_status check_spans(size_t count, Buf* b, int nb) {
-  for (int i = 0; i < nb; ++i)
-    if (!span_of(b[i].p, count, b[i].len, b[i].stride, &b[i].span)) return PSF_ERR_PARAM;
-  return PSF_OK;
-}
-psf_status check_ws(bool dev, const void* ws, size_t ws_bytes, size_t need) {
-  return dev && (!ws || (uintptr_t)ws % 256 != 0 || ws_bytes < need) ? PSF_ERR_PARAM : PSF_OK;       // the host forms allocate their own
-}
-psf_status check_overlaps(const Buf* b, int nb, bool dev, const void* ws, size_t need) {
-  for (int i = 0; i < nb; ++i) {
-    if (!b[i].out || !b[i].p) continue;
-    for (int j = 0; j < nb; ++j)
-      if (j != i && b[j].p && overlap(b[i].p, b[i].span, b[j].p, b[j].span)) return PSF_ERR_PARAM;
-    if (dev && overlap(b[i].p, b[i].span, ws, need)) return PSF_ERR_PARAM;
-  }
-  return PSF_OK;
-}
-psf_status check_rest(const Set& s, size_t count, Buf* b, int nb, int op, bool dev, const void* ws, size_t ws_bytes, size_t* need) {
-  PSF_TRY(check_spans(count, b, nb));
-  if (!ws_need(s, count, op, need)) return PSF_ERR_PARAM;
-  PSF_TRY(check_ws(dev, ws, ws_bytes, *need));
-  return check_overlaps(b, nb, dev, ws, *need);
+Layout ws_need(const Set& s, size_t count, int op) {
+  if (op == PSF_MLDSA_OP_KEYGEN) return keygen_ws(s, count);
+  return verify_ws(s, count);
 }
 
 // ---- launches of the stages (arguments checked by the caller; `device` is current) ------------------------------------------------------------------
@@ -531,13 +480,14 @@ psf_status verify_run(int device, const Set& s, size_t count, const VerifyIn& in
 }
 
 // ---- argument checks of the entry points -----------------------------------------------------------------------------------------------------------
-struct Checked { Set s; size_t need; };
+struct Checked { Set s; Layout need; };
 psf_status keygen_check(int param, size_t count, const uint8_t* xi, uint8_t* pk, uint8_t* sk, bool dev, const void* ws, size_t ws_bytes, Checked* kc_) {
   if (!set_of(param, &kc_->s)) return PSF_ERR_PARAM;
   if (count == 0) return PSF_OK;
   Buf b[3] = {{xi, 32, 32, false, false, 0}, {pk, kc_->s.pk, kc_->s.pk, true, false, 0}, {sk, kc_->s.sk, kc_->s.sk, true, false, 0}};
   PSF_TRY(check_null(b, 3));
-  PSF_TRY(check_rest(kc_->s, count, b, 3, PSF_MLDSA_OP_KEYGEN, dev, ws, ws_bytes, &kc_->need));
+  kc_->need = ws_need(kc_->s, count, PSF_MLDSA_OP_KEYGEN);
+  PSF_TRY(check_rest(count, b, 3, kc_->need, dev, ws, ws_bytes));
   return grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
 }
 psf_status verify_check(int param, size_t count, const VerifyIn& in, uint8_t* ok, uint8_t* why, bool dev, const void* ws, size_t ws_bytes, Checked* kc_) {
@@ -550,14 +500,9 @@ psf_status verify_check(int param, size_t count, const VerifyIn& in, uint8_t* ok
   if ((in.pk_stride != 0 && in.pk_stride < s.pk) || in.msg_stride < in.msg_len) return PSF_ERR_PARAM;
   if (in.msg_kind == PSF_MLDSA_MSG_MU && in.msg_len != 64) return PSF_ERR_PARAM;
   if (in.msg_len > SIZE_MAX - 64) return PSF_ERR_PARAM;
-  PSF_TRY(check_rest(s, count, b, 5, PSF_MLDSA_OP_VERIFY, dev, ws, ws_bytes, &kc_->need));
+  kc_->need = ws_need(s, count, PSF_MLDSA_OP_VERIFY);
+  PSF_TRY(check_rest(count, b, 5, kc_->need, dev, ws, ws_bytes));
   return grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
-}
-
-// host rows of `len` bytes at `stride` -> packed device rows, and back
-hipError_t upload_rows(void* d, const void* h, size_t count, size_t len, size_t stride) {
-  if (count == 0 || len == 0) return hipSuccess;
-  return stride == len ? hipMemcpy(d, h, count * len, hipMemcpyHostToDevice) : hipMemcpy2D(d, len, h, stride, len, count, hipMemcpyHostToDevice);
 }
 
 // the checks every stage shares: pointers, strides, sizes, overlap of the seeds with the output
@@ -597,17 +542,14 @@ psf_status check_image(size_t count, const uint64_t* fhat, const uint32_t* hat) 
 // a stage on host buffers: packed device copies of the seeds, the output, the flag
 template <class Launch> psf_status stage_host(int device, size_t count, const void* seed, size_t seed_len, size_t seed_stride, void* out, size_t out_bytes, Launch&& launch) {
   PSF_TRY(use_device(device));
-  DevBuf dseed, dout, dflag;
-  if (count * seed_len) HIP_TRY(dseed.alloc(count * seed_len));
-  HIP_TRY(dout.alloc(out_bytes));
-  HIP_TRY(dflag.alloc(sizeof(int)));
-  HIP_TRY(dflag.zero(sizeof(int)));
-  HIP_TRY(upload_rows(dseed.as<void>(), seed, count, seed_len, seed_stride));
-  PSF_TRY(launch(dseed.as<uint8_t>(), dout.as<void>(), dflag.as<int>()));
-  HIP_TRY(dout.download(out, out_bytes));
-  int fl = 0;
-  HIP_TRY(dflag.download(&fl, sizeof(int)));
-  return fl ? PSF_ERR_SAMPLER : PSF_OK;
+  HostCall h;
+  const uint8_t* dseed = h.in(seed, count, seed_len, seed_stride);                  // stage_check: seed_stride >= seed_len
+  uint8_t* dout = h.out(out_bytes);
+  int* dflag = h.flag();
+  PSF_TRY(h.status());
+  PSF_TRY(launch(dseed, dout, dflag));
+  PSF_TRY(h.fetch(out, dout, out_bytes));
+  return h.finish();
 }
 
 }  // namespace dsa
@@ -630,9 +572,9 @@ psf_status psf_mldsa_sizes(int param, size_t* pk, size_t* sk, size_t* sig) {
 psf_status psf_mldsa_workspace_bytes(int param, size_t count, int op, size_t* bytes) {
   Set s;
   if (!set_of(param, &s) || (op != PSF_MLDSA_OP_KEYGEN && op != PSF_MLDSA_OP_VERIFY) || !bytes) return PSF_ERR_PARAM;
-  size_t need = 0;
-  if (!ws_need(s, count, op, &need)) return PSF_ERR_PARAM;
-  *bytes = need;
+  const Layout need = ws_need(s, count, op);
+  if (!need.ok) return PSF_ERR_PARAM;
+  *bytes = need.total;
   return PSF_OK;
 }
 
@@ -659,20 +601,16 @@ psf_status psf_mldsa_keygen(int device, int param, size_t count, const uint8_t* 
   if (rc != PSF_OK || count == 0) return rc;
   PSF_TRY(use_device(device));
   const Set& s = kc_.s;
-  DevBuf dxi, dpk, dsk, dws, dflag;
-  HIP_TRY(dxi.alloc(count * 32));
-  HIP_TRY(dpk.alloc(count * s.pk));
-  HIP_TRY(dsk.alloc(count * s.sk));
-  HIP_TRY(dws.alloc(kc_.need));
-  HIP_TRY(dflag.alloc(sizeof(int)));
-  HIP_TRY(dflag.zero(sizeof(int)));
-  HIP_TRY(dxi.upload(xi, count * 32));
-  PSF_TRY(keygen_run(device, s, count, dxi.as<uint8_t>(), dpk.as<uint8_t>(), dsk.as<uint8_t>(), dws.as<void>(), keygen_ws(s, count), dflag.as<int>(), nullptr));
-  HIP_TRY(dpk.download(pk, count * s.pk));
-  HIP_TRY(dsk.download(sk, count * s.sk));
-  int fl = 0;
-  HIP_TRY(dflag.download(&fl, sizeof(int)));
-  return fl ? PSF_ERR_SAMPLER : PSF_OK;
+  HostCall h;
+  const uint8_t* dxi = h.in(xi, count, 32, 32, SECRET);
+  uint8_t *dpk = h.out(count * s.pk), *dsk = h.out(count * s.sk, SECRET);
+  void* dws = h.workspace(kc_.need.total);
+  int* dflag = h.flag();
+  PSF_TRY(h.status());
+  PSF_TRY(keygen_run(device, s, count, dxi, dpk, dsk, dws, keygen_ws(s, count), dflag, nullptr));
+  PSF_TRY(h.fetch(pk, dpk, count * s.pk));
+  PSF_TRY(h.fetch(sk, dsk, count * s.sk));
+  return h.finish();
 }
 
 psf_status psf_mldsa_verify(int device, int param, size_t count, const uint8_t* pk, size_t pk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
@@ -683,26 +621,16 @@ psf_status psf_mldsa_verify(int device, int param, size_t count, const uint8_t* 
   if (rc != PSF_OK || count == 0) return rc;
   PSF_TRY(use_device(device));
   const Set& s = kc_.s;
-  const size_t keys = pk_stride ? count : 1;
-  DevBuf dpk, dmsg, dsig, dok, dwhy, dws, dflag;
-  HIP_TRY(dpk.alloc(keys * s.pk));
-  if (msg_len) HIP_TRY(dmsg.alloc(count * msg_len));
-  HIP_TRY(dsig.alloc(count * s.sig));
-  HIP_TRY(dok.alloc(count));
-  HIP_TRY(dwhy.alloc(count));
-  HIP_TRY(dws.alloc(kc_.need));
-  HIP_TRY(dflag.alloc(sizeof(int)));
-  HIP_TRY(dflag.zero(sizeof(int)));
-  HIP_TRY(upload_rows(dpk.as<void>(), pk, keys, s.pk, pk_stride ? pk_stride : s.pk));
-  HIP_TRY(upload_rows(dmsg.as<void>(), msg, count, msg_len, msg_stride));
-  HIP_TRY(dsig.upload(sig, count * s.sig));
-  const VerifyIn din{dpk.as<uint8_t>(), pk_stride ? s.pk : 0, dmsg.as<uint8_t>(), msg_len, msg_len, msg_kind, dsig.as<uint8_t>()};
-  PSF_TRY(verify_run(device, s, count, din, dok.as<uint8_t>(), dwhy.as<uint8_t>(), dws.as<void>(), verify_ws(s, count), dflag.as<int>(), nullptr));
-  HIP_TRY(dok.download(ok, count));
-  if (why) HIP_TRY(dwhy.download(why, count));
-  int fl = 0;
-  HIP_TRY(dflag.download(&fl, sizeof(int)));
-  return fl ? PSF_ERR_SAMPLER : PSF_OK;
+  HostCall h;
+  const VerifyIn din{h.in(pk, count, s.pk, pk_stride), pk_stride ? s.pk : 0, h.in(msg, count, msg_len, msg_stride), msg_len, msg_len, msg_kind, h.in(sig, count, s.sig, s.sig)};
+  uint8_t *dok = h.out(count), *dwhy = h.out(count);
+  void* dws = h.workspace(kc_.need.total);
+  int* dflag = h.flag();
+  PSF_TRY(h.status());
+  PSF_TRY(verify_run(device, s, count, din, dok, dwhy, dws, verify_ws(s, count), dflag, nullptr));
+  PSF_TRY(h.fetch(ok, dok, count));
+  PSF_TRY(h.fetch(why, dwhy, count));
+  return h.finish();
 }
 
 // ---- the stages ------------------------------------------------------------------------------------------------------------------------------------

@@ -1,11 +1,12 @@
 // psf_mldsa_api.hpp -- what psf_mldsa.hip (ML-DSA KeyGen / Verify and the FIPS 204 stages) offers psf_mldsa_sign.hip (ML-DSA signing), as
-// psf_ntt_api.hpp does for the transforms: the parameter sets, the map between FIPS 204's NTT-domain order and the product images, the workspace
-// layout helper, the argument checks of a call's buffers, the launches of ExpandA, SampleInBall and the field (un)packing, and the reader that feeds
-// mu || w1Encode(...) to the sponge.  The functions are defined in psf_mldsa.hip; the templates and small structs live here.
+// psf_ntt_api.hpp does for the transforms: the parameter sets, the map between FIPS 204's NTT-domain order and the product images, the launches of
+// ExpandA, SampleInBall and the field (un)packing, and the readers that feed tr || M' and mu || w1Encode(...) to the sponge.  The functions are defined
+// in psf_mldsa.hip; the templates and small structs live here.  What is not ML-DSA's own (checks, layout, grid limits, host staging) is psf_call.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "psf_call.hpp"
 #include "psf_hip_util.hpp"
 #include "psf_keccak_core.hpp"
 #include "psf_mldsa_core.hpp"
@@ -13,17 +14,9 @@
 namespace psf {
 namespace dsa {
 
-__device__ __forceinline__ void zero_state(uint64_t (&s)[25]) {
-#pragma unroll
-  for (int i = 0; i < 25; ++i) s[i] = 0;
-}
-// words s[first ... first + COUNT - 1] of a state as 8 COUNT bytes at p
-template <int FIRST, int COUNT> __device__ __forceinline__ void put_words(const uint64_t (&s)[25], uint8_t* p) {
-  const kc::PtrWriter wr{p, (uintptr_t)p % 8 == 0};
-#pragma unroll
-  for (int i = 0; i < COUNT; ++i) wr.put64(8 * i, s[FIRST + i]);
-}
-__device__ __forceinline__ bool aligned8(const void* p, size_t pitch) { return ((uintptr_t)p | pitch) % 8 == 0; }
+using kc::aligned8;
+using kc::put_words;
+using kc::zero_state;
 
 // na bytes of a, then nb bytes of b.  fast: both start at multiples of 8 and so is na.
 struct CatReader {
@@ -52,46 +45,6 @@ bool set_of(int param, Set* s);
 // points of the library's plan with those of Algorithm 41 (zeta = 1753).  The change of scale is the reduction of any 64-bit value to [0, q).
 struct ImageMap { bool ok = false; uint8_t word_of[256] = {}, fips_of[256] = {}; };
 const ImageMap& image_map();
-
-// ---- the workspace ---------------------------------------------------------------------------------------------------------------------------------
-// The workspace of an operation: sections in a fixed order, each rounded up to 256 bytes.  A polynomial of 64-bit words takes 2048 bytes, an image
-// 1024 bytes.
-typedef unsigned __int128 u128;
-struct Layout {
-  size_t total = 0;
-  bool ok = true;
-  size_t take(u128 bytes) {
-    const size_t at = total;
-    const u128 end = (u128)total + ((bytes + 255) / 256) * 256;
-    if (end > (u128)SIZE_MAX) { ok = false; return 0; }
-    total = (size_t)end;
-    return at;
-  }
-};
-template <class T> T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<uint8_t*>(ws) + off); }
-
-// ---- the buffers of a call -------------------------------------------------------------------------------------------------------------------------
-// `count` items of `len` bytes, item c at base + c stride (stride 0: one item): the bytes from the first of item 0 to the last of the last item;
-// false: the span or its end address does not fit size_t
-bool span_of(const void* base, size_t count, size_t len, size_t stride, size_t* span);
-bool overlap(const void* a, size_t na, const void* b, size_t nb);
-// a buffer of a call: `count` items of `len` bytes at `stride`; ok_null: may be NULL (an empty message, d_why)
-struct Buf { const void* p; size_t len, stride; bool out, ok_null; size_t span; };
-// the header's order after `param`, `op`, `msg_kind` and count = 0: NULL pointers, [strides: the caller], byte counts, the workspace (device forms), overlaps
-psf_status check_null(const Buf* b, int nb);
-psf_status check_spans(size_t count, Buf* b, int nb);
-psf_status check_ws(bool dev, const void* ws, size_t ws_bytes, size_t need);
-psf_status check_overlaps(const Buf* b, int nb, bool dev, const void* ws, size_t need);
-
-#define PSF_TRY(expr)                      \
-  do {                                     \
-    const psf_status rc__ = (expr);        \
-    if (rc__ != PSF_OK) return rc__;       \
-  } while (0)
-
-constexpr unsigned kMaxGrid = 0x7fffffffu;
-inline unsigned blocks_of(size_t items, size_t per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-inline bool grid_fits(size_t count) { return count <= kMaxGrid; }
 
 // ---- launches of the stages (arguments checked by the caller; `device` is current) ------------------------------------------------------------------
 psf_status rej_ntt_launch(size_t total, uint32_t k, uint32_t l, const uint8_t* d_seed, size_t seed_stride, void* d_out, bool img, int* d_fail, hipStream_t st);

@@ -13,6 +13,7 @@
 //   k_sign_move     copies the state of each such slot into its hole
 //   k_sign_commit   *d_live = new_live
 // No kernel here branches or addresses on s1, s2, t0, y or a value of a rejected attempt; the accept bit of a whole attempt is the one exception.
+#include "psf_call.hpp"
 #include "psf_hip_util.hpp"
 #include "psf_host.hpp"
 #include "psf_keccak_core.hpp"
@@ -286,31 +287,28 @@ __global__ __launch_bounds__(256) void k_sign_commit(uint32_t* live, uint32_t* c
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------------
 // sk_stride = 0: the four image sections hold one key.  During begin the unpacked s1, s2, t0 (keys (l + 2 k) polynomials of 64-bit words) lie at y and
 // run on into w, c, z, ct0, which follow without a gap: count (2 l + 2 k + 1) polynomials.
-struct SignWs { size_t a_hat, s1, s2, t0, mu, rho, kappa, index, ctl, y, w, c, z, ct0, ct, flags, holes, srcs, total; bool ok; };
+struct SignWs : Layout { size_t a_hat, s1, s2, t0, mu, rho, kappa, index, ctl, y, w, c, z, ct0, ct, flags, holes, srcs; };
 SignWs sign_ws(const Set& s, size_t count, bool per_key) {
-  Layout l;
   SignWs w;
   const u128 c = count, keys = per_key ? count : (count ? 1 : 0), k = s.k, el = s.l;
-  w.a_hat = l.take(keys * k * el * 1024);
-  w.s1 = l.take(keys * el * 1024);
-  w.s2 = l.take(keys * k * 1024);
-  w.t0 = l.take(keys * k * 1024);
-  w.mu = l.take(c * 64);
-  w.rho = l.take(c * 64);
-  w.kappa = l.take(c * 4);
-  w.index = l.take(c * 4);
-  w.ctl = l.take(count ? CTL_WORDS * 4 : 0);
-  w.y = l.take(c * el * 2048);
-  w.w = l.take(c * k * 2048);
-  w.c = l.take(c * 2048);
-  w.z = l.take(c * el * 2048);
-  w.ct0 = l.take(c * k * 2048);
-  w.ct = l.take(c * 64);
-  w.flags = l.take(c * 4);
-  w.holes = l.take(c * 4);
-  w.srcs = l.take(c * 4);
-  w.total = l.total;
-  w.ok = l.ok;
+  w.a_hat = w.take(keys * k * el * 1024);
+  w.s1 = w.take(keys * el * 1024);
+  w.s2 = w.take(keys * k * 1024);
+  w.t0 = w.take(keys * k * 1024);
+  w.mu = w.take(c * 64);
+  w.rho = w.take(c * 64);
+  w.kappa = w.take(c * 4);
+  w.index = w.take(c * 4);
+  w.ctl = w.take(count ? CTL_WORDS * 4 : 0);
+  w.y = w.take(c * el * 2048);
+  w.w = w.take(c * k * 2048);
+  w.c = w.take(c * 2048);
+  w.z = w.take(c * el * 2048);
+  w.ct0 = w.take(c * k * 2048);
+  w.ct = w.take(c * 64);
+  w.flags = w.take(c * 4);
+  w.holes = w.take(c * 4);
+  w.srcs = w.take(c * 4);
   return w;
 }
 
@@ -396,12 +394,9 @@ psf_status begin_check(int param, size_t count, const SignIn& in, bool dev, cons
   if (!stride_ok(s, in.sk_stride) || in.msg_stride < in.msg_len) return PSF_ERR_PARAM;
   if (in.msg_kind == PSF_MLDSA_MSG_MU && in.msg_len != 64) return PSF_ERR_PARAM;
   if (in.msg_len > SIZE_MAX - 64) return PSF_ERR_PARAM;
-  PSF_TRY(check_spans(count, b, nb));
   ck->w = sign_ws(s, count, in.sk_stride != 0);
-  if (!ck->w.ok) return PSF_ERR_PARAM;
-  PSF_TRY(check_ws(dev, ws, ws_bytes, ck->w.total));
+  PSF_TRY(check_rest(count, b, nb, ck->w, dev, ws, ws_bytes));
   if (dev && (uintptr_t)live % 4 != 0) return PSF_ERR_PARAM;
-  PSF_TRY(check_overlaps(b, nb, dev, ws, ck->w.total));
   return grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
 }
 
@@ -413,12 +408,9 @@ psf_status round_check(int param, size_t count, size_t sk_stride, size_t active,
   Buf b[3] = {{sig, s.sig, s.sig, true, false, 0}, {rounds, 4, 4, true, true, 0}, {live, 4, 0, true, false, 0}};
   PSF_TRY(check_null(b, 3));
   if (!stride_ok(s, sk_stride) || active > count) return PSF_ERR_PARAM;
-  PSF_TRY(check_spans(count, b, 3));
   ck->w = sign_ws(s, count, sk_stride != 0);
-  if (!ck->w.ok) return PSF_ERR_PARAM;
-  PSF_TRY(check_ws(true, ws, ws_bytes, ck->w.total));
+  PSF_TRY(check_rest(count, b, 3, ck->w, true, ws, ws_bytes));
   if ((uintptr_t)live % 4 != 0 || (uintptr_t)rounds % 4 != 0) return PSF_ERR_PARAM;
-  PSF_TRY(check_overlaps(b, 3, true, ws, ck->w.total));
   return grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
 }
 
@@ -478,37 +470,27 @@ psf_status psf_mldsa_sign(int device, int param, size_t count, const uint8_t* sk
   if (rc != PSF_OK || count == 0) return rc;
   PSF_TRY(use_device(device));
   const Set& s = ck.s;
-  const size_t keys = sk_stride ? count : 1;
-  DevBuf dsk, dmsg, drnd, dsig, drounds, dws, dlive, dflag;
-  HIP_TRY(dsk.alloc(keys * s.sk));
-  if (msg_len) HIP_TRY(dmsg.alloc(count * msg_len));
-  if (rnd) HIP_TRY(drnd.alloc(count * 32));
-  HIP_TRY(dsig.alloc(count * s.sig));
-  HIP_TRY(drounds.alloc(count * 4));
-  HIP_TRY(dws.alloc(ck.w.total));
-  HIP_TRY(dlive.alloc(4));
-  HIP_TRY(dflag.alloc(sizeof(int)));
-  HIP_TRY(dflag.zero(sizeof(int)));
-  HIP_TRY(dsig.zero(count * s.sig));
-  HIP_TRY(drounds.zero(count * 4));
-  HIP_TRY(hipMemcpy2D(dsk.as<void>(), s.sk, sk, sk_stride ? sk_stride : s.sk, s.sk, keys, hipMemcpyHostToDevice));
-  if (msg_len) HIP_TRY(hipMemcpy2D(dmsg.as<void>(), msg_len, msg, msg_stride, msg_len, count, hipMemcpyHostToDevice));
-  if (rnd) HIP_TRY(drnd.upload(rnd, count * 32));
-  const SignIn din{dsk.as<uint8_t>(), sk_stride ? s.sk : 0, dmsg.as<uint8_t>(), msg_len, msg_len, msg_kind, rnd ? drnd.as<uint8_t>() : nullptr};
+  HostCall h;
   // the packed device copies change the layout only through sk_stride != 0, which din keeps
-  psf_status run = begin_run(device, s, count, din, dws.as<void>(), ck.w, dlive.as<uint32_t>(), dflag.as<int>(), nullptr);
+  const SignIn din{h.in(sk, count, s.sk, sk_stride, SECRET), sk_stride ? s.sk : 0, h.in(msg, count, msg_len, msg_stride), msg_len, msg_len, msg_kind,
+                   h.in(rnd, count, 32, 32, SECRET)};
+  uint8_t* dsig = h.out(count * s.sig, PUBLIC, true);
+  uint32_t *drounds = reinterpret_cast<uint32_t*>(h.out(count * 4, PUBLIC, true)), *dlive = reinterpret_cast<uint32_t*>(h.out(4));
+  void* dws = h.workspace(ck.w.total);
+  int* dflag = h.flag();
+  PSF_TRY(h.status());
+  psf_status run = begin_run(device, s, count, din, dws, ck.w, dlive, dflag, nullptr);
   uint32_t live = (uint32_t)count;
   for (uint32_t r = 0; run == PSF_OK && r < max_rounds && live != 0; ++r) {
-    run = round_run(device, s, count, sk_stride != 0, live, dsig.as<uint8_t>(), drounds.as<uint32_t>(), dws.as<void>(), ck.w, dlive.as<uint32_t>(), dflag.as<int>(), nullptr);
-    if (run == PSF_OK && dlive.download(&live, 4) != hipSuccess) run = PSF_ERR_HIP;
+    run = round_run(device, s, count, sk_stride != 0, live, dsig, drounds, dws, ck.w, dlive, dflag, nullptr);
+    if (run == PSF_OK) run = h.fetch(&live, dlive, 4);
   }
-  HIP_TRY(hipMemsetAsync(dws.as<void>(), 0, ck.w.total, nullptr));        // everything in the workspace but A_hat is secret: cleared on every path
+  HIP_TRY(hipMemsetAsync(dws, 0, ck.w.total, nullptr));                   // everything in the workspace but A_hat is secret: cleared on every path
   PSF_TRY(run);
-  HIP_TRY(dsig.download(sig, count * s.sig));
-  if (rounds) HIP_TRY(drounds.download(rounds, count * 4));
-  int fl = 0;
-  HIP_TRY(dflag.download(&fl, sizeof(int)));
-  return fl || live != 0 ? PSF_ERR_SAMPLER : PSF_OK;
+  PSF_TRY(h.fetch(sig, dsig, count * s.sig));
+  PSF_TRY(h.fetch(rounds, drounds, count * 4));
+  PSF_TRY(h.finish());
+  return live != 0 ? PSF_ERR_SAMPLER : PSF_OK;
 }
 
 }  // extern "C"

@@ -11,16 +11,20 @@
 //   k_decaps_tail  J(z || c), the comparison of c with c' and the selection of K, in one kernel
 //   k_check_ek / k_check_dk   the per-instance modulus check and hash check
 // Everything secret lives in the caller's workspace, which the last operation of every entry point clears (DESIGN.md "ML-KEM").
+#include "psf_call.hpp"
 #include "psf_hip_util.hpp"
 #include "psf_keccak_core.hpp"
 
 namespace psf {
 namespace mlkem {
 
+using kc::aligned8;
 using kc::kDomSha3;
 using kc::kDomShake;
 using kc::kN;
 using kc::kQ;
+using kc::put_words;
+using kc::zero_state;
 
 // ---- readers ---------------------------------------------------------------------------------------------------------------------------------
 // na bytes of a, then nb bytes of b, then the bytes of `tail`, least significant first.  fast: a and b are multiples of 8 and so is na, so every
@@ -45,18 +49,6 @@ struct CatReader {
   }
 };
 
-__device__ __forceinline__ void zero_state(uint64_t (&s)[25]) {
-#pragma unroll
-  for (int i = 0; i < 25; ++i) s[i] = 0;
-}
-// words s[first ... first + 3] of a state as 32 bytes at p
-template <int FIRST> __device__ __forceinline__ void put_words(const uint64_t (&s)[25], uint8_t* p) {
-  const kc::PtrWriter wr{p, (uintptr_t)p % 8 == 0};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) wr.put64(8 * i, s[FIRST + i]);
-}
-__device__ __forceinline__ bool aligned8(const void* p, size_t pitch) { return ((uintptr_t)p | pitch) % 8 == 0; }
-
 // ---- hashes ------------------------------------------------------------------------------------------------------------------------------------
 // (o0, o1) = G(a_c || b_c || tail): a_c is 32 bytes at a + c a_pitch, b_c nb bytes at b + c b_pitch; 32 bytes each to o0 + c o0_pitch and o1 + c o1_pitch
 struct GArgs {
@@ -74,8 +66,8 @@ __global__ __launch_bounds__(256) void k_g(GArgs g) {
   zero_state(s);
   const CatReader rd{g.a + c * g.a_pitch, g.b + c * g.b_pitch, 32, g.nb, g.tail, aligned8(g.a, g.a_pitch) && aligned8(g.b, g.b_pitch)};
   kc::absorb<kc::kRateSha3_512, kc::DevOps>(s, rd, g.len, kDomSha3);
-  put_words<0>(s, g.o0 + c * g.o0_pitch);
-  put_words<4>(s, g.o1 + c * g.o1_pitch);
+  put_words<0, 4>(s, g.o0 + c * g.o0_pitch);
+  put_words<4, 4>(s, g.o1 + c * g.o1_pitch);
 }
 
 // Encaps: h = H(ek_c) (kept in the workspace: public), (K, r) = G(m_c || h)
@@ -87,13 +79,13 @@ __global__ __launch_bounds__(256) void k_encaps_hash(EncHashArgs e) {
   zero_state(s);
   kc::absorb<kc::kRateSha3_256, kc::DevOps>(s, kc::PtrReader{e.ek + c * e.ek_len, aligned8(e.ek, e.ek_len)}, e.ek_len, kDomSha3);
   uint8_t* h = e.h + c * 32;
-  put_words<0>(s, h);
+  put_words<0, 4>(s, h);
   uint64_t g[25];
   zero_state(g);
   const CatReader rd{e.m + c * 32, h, 32, 32, 0, aligned8(e.m, 32)};     // h is read back by the lane that wrote it
   kc::absorb<kc::kRateSha3_512, kc::DevOps>(g, rd, 64, kDomSha3);
-  put_words<0>(g, e.K + c * 32);
-  put_words<4>(g, e.r + c * 32);
+  put_words<0, 4>(g, e.K + c * 32);
+  put_words<4, 4>(g, e.r + c * 32);
 }
 
 // KeyGen: dk_c = dk_pke || ek || H(ek) || z -- the two encodings are in place (k_pack); this adds rho, H(ek) and z
@@ -106,7 +98,7 @@ __global__ __launch_bounds__(256) void k_keygen_tail(KgTailArgs a) {
   uint64_t s[25];
   zero_state(s);
   kc::absorb<kc::kRateSha3_256, kc::DevOps>(s, kc::PtrReader{ek, aligned8(a.ek, a.ek_len)}, a.ek_len, kDomSha3);
-  put_words<0>(s, dk + 768 * a.k + 32);
+  put_words<0, 4>(s, dk + 768 * a.k + 32);
   for (int i = 0; i < 32; ++i) {
     dk[768 * a.k + i] = ek[384 * a.k + i];
     dk[768 * a.k + 64 + i] = a.z[c * 32 + i];
@@ -263,7 +255,7 @@ __global__ __launch_bounds__(256) void k_decaps_tail(TailArgs a) {
     const uint64_t k1 = kp[i];
     s[i] = k1 ^ (mask & (k1 ^ s[i]));
   }
-  if (p0 + lane < a.count) put_words<0>(s, a.ss + c * 32);
+  if (p0 + lane < a.count) put_words<0, 4>(s, a.ss + c * 32);
 }
 
 // ---- the input checks ----------------------------------------------------------------------------------------------------------------------------
@@ -295,9 +287,6 @@ __global__ __launch_bounds__(256) void k_check_dk(const uint8_t* dk, size_t dk_l
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------------
-constexpr unsigned kMaxGrid = 0x7fffffffu;
-typedef unsigned __int128 u128;
-
 struct Set { uint32_t k, eta1, eta2, du, dv; size_t ek, dk, ct; };
 bool set_of(int param, Set* s) {
   switch (param) {
@@ -315,122 +304,64 @@ bool set_of(int param, Set* s) {
 // The workspace of an operation: sections in a fixed order, each rounded up to 256 bytes.  `P` polynomials of 16-bit words take 512 P bytes, of image
 // words 1024 P bytes.  Sections that one library call reads or writes as a whole are adjacent ([A | t | s]: one image_from; [t | s]: one forward
 // transform and one image_to).
-struct Layout {
-  size_t total = 0;
-  bool ok = true;
-  size_t take(u128 bytes) {
-    const size_t at = total;
-    const u128 end = (u128)total + ((bytes + 255) / 256) * 256;
-    if (end > (u128)SIZE_MAX) { ok = false; return 0; }
-    total = (size_t)end;
-    return at;
-  }
-};
-struct KeygenWs { size_t sigma, a_fips, a_hat, e, ts, st_hat, st_fips, total; bool ok; };
-struct EncapsWs { size_t h, r, fips, hat, y, e1, e2, u, v, total; bool ok; };
-struct DecapsWs { size_t fips, hat, u2, v2, w, mp, kp, rp, y, e1, e2, u, v, cp, total; bool ok; };
+struct KeygenWs : Layout { size_t sigma, a_fips, a_hat, e, ts, st_hat, st_fips; };
+struct EncapsWs : Layout { size_t h, r, fips, hat, y, e1, e2, u, v; };
+struct DecapsWs : Layout { size_t fips, hat, u2, v2, w, mp, kp, rp, y, e1, e2, u, v, cp; };
 
 KeygenWs keygen_ws(const Set& s, size_t count) {
-  Layout l;
   KeygenWs w;
   const u128 c = count, k = s.k, poly = 512;
-  w.sigma = l.take(c * 32);
-  w.a_fips = l.take(c * k * k * poly);
-  w.a_hat = l.take(c * k * k * poly * 2);
-  w.e = l.take(c * k * poly);
-  w.ts = l.take(c * 2 * k * poly);
-  w.st_hat = l.take(c * 2 * k * poly * 2);
-  w.st_fips = l.take(c * 2 * k * poly);
-  w.total = l.total;
-  w.ok = l.ok;
+  w.sigma = w.take(c * 32);
+  w.a_fips = w.take(c * k * k * poly);
+  w.a_hat = w.take(c * k * k * poly * 2);
+  w.e = w.take(c * k * poly);
+  w.ts = w.take(c * 2 * k * poly);
+  w.st_hat = w.take(c * 2 * k * poly * 2);
+  w.st_fips = w.take(c * 2 * k * poly);
   return w;
 }
 EncapsWs encaps_ws(const Set& s, size_t count) {
-  Layout l;
   EncapsWs w;
   const u128 c = count, k = s.k, poly = 512;
-  w.h = l.take(c * 32);
-  w.r = l.take(c * 32);
-  w.fips = l.take(c * (k * k + k) * poly);
-  w.hat = l.take(c * (k * k + k) * poly * 2);
-  w.y = l.take(c * k * poly);
-  w.e1 = l.take(c * k * poly);
-  w.e2 = l.take(c * poly);
-  w.u = l.take(c * k * poly);
-  w.v = l.take(c * poly);
-  w.total = l.total;
-  w.ok = l.ok;
+  w.h = w.take(c * 32);
+  w.r = w.take(c * 32);
+  w.fips = w.take(c * (k * k + k) * poly);
+  w.hat = w.take(c * (k * k + k) * poly * 2);
+  w.y = w.take(c * k * poly);
+  w.e1 = w.take(c * k * poly);
+  w.e2 = w.take(c * poly);
+  w.u = w.take(c * k * poly);
+  w.v = w.take(c * poly);
   return w;
 }
 DecapsWs decaps_ws(const Set& s, size_t count) {
-  Layout l;
   DecapsWs w;
   const u128 c = count, k = s.k, poly = 512;
-  w.fips = l.take(c * (k * k + 2 * k) * poly);
-  w.hat = l.take(c * (k * k + 2 * k) * poly * 2);
-  w.u2 = l.take(c * k * poly);
-  w.v2 = l.take(c * poly);
-  w.w = l.take(c * poly);
-  w.mp = l.take(c * 32);
-  w.kp = l.take(c * 32);
-  w.rp = l.take(c * 32);
-  w.y = l.take(c * k * poly);
-  w.e1 = l.take(c * k * poly);
-  w.e2 = l.take(c * poly);
-  w.u = l.take(c * k * poly);
-  w.v = l.take(c * poly);
-  w.cp = l.take(c * s.ct);
-  w.total = l.total;
-  w.ok = l.ok;
+  w.fips = w.take(c * (k * k + 2 * k) * poly);
+  w.hat = w.take(c * (k * k + 2 * k) * poly * 2);
+  w.u2 = w.take(c * k * poly);
+  w.v2 = w.take(c * poly);
+  w.w = w.take(c * poly);
+  w.mp = w.take(c * 32);
+  w.kp = w.take(c * 32);
+  w.rp = w.take(c * 32);
+  w.y = w.take(c * k * poly);
+  w.e1 = w.take(c * k * poly);
+  w.e2 = w.take(c * poly);
+  w.u = w.take(c * k * poly);
+  w.v = w.take(c * poly);
+  w.cp = w.take(c * s.ct);
   return w;
 }
-// false: the size does not fit size_t
-bool ws_need(const Set& s, size_t count, int op, size_t* need) {
-  bool ok = true;
-  *need = 0;
-  if (op == PSF_MLKEM_OP_KEYGEN) { const KeygenWs w = keygen_ws(s, count); ok = w.ok; *need = w.total; }
-  if (op == PSF_MLKEM_OP_ENCAPS) { const EncapsWs w = encaps_ws(s, count); ok = w.ok; *need = w.total; }
-  if (op == PSF_MLKEM_OP_DECAPS) { const DecapsWs w = decaps_ws(s, count); ok = w.ok; *need = w.total; }
-  return ok;
+Layout ws_need(const Set& s, size_t count, int op) {
+  if (op == PSF_MLKEM_OP_KEYGEN) return keygen_ws(s, count);
+  if (op == PSF_MLKEM_OP_ENCAPS) return encaps_ws(s, count);
+  if (op == PSF_MLKEM_OP_DECAPS) return decaps_ws(s, count);
+  return Layout{};
 }
 
-// the buffers of a call: `count` items of `len` bytes each
-struct Buf { const void* p; size_t len; bool out; };
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  if (na == 0 || nb == 0) return false;
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + nb && pb < pa + na;
-}
-// the header's order: NULL pointers, byte counts, the workspace (op >= 0), overlaps.  The caller has dealt with `param` and count = 0.
-psf_status check_bufs(const Set& s, size_t count, const Buf* b, int nb, int op, const void* ws, size_t ws_bytes, size_t* need) {
-  for (int i = 0; i < nb; ++i)
-    if (!b[i].p) return PSF_ERR_PARAM;
-  for (int i = 0; i < nb; ++i)
-    if (count > SIZE_MAX / b[i].len || count * b[i].len > SIZE_MAX - (uintptr_t)b[i].p) return PSF_ERR_PARAM;
-  *need = 0;
-  if (op >= 0) {
-    if (!ws_need(s, count, op, need)) return PSF_ERR_PARAM;
-    if (!ws || (uintptr_t)ws % 256 != 0 || ws_bytes < *need) return PSF_ERR_PARAM;
-  }
-  for (int i = 0; i < nb; ++i) {
-    if (!b[i].out) continue;
-    for (int j = 0; j < nb; ++j)
-      if (j != i && overlap(b[i].p, count * b[i].len, b[j].p, count * b[j].len)) return PSF_ERR_PARAM;
-    if (op >= 0 && overlap(b[i].p, count * b[i].len, ws, *need)) return PSF_ERR_PARAM;
-  }
-  return PSF_OK;
-}
-
-#define PSF_TRY(expr)                      \
-  do {                                     \
-    const psf_status rc__ = (expr);        \
-    if (rc__ != PSF_OK) return rc__;       \
-  } while (0)
-
-unsigned blocks_of(size_t items, size_t per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-// every grid of this unit has at most one workgroup per instance (k_check_ek: exactly one; k_pack / k_unpack: 128 k threads per instance)
-bool grid_fits(size_t count) { return count <= kMaxGrid; }
-
+// a buffer of `len` bytes per instance, packed
+Buf buf_of(const void* p, size_t len, bool out) { return Buf{p, len, len, out, false, 0}; }
 psf_status launch_segs(bool pack, size_t count, const Seg* segs, int nseg, hipStream_t st) {
   SegArgs a{};
   a.count = count;
@@ -543,28 +474,38 @@ psf_status decaps_run(int device, const Set& s, size_t count, const uint8_t* dk,
   return PSF_OK;
 }
 
-// a call on host buffers: device copies of the inputs, the workspace and the flag for the life of the call
-struct HostCall {
-  DevArr<uint8_t> buf[4], ws;
-  DevArr<int> flag;
-  psf_status prepare(const Buf* b, int nb, size_t count, size_t ws_bytes) {
-    for (int i = 0; i < nb; ++i) {
-      HIP_TRY(buf[i].alloc(count * b[i].len));
-      if (!b[i].out) HIP_TRY(hipMemcpy(buf[i], b[i].p, count * b[i].len, hipMemcpyHostToDevice));
-    }
-    if (ws_bytes) HIP_TRY(ws.alloc(ws_bytes));
-    HIP_TRY(flag.alloc(1));
-    HIP_TRY(hipMemset(flag, 0, sizeof(int)));
-    return PSF_OK;
-  }
-  psf_status finish(const Buf* b, int nb, size_t count) {
-    for (int i = 0; i < nb; ++i)
-      if (b[i].out) HIP_TRY(hipMemcpy(const_cast<void*>(b[i].p), buf[i], count * b[i].len, hipMemcpyDeviceToHost));
-    int f = 0;
-    HIP_TRY(hipMemcpy(&f, flag, sizeof(int), hipMemcpyDeviceToHost));
-    return f ? PSF_ERR_SAMPLER : PSF_OK;
-  }
-};
+// ---- argument checks of the three operations, for both forms ---------------------------------------------------------------------------------------
+// the header's order after `param` and count = 0: NULL pointers, byte counts, the workspace (device forms), overlaps; then the instance limit: every grid of
+// this unit has at most one workgroup per instance (k_check_ek: exactly one; k_pack / k_unpack: 128 k threads per instance)
+psf_status keygen_check(int param, size_t count, const uint8_t* d, const uint8_t* z, uint8_t* ek, uint8_t* dk, bool dev, const void* ws, size_t ws_bytes, Set* s,
+                        KeygenWs* w) {
+  if (!set_of(param, s)) return PSF_ERR_PARAM;
+  if (count == 0) return PSF_OK;
+  Buf b[4] = {buf_of(d, 32, false), buf_of(z, 32, false), buf_of(ek, s->ek, true), buf_of(dk, s->dk, true)};
+  *w = keygen_ws(*s, count);
+  PSF_TRY(check_null(b, 4));
+  PSF_TRY(check_rest(count, b, 4, *w, dev, ws, ws_bytes));
+  return grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
+}
+psf_status encaps_check(int param, size_t count, const uint8_t* ek, const uint8_t* m, uint8_t* ss, uint8_t* ct, bool dev, const void* ws, size_t ws_bytes, Set* s,
+                        EncapsWs* w) {
+  if (!set_of(param, s)) return PSF_ERR_PARAM;
+  if (count == 0) return PSF_OK;
+  Buf b[4] = {buf_of(ek, s->ek, false), buf_of(m, 32, false), buf_of(ss, 32, true), buf_of(ct, s->ct, true)};
+  *w = encaps_ws(*s, count);
+  PSF_TRY(check_null(b, 4));
+  PSF_TRY(check_rest(count, b, 4, *w, dev, ws, ws_bytes));
+  return grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
+}
+psf_status decaps_check(int param, size_t count, const uint8_t* dk, const uint8_t* ct, uint8_t* ss, bool dev, const void* ws, size_t ws_bytes, Set* s, DecapsWs* w) {
+  if (!set_of(param, s)) return PSF_ERR_PARAM;
+  if (count == 0) return PSF_OK;
+  Buf b[3] = {buf_of(dk, s->dk, false), buf_of(ct, s->ct, false), buf_of(ss, 32, true)};
+  *w = decaps_ws(*s, count);
+  PSF_TRY(check_null(b, 3));
+  PSF_TRY(check_rest(count, b, 3, *w, dev, ws, ws_bytes));
+  return grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
+}
 
 psf_status check_run(bool dk_form, int device, const Set& s, size_t count, const uint8_t* in, uint8_t* ok, hipStream_t st) {
   if (!grid_fits(count)) return PSF_ERR_UNSUPPORTED;
@@ -578,15 +519,18 @@ psf_status check_call(bool dk_form, bool host, int device, int param, size_t cou
   Set s;
   if (!set_of(param, &s)) return PSF_ERR_PARAM;
   if (count == 0) return PSF_OK;
-  const Buf b[2] = {{in, dk_form ? s.dk : s.ek, false}, {ok, 1, true}};
-  size_t need = 0;
-  PSF_TRY(check_bufs(s, count, b, 2, -1, nullptr, 0, &need));
+  const size_t len = dk_form ? s.dk : s.ek;
+  Buf b[2] = {buf_of(in, len, false), buf_of(ok, 1, true)};
+  PSF_TRY(check_null(b, 2));
+  PSF_TRY(check_rest(count, b, 2, Layout{}, false, nullptr, 0));
   if (!host) return check_run(dk_form, device, s, count, in, ok, st);
   PSF_TRY(use_device(device));
   HostCall h;
-  PSF_TRY(h.prepare(b, 2, count, 0));
-  PSF_TRY(check_run(dk_form, device, s, count, h.buf[0], h.buf[1], nullptr));
-  return h.finish(b, 2, count);
+  const uint8_t* din = h.in(in, count, len, len, dk_form ? SECRET : PUBLIC);
+  uint8_t* dok = h.out(count);
+  PSF_TRY(h.status());
+  PSF_TRY(check_run(dk_form, device, s, count, din, dok, nullptr));
+  return h.fetch(ok, dok, count);
 }
 
 }  // namespace mlkem
@@ -610,46 +554,37 @@ psf_status psf_mlkem_sizes(int param, size_t* ek, size_t* dk, size_t* ct, size_t
 psf_status psf_mlkem_workspace_bytes(int param, size_t count, int op, size_t* bytes) {
   Set s;
   if (!set_of(param, &s) || op < PSF_MLKEM_OP_KEYGEN || op > PSF_MLKEM_OP_CHECK || !bytes) return PSF_ERR_PARAM;
-  size_t need = 0;
-  if (!ws_need(s, count, op, &need)) return PSF_ERR_PARAM;
-  *bytes = need;
+  const Layout need = ws_need(s, count, op);
+  if (!need.ok) return PSF_ERR_PARAM;
+  *bytes = need.total;
   return PSF_OK;
 }
 
 psf_status psf_mlkem_keygen_dev(int device, int param, size_t count, const uint8_t* d_d, const uint8_t* d_z, uint8_t* d_ek, uint8_t* d_dk, void* d_ws, size_t ws_bytes,
                                 int* d_fail, void* stream) {
   Set s;
-  if (!set_of(param, &s)) return PSF_ERR_PARAM;
-  if (count == 0) return PSF_OK;
-  const Buf b[4] = {{d_d, 32, false}, {d_z, 32, false}, {d_ek, s.ek, true}, {d_dk, s.dk, true}};
-  size_t need = 0;
-  PSF_TRY(check_bufs(s, count, b, 4, PSF_MLKEM_OP_KEYGEN, d_ws, ws_bytes, &need));
-  if (!grid_fits(count)) return PSF_ERR_UNSUPPORTED;
-  return keygen_run(device, s, count, d_d, d_z, d_ek, d_dk, d_ws, keygen_ws(s, count), d_fail, (hipStream_t)stream);
+  KeygenWs w;
+  const psf_status rc = keygen_check(param, count, d_d, d_z, d_ek, d_dk, true, d_ws, ws_bytes, &s, &w);
+  if (rc != PSF_OK || count == 0) return rc;
+  return keygen_run(device, s, count, d_d, d_z, d_ek, d_dk, d_ws, w, d_fail, (hipStream_t)stream);
 }
 
 psf_status psf_mlkem_encaps_dev(int device, int param, size_t count, const uint8_t* d_ek, const uint8_t* d_m, uint8_t* d_ss, uint8_t* d_ct, void* d_ws, size_t ws_bytes,
                                 int* d_fail, void* stream) {
   Set s;
-  if (!set_of(param, &s)) return PSF_ERR_PARAM;
-  if (count == 0) return PSF_OK;
-  const Buf b[4] = {{d_ek, s.ek, false}, {d_m, 32, false}, {d_ss, 32, true}, {d_ct, s.ct, true}};
-  size_t need = 0;
-  PSF_TRY(check_bufs(s, count, b, 4, PSF_MLKEM_OP_ENCAPS, d_ws, ws_bytes, &need));
-  if (!grid_fits(count)) return PSF_ERR_UNSUPPORTED;
-  return encaps_run(device, s, count, d_ek, d_m, d_ss, d_ct, d_ws, encaps_ws(s, count), d_fail, (hipStream_t)stream);
+  EncapsWs w;
+  const psf_status rc = encaps_check(param, count, d_ek, d_m, d_ss, d_ct, true, d_ws, ws_bytes, &s, &w);
+  if (rc != PSF_OK || count == 0) return rc;
+  return encaps_run(device, s, count, d_ek, d_m, d_ss, d_ct, d_ws, w, d_fail, (hipStream_t)stream);
 }
 
 psf_status psf_mlkem_decaps_dev(int device, int param, size_t count, const uint8_t* d_dk, const uint8_t* d_ct, uint8_t* d_ss, void* d_ws, size_t ws_bytes, int* d_fail,
                                 void* stream) {
   Set s;
-  if (!set_of(param, &s)) return PSF_ERR_PARAM;
-  if (count == 0) return PSF_OK;
-  const Buf b[3] = {{d_dk, s.dk, false}, {d_ct, s.ct, false}, {d_ss, 32, true}};
-  size_t need = 0;
-  PSF_TRY(check_bufs(s, count, b, 3, PSF_MLKEM_OP_DECAPS, d_ws, ws_bytes, &need));
-  if (!grid_fits(count)) return PSF_ERR_UNSUPPORTED;
-  return decaps_run(device, s, count, d_dk, d_ct, d_ss, d_ws, decaps_ws(s, count), d_fail, (hipStream_t)stream);
+  DecapsWs w;
+  const psf_status rc = decaps_check(param, count, d_dk, d_ct, d_ss, true, d_ws, ws_bytes, &s, &w);
+  if (rc != PSF_OK || count == 0) return rc;
+  return decaps_run(device, s, count, d_dk, d_ct, d_ss, d_ws, w, d_fail, (hipStream_t)stream);
 }
 
 psf_status psf_mlkem_check_ek_dev(int device, int param, size_t count, const uint8_t* d_ek, uint8_t* d_ok, void* stream) {
@@ -667,50 +602,55 @@ psf_status psf_mlkem_check_dk(int device, int param, size_t count, const uint8_t
 
 psf_status psf_mlkem_keygen(int device, int param, size_t count, const uint8_t* d, const uint8_t* z, uint8_t* ek, uint8_t* dk) {
   Set s;
-  if (!set_of(param, &s)) return PSF_ERR_PARAM;
-  if (count == 0) return PSF_OK;
-  const Buf b[4] = {{d, 32, false}, {z, 32, false}, {ek, s.ek, true}, {dk, s.dk, true}};
-  size_t need = 0;
-  PSF_TRY(check_bufs(s, count, b, 4, -1, nullptr, 0, &need));
-  if (!ws_need(s, count, PSF_MLKEM_OP_KEYGEN, &need)) return PSF_ERR_PARAM;
-  if (!grid_fits(count)) return PSF_ERR_UNSUPPORTED;
+  KeygenWs w;
+  const psf_status rc = keygen_check(param, count, d, z, ek, dk, false, nullptr, 0, &s, &w);
+  if (rc != PSF_OK || count == 0) return rc;
   PSF_TRY(use_device(device));
   HostCall h;
-  PSF_TRY(h.prepare(b, 4, count, need));
-  PSF_TRY(keygen_run(device, s, count, h.buf[0], h.buf[1], h.buf[2], h.buf[3], h.ws, keygen_ws(s, count), h.flag, nullptr));
-  return h.finish(b, 4, count);
+  const uint8_t *dd = h.in(d, count, 32, 32, SECRET), *dz = h.in(z, count, 32, 32, SECRET);
+  uint8_t *dek = h.out(count * s.ek), *ddk = h.out(count * s.dk, SECRET);
+  void* dws = h.workspace(w.total);
+  int* dflag = h.flag();
+  PSF_TRY(h.status());
+  PSF_TRY(keygen_run(device, s, count, dd, dz, dek, ddk, dws, w, dflag, nullptr));
+  PSF_TRY(h.fetch(ek, dek, count * s.ek));
+  PSF_TRY(h.fetch(dk, ddk, count * s.dk));
+  return h.finish();
 }
 
 psf_status psf_mlkem_encaps(int device, int param, size_t count, const uint8_t* ek, const uint8_t* m, uint8_t* ss, uint8_t* ct) {
   Set s;
-  if (!set_of(param, &s)) return PSF_ERR_PARAM;
-  if (count == 0) return PSF_OK;
-  const Buf b[4] = {{ek, s.ek, false}, {m, 32, false}, {ss, 32, true}, {ct, s.ct, true}};
-  size_t need = 0;
-  PSF_TRY(check_bufs(s, count, b, 4, -1, nullptr, 0, &need));
-  if (!ws_need(s, count, PSF_MLKEM_OP_ENCAPS, &need)) return PSF_ERR_PARAM;
-  if (!grid_fits(count)) return PSF_ERR_UNSUPPORTED;
+  EncapsWs w;
+  const psf_status rc = encaps_check(param, count, ek, m, ss, ct, false, nullptr, 0, &s, &w);
+  if (rc != PSF_OK || count == 0) return rc;
   PSF_TRY(use_device(device));
   HostCall h;
-  PSF_TRY(h.prepare(b, 4, count, need));
-  PSF_TRY(encaps_run(device, s, count, h.buf[0], h.buf[1], h.buf[2], h.buf[3], h.ws, encaps_ws(s, count), h.flag, nullptr));
-  return h.finish(b, 4, count);
+  const uint8_t *dek = h.in(ek, count, s.ek, s.ek), *dm = h.in(m, count, 32, 32, SECRET);
+  uint8_t *dss = h.out(count * 32, SECRET), *dct = h.out(count * s.ct);
+  void* dws = h.workspace(w.total);
+  int* dflag = h.flag();
+  PSF_TRY(h.status());
+  PSF_TRY(encaps_run(device, s, count, dek, dm, dss, dct, dws, w, dflag, nullptr));
+  PSF_TRY(h.fetch(ss, dss, count * 32));
+  PSF_TRY(h.fetch(ct, dct, count * s.ct));
+  return h.finish();
 }
 
 psf_status psf_mlkem_decaps(int device, int param, size_t count, const uint8_t* dk, const uint8_t* ct, uint8_t* ss) {
   Set s;
-  if (!set_of(param, &s)) return PSF_ERR_PARAM;
-  if (count == 0) return PSF_OK;
-  const Buf b[3] = {{dk, s.dk, false}, {ct, s.ct, false}, {ss, 32, true}};
-  size_t need = 0;
-  PSF_TRY(check_bufs(s, count, b, 3, -1, nullptr, 0, &need));
-  if (!ws_need(s, count, PSF_MLKEM_OP_DECAPS, &need)) return PSF_ERR_PARAM;
-  if (!grid_fits(count)) return PSF_ERR_UNSUPPORTED;
+  DecapsWs w;
+  const psf_status rc = decaps_check(param, count, dk, ct, ss, false, nullptr, 0, &s, &w);
+  if (rc != PSF_OK || count == 0) return rc;
   PSF_TRY(use_device(device));
   HostCall h;
-  PSF_TRY(h.prepare(b, 3, count, need));
-  PSF_TRY(decaps_run(device, s, count, h.buf[0], h.buf[1], h.buf[2], h.ws, decaps_ws(s, count), h.flag, nullptr));
-  return h.finish(b, 3, count);
+  const uint8_t *ddk = h.in(dk, count, s.dk, s.dk, SECRET), *dct = h.in(ct, count, s.ct, s.ct);
+  uint8_t* dss = h.out(count * 32, SECRET);
+  void* dws = h.workspace(w.total);
+  int* dflag = h.flag();
+  PSF_TRY(h.status());
+  PSF_TRY(decaps_run(device, s, count, ddk, dct, dss, dws, w, dflag, nullptr));
+  PSF_TRY(h.fetch(ss, dss, count * 32));
+  return h.finish();
 }
 
 }  // extern "C"

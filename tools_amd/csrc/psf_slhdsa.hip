@@ -12,22 +12,15 @@
 // One lane per unit of work and one Keccak state per lane throughout; lane and byte indices are size_t.  KeyGen's secrets (the WOTS+ secret values and
 // the chain intermediates) exist in registers only; the workspace holds public values and the last operation of KeyGen clears it all the same.
 // Verification has no secret (DESIGN.md "SLH-DSA").
+#include "psf_call.hpp"
 #include "psf_hip_util.hpp"
 #include "psf_host.hpp"
 #include "psf_keccak_core.hpp"
-#include "psf_mldsa_api.hpp"
 #include "psf_slhdsa_api.hpp"
 #include "psf_slhdsa_core.hpp"
 
 namespace psf {
 namespace slh {
-
-using dsa::at;
-using dsa::blocks_of;
-using dsa::Buf;
-using dsa::kMaxGrid;
-using dsa::Layout;
-using dsa::u128;
 
 // ---- KeyGen ----------------------------------------------------------------------------------------------------------------------------------------------
 // `first`: the launches of one stage are chunks of at most 2^31 - 1 workgroups; lane g of the stage is first + its index in the launch
@@ -208,36 +201,27 @@ bool set_of(int param, Params* p) {
   return true;
 }
 
-struct KeygenWs { size_t ends, nodes, total; bool ok; };
-struct VerifyWs { size_t digest, roots, node, ends, total; bool ok; };
+struct KeygenWs : Layout { size_t ends, nodes; };
+struct VerifyWs : Layout { size_t digest, roots, node, ends; };
 KeygenWs keygen_ws(const Params& p, size_t count) {
-  Layout l;
   KeygenWs w;
   const u128 c = count, leaves = (u128)1 << p.hp;
-  w.ends = l.take(c * leaves * wots_len(p.n) * p.n);
-  w.nodes = l.take(c * leaves * p.n);
-  w.total = l.total;
-  w.ok = l.ok;
+  w.ends = w.take(c * leaves * wots_len(p.n) * p.n);
+  w.nodes = w.take(c * leaves * p.n);
   return w;
 }
 VerifyWs verify_ws(const Params& p, size_t count) {
-  Layout l;
   VerifyWs w;
   const u128 c = count;
-  w.digest = l.take(c * 8 * kDigestWords);
-  w.roots = l.take(c * p.k * p.n);
-  w.node = l.take(c * 8 * kNodeWords);
-  w.ends = l.take(c * wots_len(p.n) * p.n);
-  w.total = l.total;
-  w.ok = l.ok;
+  w.digest = w.take(c * 8 * kDigestWords);
+  w.roots = w.take(c * p.k * p.n);
+  w.node = w.take(c * 8 * kNodeWords);
+  w.ends = w.take(c * wots_len(p.n) * p.n);
   return w;
 }
-bool ws_need(const Params& p, size_t count, int op, size_t* need) {
-  bool ok = true;
-  *need = 0;
-  if (op == PSF_SLHDSA_OP_KEYGEN) { const KeygenWs w = keygen_ws(p, count); ok = w.ok; *need = w.total; }
-  if (op == PSF_SLHDSA_OP_VERIFY) { const VerifyWs w = verify_ws(p, count); ok = w.ok; *need = w.total; }
-  return ok;
+Layout ws_need(const Params& p, size_t count, int op) {
+  if (op == PSF_SLHDSA_OP_KEYGEN) return keygen_ws(p, count);
+  return verify_ws(p, count);
 }
 
 template <int NW> psf_status keygen_run_nw(KgArgs a, hipStream_t st) {
@@ -288,13 +272,7 @@ psf_status verify_run(int device, const Params& p, size_t count, const VerifyIn&
 }
 
 // ---- argument checks of the entry points: the header's order -------------------------------------------------------------------------------------------
-struct Checked { Params p; size_t need; };
-psf_status check_rest(const Params& p, size_t count, Buf* b, int nb, int op, bool dev, const void* ws, size_t ws_bytes, size_t* need) {
-  PSF_TRY(dsa::check_spans(count, b, nb));
-  if (!ws_need(p, count, op, need)) return PSF_ERR_PARAM;
-  PSF_TRY(dsa::check_ws(dev, ws, ws_bytes, *need));
-  return dsa::check_overlaps(b, nb, dev, ws, *need);
-}
+struct Checked { Params p; Layout need; };
 psf_status keygen_check(int param, size_t count, const uint8_t* sk_seed, const uint8_t* sk_prf, const uint8_t* pk_seed, uint8_t* pk, uint8_t* sk, bool dev,
                         const void* ws, size_t ws_bytes, Checked* ck) {
   if (!set_of(param, &ck->p)) return PSF_ERR_PARAM;
@@ -302,9 +280,10 @@ psf_status keygen_check(int param, size_t count, const uint8_t* sk_seed, const u
   const size_t n = ck->p.n;
   Buf b[5] = {{sk_seed, n, n, false, false, 0}, {sk_prf, n, n, false, false, 0}, {pk_seed, n, n, false, false, 0}, {pk, 2 * n, 2 * n, true, false, 0},
               {sk, 4 * n, 4 * n, true, false, 0}};
-  PSF_TRY(dsa::check_null(b, 5));
-  PSF_TRY(check_rest(ck->p, count, b, 5, PSF_SLHDSA_OP_KEYGEN, dev, ws, ws_bytes, &ck->need));
-  return dsa::grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
+  PSF_TRY(check_null(b, 5));
+  ck->need = ws_need(ck->p, count, PSF_SLHDSA_OP_KEYGEN);
+  PSF_TRY(check_rest(count, b, 5, ck->need, dev, ws, ws_bytes));
+  return grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
 }
 psf_status verify_check(int param, size_t count, const VerifyIn& in, uint8_t* ok, bool dev, const void* ws, size_t ws_bytes, Checked* ck) {
   if (!set_of(param, &ck->p)) return PSF_ERR_PARAM;
@@ -312,16 +291,12 @@ psf_status verify_check(int param, size_t count, const VerifyIn& in, uint8_t* ok
   const size_t n = ck->p.n;
   Buf b[4] = {{in.pk, 2 * n, in.pk_stride, false, false, 0}, {in.msg, in.msg_len, in.msg_stride, false, in.msg_len == 0, 0},
               {in.sig, sig_bytes(ck->p), sig_bytes(ck->p), false, false, 0}, {ok, 1, 1, true, false, 0}};
-  PSF_TRY(dsa::check_null(b, 4));
+  PSF_TRY(check_null(b, 4));
   if ((in.pk_stride != 0 && in.pk_stride < 2 * n) || in.msg_stride < in.msg_len) return PSF_ERR_PARAM;
   if (in.msg_len > SIZE_MAX - 3 * n) return PSF_ERR_PARAM;
-  PSF_TRY(check_rest(ck->p, count, b, 4, PSF_SLHDSA_OP_VERIFY, dev, ws, ws_bytes, &ck->need));
-  return dsa::grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
-}
-
-hipError_t upload_rows(void* d, const void* h, size_t count, size_t len, size_t stride) {
-  if (count == 0 || len == 0) return hipSuccess;
-  return stride == len ? hipMemcpy(d, h, count * len, hipMemcpyHostToDevice) : hipMemcpy2D(d, len, h, stride, len, count, hipMemcpyHostToDevice);
+  ck->need = ws_need(ck->p, count, PSF_SLHDSA_OP_VERIFY);
+  PSF_TRY(check_rest(count, b, 4, ck->need, dev, ws, ws_bytes));
+  return grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
 }
 
 }  // namespace slh
@@ -344,9 +319,9 @@ psf_status psf_slhdsa_sizes(int param, size_t* pk, size_t* sk, size_t* sig) {
 psf_status psf_slhdsa_workspace_bytes(int param, size_t count, int op, size_t* bytes) {
   Params p;
   if (!set_of(param, &p) || (op != PSF_SLHDSA_OP_KEYGEN && op != PSF_SLHDSA_OP_VERIFY) || !bytes) return PSF_ERR_PARAM;
-  size_t need = 0;
-  if (!ws_need(p, count, op, &need)) return PSF_ERR_PARAM;
-  *bytes = need;
+  const Layout need = ws_need(p, count, op);
+  if (!need.ok) return PSF_ERR_PARAM;
+  *bytes = need.total;
   return PSF_OK;
 }
 
@@ -373,21 +348,14 @@ psf_status psf_slhdsa_keygen(int device, int param, size_t count, const uint8_t*
   if (rc != PSF_OK || count == 0) return rc;
   PSF_TRY(use_device(device));
   const size_t n = ck.p.n;
-  DevBuf din, dpk, dsk, dws;
-  HIP_TRY(din.alloc(3 * count * n));
-  HIP_TRY(dpk.alloc(2 * count * n));
-  HIP_TRY(dsk.alloc(4 * count * n));
-  HIP_TRY(dws.alloc(ck.need));
-  uint8_t* d = din.as<uint8_t>();
-  HIP_TRY(hipMemcpy(d, sk_seed, count * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d + count * n, sk_prf, count * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d + 2 * count * n, pk_seed, count * n, hipMemcpyHostToDevice));
-  PSF_TRY(keygen_run(device, ck.p, count, d, d + count * n, d + 2 * count * n, dpk.as<uint8_t>(), dsk.as<uint8_t>(), dws.as<void>(), keygen_ws(ck.p, count), nullptr));
-  HIP_TRY(dpk.download(pk, 2 * count * n));
-  HIP_TRY(dsk.download(sk, 4 * count * n));
-  HIP_TRY(din.zero(3 * count * n));                                       // the device copies of SK.seed and SK.prf, and of sk
-  HIP_TRY(dsk.zero(4 * count * n));
-  return PSF_OK;
+  HostCall h;
+  const uint8_t *dseed = h.in(sk_seed, count, n, n, SECRET), *dprf = h.in(sk_prf, count, n, n, SECRET), *dpseed = h.in(pk_seed, count, n, n);
+  uint8_t *dpk = h.out(2 * count * n), *dsk = h.out(4 * count * n, SECRET);
+  void* dws = h.workspace(ck.need.total);
+  PSF_TRY(h.status());
+  PSF_TRY(keygen_run(device, ck.p, count, dseed, dprf, dpseed, dpk, dsk, dws, keygen_ws(ck.p, count), nullptr));
+  PSF_TRY(h.fetch(pk, dpk, 2 * count * n));
+  return h.fetch(sk, dsk, 4 * count * n);
 }
 
 psf_status psf_slhdsa_verify(int device, int param, size_t count, const uint8_t* pk, size_t pk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
@@ -397,20 +365,14 @@ psf_status psf_slhdsa_verify(int device, int param, size_t count, const uint8_t*
   const psf_status rc = verify_check(param, count, in, ok, false, nullptr, 0, &ck);
   if (rc != PSF_OK || count == 0) return rc;
   PSF_TRY(use_device(device));
-  const size_t n = ck.p.n, keys = pk_stride ? count : 1, sig_len = sig_bytes(ck.p);
-  DevBuf dpk, dmsg, dsig, dok, dws;
-  HIP_TRY(dpk.alloc(keys * 2 * n));
-  if (msg_len) HIP_TRY(dmsg.alloc(count * msg_len));
-  HIP_TRY(dsig.alloc(count * sig_len));
-  HIP_TRY(dok.alloc(count));
-  HIP_TRY(dws.alloc(ck.need));
-  HIP_TRY(upload_rows(dpk.as<void>(), pk, keys, 2 * n, pk_stride ? pk_stride : 2 * n));
-  HIP_TRY(upload_rows(dmsg.as<void>(), msg, count, msg_len, msg_stride));
-  HIP_TRY(dsig.upload(sig, count * sig_len));
-  const VerifyIn din{dpk.as<uint8_t>(), pk_stride ? 2 * n : 0, dmsg.as<uint8_t>(), msg_len, msg_len, dsig.as<uint8_t>()};
-  PSF_TRY(verify_run(device, ck.p, count, din, dok.as<uint8_t>(), dws.as<void>(), verify_ws(ck.p, count), nullptr));
-  HIP_TRY(dok.download(ok, count));
-  return PSF_OK;
+  const size_t n = ck.p.n, sig_len = sig_bytes(ck.p);
+  HostCall h;
+  const VerifyIn din{h.in(pk, count, 2 * n, pk_stride), pk_stride ? 2 * n : 0, h.in(msg, count, msg_len, msg_stride), msg_len, msg_len, h.in(sig, count, sig_len, sig_len)};
+  uint8_t* dok = h.out(count);
+  void* dws = h.workspace(ck.need.total);
+  PSF_TRY(h.status());
+  PSF_TRY(verify_run(device, ck.p, count, din, dok, dws, verify_ws(ck.p, count), nullptr));
+  return h.fetch(ok, dok, count);
 }
 
 }  // extern "C"

@@ -17,20 +17,15 @@
 // No secret leaves registers: the stores of every kernel write a value that the signature reveals or that a verifier recomputes from it (DESIGN.md
 // "SLH-DSA: signing" goes through them one by one).  Every index, digit, branch and loop bound comes from the digest or a root.  Lane and byte indices
 // are size_t; every stage goes through launch_chunked.
+#include "psf_call.hpp"
 #include "psf_hip_util.hpp"
 #include "psf_host.hpp"
 #include "psf_keccak_core.hpp"
-#include "psf_mldsa_api.hpp"
 #include "psf_slhdsa_api.hpp"
 #include "psf_slhdsa_sign_core.hpp"
 
 namespace psf {
 namespace slh {
-
-using dsa::at;
-using dsa::Buf;
-using dsa::Layout;
-using dsa::u128;
 
 // `first`: the launches of one stage are chunks of at most 2^31 - 1 workgroups; lane g of the stage is first + its index in the launch, and workgroup
 // first / 256 + blockIdx.x where a workgroup is the unit
@@ -284,19 +279,16 @@ template <int NW> __global__ __launch_bounds__(256) void k_sg_wots(SgArgs a) {
 uint32_t fors_wgs(const Params& p) {
   return p.a >= kSgForsHeight ? p.k << (p.a - kSgForsHeight) : (p.k + (1u << (kSgForsHeight - p.a)) - 1) >> (kSgForsHeight - p.a);
 }
-struct SignWs { size_t digest, fors_sub, fors_roots, msgs, ends, nodes, total; bool ok; };
+struct SignWs : Layout { size_t digest, fors_sub, fors_roots, msgs, ends, nodes; };
 SignWs sign_ws(const Params& p, size_t count) {
-  Layout l;
   SignWs w;
   const u128 c = count, leaves = (u128)1 << p.hp;
-  w.digest = l.take(c * 8 * kSgDigestWords);
-  w.fors_sub = l.take(p.a > kSgForsHeight ? c * ((u128)p.k << (p.a - kSgForsHeight)) * p.n : (u128)0);
-  w.fors_roots = l.take(c * p.k * p.n);
-  w.msgs = l.take(c * p.d * 8 * kSgMsgWords);
-  w.ends = l.take(c * p.d * leaves * wots_len(p.n) * p.n);
-  w.nodes = l.take(c * p.d * leaves * p.n);
-  w.total = l.total;
-  w.ok = l.ok;
+  w.digest = w.take(c * 8 * kSgDigestWords);
+  w.fors_sub = w.take(p.a > kSgForsHeight ? c * ((u128)p.k << (p.a - kSgForsHeight)) * p.n : (u128)0);
+  w.fors_roots = w.take(c * p.k * p.n);
+  w.msgs = w.take(c * p.d * 8 * kSgMsgWords);
+  w.ends = w.take(c * p.d * leaves * wots_len(p.n) * p.n);
+  w.nodes = w.take(c * p.d * leaves * p.n);
   return w;
 }
 
@@ -334,15 +326,12 @@ psf_status sign_check(int param, size_t count, const SignIn& in, uint8_t* sig, b
   const size_t n = p->n;
   Buf b[4] = {{in.sk, 4 * n, in.sk_stride, false, false, 0}, {in.msg, in.msg_len, in.msg_stride, false, in.msg_len == 0, 0}, {in.addrnd, n, n, false, true, 0},
               {sig, sig_bytes(*p), sig_bytes(*p), true, false, 0}};
-  PSF_TRY(dsa::check_null(b, 4));
+  PSF_TRY(check_null(b, 4));
   if ((in.sk_stride != 0 && in.sk_stride < 4 * n) || in.msg_stride < in.msg_len) return PSF_ERR_PARAM;
   if (in.msg_len > SIZE_MAX - 3 * n) return PSF_ERR_PARAM;
-  PSF_TRY(dsa::check_spans(count, b, 4));
   *w = sign_ws(*p, count);
-  if (!w->ok) return PSF_ERR_PARAM;
-  PSF_TRY(dsa::check_ws(dev, ws, ws_bytes, w->total));
-  PSF_TRY(dsa::check_overlaps(b, 4, dev, ws, w->total));
-  return dsa::grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
+  PSF_TRY(check_rest(count, b, 4, *w, dev, ws, ws_bytes));
+  return grid_fits(count) ? PSF_OK : PSF_ERR_UNSUPPORTED;
 }
 
 }  // namespace slh
@@ -380,22 +369,14 @@ psf_status psf_slhdsa_sign(int device, int param, size_t count, const uint8_t* s
   const psf_status rc = sign_check(param, count, in, sig, false, nullptr, 0, &p, &w);
   if (rc != PSF_OK || count == 0) return rc;
   PSF_TRY(use_device(device));
-  const size_t n = p.n, keys = sk_stride ? count : 1, sig_len = sig_bytes(p);
-  DevBuf dsk, dmsg, drnd, dsig, dws;
-  HIP_TRY(dsk.alloc(keys * 4 * n));
-  if (msg_len) HIP_TRY(dmsg.alloc(count * msg_len));
-  if (addrnd) HIP_TRY(drnd.alloc(count * n));
-  HIP_TRY(dsig.alloc(count * sig_len));
-  HIP_TRY(dws.alloc(w.total));
-  HIP_TRY(upload_rows(dsk.as<void>(), sk, keys, 4 * n, sk_stride ? sk_stride : 4 * n));
-  HIP_TRY(upload_rows(dmsg.as<void>(), msg, count, msg_len, msg_stride));
-  if (addrnd) HIP_TRY(drnd.upload(addrnd, count * n));
-  const SignIn din{dsk.as<uint8_t>(), sk_stride ? 4 * n : 0, dmsg.as<uint8_t>(), msg_len, msg_len, addrnd ? drnd.as<uint8_t>() : nullptr};
-  PSF_TRY(sign_run(device, p, count, din, dsig.as<uint8_t>(), dws.as<void>(), w, nullptr));
-  HIP_TRY(dsig.download(sig, count * sig_len));
-  HIP_TRY(dsk.zero(keys * 4 * n));                                        // the device copies of sk and addrnd
-  if (addrnd) HIP_TRY(drnd.zero(count * n));
-  return PSF_OK;
+  const size_t n = p.n, sig_len = sig_bytes(p);
+  HostCall h;
+  const SignIn din{h.in(sk, count, 4 * n, sk_stride, SECRET), sk_stride ? 4 * n : 0, h.in(msg, count, msg_len, msg_stride), msg_len, msg_len, h.in(addrnd, count, n, n, SECRET)};
+  uint8_t* dsig = h.out(count * sig_len);
+  void* dws = h.workspace(w.total);
+  PSF_TRY(h.status());
+  PSF_TRY(sign_run(device, p, count, din, dsig, dws, w, nullptr));
+  return h.fetch(sig, dsig, count * sig_len);
 }
 
 }  // extern "C"

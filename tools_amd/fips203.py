@@ -13,14 +13,10 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import check, lib
+from ._ffi import _vp, check, lib
 
 SHA3_256, SHA3_512, SHAKE128, SHAKE256 = range(4)
 Q, N = 3329, 256
-
-
-def _vp(a):
-    return C.c_void_p(a.ctypes.data) if a is not None and a.size else None
 
 
 def keccak_dev(func, count, d_in, in_len, d_out, out_len, in_stride=None, out_stride=None, device=0, stream=None):

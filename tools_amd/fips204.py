@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import check, lib
+from ._ffi import _vp, check, lib
 
 Q, N = 8380417, 256
 _typed = False
@@ -33,10 +33,6 @@ def _lib():
         L.psf_ntt_image_from_fips204.argtypes = [i, sz, vp, vp]
         _typed = True
     return L
-
-
-def _vp(a):
-    return C.c_void_p(a.ctypes.data) if a is not None and a.size else None
 
 
 def sample_ntt_dev(d_out, count, d_seed, k=0, l=0, seed_stride=None, d_fail=None, device=0, stream=None):

@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from ._ffi import check, lib
+from ._ffi import _rows, _vp, check, lib
 
 PARAM = {"ML-DSA-44": 44, "ML-DSA-65": 65, "ML-DSA-87": 87}
 OP_KEYGEN, OP_VERIFY = range(2)
@@ -120,22 +120,10 @@ def sign_end_dev(name, count, d_ws, ws_bytes, sk_stride=None, device=0, stream=N
 
 # ---- host forms ------------------------------------------------------------------------------------------------------------------------------------
 
-def _rows(items, size, what):
-    items = [bytes(x) for x in items]
-    for x in items:
-        if len(x) != size:
-            raise ValueError(f"mldsa: {what} of {len(x)} bytes, expected {size}")
-    return np.frombuffer(b"".join(items), dtype=np.uint8).reshape(len(items), size).copy()
-
-
-def _vp(a):
-    return C.c_void_p(a.ctypes.data) if a.size else None
-
-
 def keygen_internal(name, xis, device=0):
     """[(pk, sk)] for the 32-byte seed xi of each instance"""
     sz = sizes(name)
-    xi = _rows(xis, 32, "xi")
+    xi = _rows(xis, 32, "xi", "mldsa")
     pk, sk = np.empty((len(xi), sz["pk"]), np.uint8), np.empty((len(xi), sz["sk"]), np.uint8)
     check(_lib().psf_mldsa_keygen(device, _param(name), len(xi), _vp(xi), _vp(pk), _vp(sk)), "mldsa.keygen_internal")
     return [(bytes(a), bytes(b)) for a, b in zip(pk, sk)]
@@ -145,15 +133,15 @@ def verify_internal(name, pks, msgs, sigs, msg_kind=MSG_BYTES, device=0, why=Fal
     """[bool] (why=True: [(bool, why)]) for each (pk, M', sigma); `pks` is one key (bytes) for all or a list with one key per instance; the messages
     of one call have one length"""
     sz = sizes(name)
-    sig = _rows(sigs, sz["sig"], "signature")
+    sig = _rows(sigs, sz["sig"], "signature", "mldsa")
     msgs = [bytes(m) for m in msgs]
     lens = {len(m) for m in msgs}
     if len(lens) > 1:
         raise ValueError("mldsa.verify_internal: the messages of one call have one length")
     msg_len = lens.pop() if lens else 0
-    msg = _rows(msgs, msg_len, "message")
+    msg = _rows(msgs, msg_len, "message", "mldsa")
     one = isinstance(pks, (bytes, bytearray))
-    pk = _rows([pks] if one else pks, sz["pk"], "pk")
+    pk = _rows([pks] if one else pks, sz["pk"], "pk", "mldsa")
     if len(msg) != len(sig) or (not one and len(pk) != len(sig)):
         raise ValueError("mldsa.verify_internal: as many keys and messages as signatures")
     ok, wh = np.zeros(len(sig), np.uint8), np.zeros(len(sig), np.uint8)
@@ -171,10 +159,10 @@ def sign_internal(name, sks, msgs, rnds=None, msg_kind=MSG_BYTES, max_rounds=102
     if len(lens) > 1:
         raise ValueError("mldsa.sign_internal: the messages of one call have one length")
     msg_len = lens.pop() if lens else 0
-    msg = _rows(msgs, msg_len, "message")
+    msg = _rows(msgs, msg_len, "message", "mldsa")
     one = isinstance(sks, (bytes, bytearray))
-    sk = _rows([sks] if one else sks, sz["sk"], "sk")
-    rnd = None if rnds is None else _rows(rnds, 32, "rnd")
+    sk = _rows([sks] if one else sks, sz["sk"], "sk", "mldsa")
+    rnd = None if rnds is None else _rows(rnds, 32, "rnd", "mldsa")
     if (not one and len(sk) != len(msg)) or (rnd is not None and len(rnd) != len(msg)):
         raise ValueError("mldsa.sign_internal: as many keys and rnd strings as messages")
     sig, rounds = np.zeros((len(msg), sz["sig"]), np.uint8), np.zeros(len(msg), np.uint32)

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._ffi import check, lib
+from ._ffi import _rows, _vp, check, lib
 
 PARAM = {"ML-KEM-512": 2, "ML-KEM-768": 3, "ML-KEM-1024": 4}
 OP_KEYGEN, OP_ENCAPS, OP_DECAPS, OP_CHECK = range(4)
@@ -96,18 +96,6 @@ def check_dk_dev(name, count, d_dk, d_ok, device=0, stream=None):
 
 # ---- host forms ------------------------------------------------------------------------------------------------------------------------------------
 
-def _rows(items, size, what):
-    items = [bytes(x) for x in items]
-    for x in items:
-        if len(x) != size:
-            raise ValueError(f"mlkem: {what} of {len(x)} bytes, expected {size}")
-    return np.frombuffer(b"".join(items), dtype=np.uint8).reshape(len(items), size).copy()
-
-
-def _vp(a):
-    return C.c_void_p(a.ctypes.data) if a.size else None
-
-
 def _split(a):
     return [bytes(r) for r in a]
 
@@ -115,7 +103,7 @@ def _split(a):
 def keygen_internal(name, ds, zs, device=0):
     """[(ek, dk)] for the 32-byte seeds d and z of each instance"""
     sz = sizes(name)
-    d, z = _rows(ds, 32, "d"), _rows(zs, 32, "z")
+    d, z = _rows(ds, 32, "d", "mlkem"), _rows(zs, 32, "z", "mlkem")
     if len(d) != len(z):
         raise ValueError("mlkem.keygen_internal: as many d as z")
     ek, dk = np.empty((len(d), sz["ek"]), np.uint8), np.empty((len(d), sz["dk"]), np.uint8)
@@ -126,7 +114,7 @@ def keygen_internal(name, ds, zs, device=0):
 def encaps_internal(name, eks, ms, device=0):
     """[(K, c)] for each encapsulation key and 32-byte m.  No input check: see encaps."""
     sz = sizes(name)
-    ek, m = _rows(eks, sz["ek"], "ek"), _rows(ms, 32, "m")
+    ek, m = _rows(eks, sz["ek"], "ek", "mlkem"), _rows(ms, 32, "m", "mlkem")
     if len(ek) != len(m):
         raise ValueError("mlkem.encaps_internal: as many ek as m")
     ss, ct = np.empty((len(ek), 32), np.uint8), np.empty((len(ek), sz["ct"]), np.uint8)
@@ -137,7 +125,7 @@ def encaps_internal(name, eks, ms, device=0):
 def decaps(name, dks, cts, device=0):
     """[K] = ML-KEM.Decaps_internal for each decapsulation key and ciphertext.  check_dk is the caller's to run once per key."""
     sz = sizes(name)
-    dk, ct = _rows(dks, sz["dk"], "dk"), _rows(cts, sz["ct"], "ciphertext")
+    dk, ct = _rows(dks, sz["dk"], "dk", "mlkem"), _rows(cts, sz["ct"], "ciphertext", "mlkem")
     if len(dk) != len(ct):
         raise ValueError("mlkem.decaps: as many dk as ciphertexts")
     ss = np.empty((len(dk), 32), np.uint8)
@@ -147,7 +135,7 @@ def decaps(name, dks, cts, device=0):
 
 def check_ek(name, eks, device=0):
     """[bool]: the modulus check of section 7.2"""
-    ek = _rows(eks, sizes(name)["ek"], "ek")
+    ek = _rows(eks, sizes(name)["ek"], "ek", "mlkem")
     ok = np.zeros(len(ek), np.uint8)
     check(_lib().psf_mlkem_check_ek(device, _param(name), len(ek), _vp(ek), _vp(ok)), "mlkem.check_ek")
     return [bool(v) for v in ok]
@@ -155,7 +143,7 @@ def check_ek(name, eks, device=0):
 
 def check_dk(name, dks, device=0):
     """[bool]: the hash check of section 7.3"""
-    dk = _rows(dks, sizes(name)["dk"], "dk")
+    dk = _rows(dks, sizes(name)["dk"], "dk", "mlkem")
     ok = np.zeros(len(dk), np.uint8)
     check(_lib().psf_mlkem_check_dk(device, _param(name), len(dk), _vp(dk), _vp(ok)), "mlkem.check_dk")
     return [bool(v) for v in ok]

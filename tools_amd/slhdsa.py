@@ -16,7 +16,7 @@ import os
 
 import numpy as np
 
-from ._ffi import check, lib
+from ._ffi import _rows, _vp, check, lib
 
 PARAM = {"SLH-DSA-SHAKE-128s": 0, "SLH-DSA-SHAKE-128f": 1, "SLH-DSA-SHAKE-192s": 2, "SLH-DSA-SHAKE-192f": 3, "SLH-DSA-SHAKE-256s": 4, "SLH-DSA-SHAKE-256f": 5}
 OP_KEYGEN, OP_VERIFY = range(2)
@@ -98,23 +98,11 @@ def sign_dev(name, count, d_sk, d_msg, msg_len, d_addrnd, d_sig, d_ws, ws_bytes,
 
 # ---- host forms ------------------------------------------------------------------------------------------------------------------------------------
 
-def _rows(items, size, what):
-    items = [bytes(x) for x in items]
-    for x in items:
-        if len(x) != size:
-            raise ValueError(f"slhdsa: {what} of {len(x)} bytes, expected {size}")
-    return np.frombuffer(b"".join(items), dtype=np.uint8).reshape(len(items), size).copy()
-
-
-def _vp(a):
-    return C.c_void_p(a.ctypes.data) if a.size else None
-
-
 def keygen_internal(name, sk_seeds, sk_prfs, pk_seeds, device=0):
     """[(pk, sk)] for the n-byte (SK.seed, SK.prf, PK.seed) of each instance"""
     sz = sizes(name)
     n = sz["pk"] // 2
-    a, b, c = _rows(sk_seeds, n, "SK.seed"), _rows(sk_prfs, n, "SK.prf"), _rows(pk_seeds, n, "PK.seed")
+    a, b, c = _rows(sk_seeds, n, "SK.seed", "slhdsa"), _rows(sk_prfs, n, "SK.prf", "slhdsa"), _rows(pk_seeds, n, "PK.seed", "slhdsa")
     if not len(a) == len(b) == len(c):
         raise ValueError("slhdsa.keygen_internal: as many SK.prf and PK.seed strings as SK.seed strings")
     pk, sk = np.empty((len(a), sz["pk"]), np.uint8), np.empty((len(a), sz["sk"]), np.uint8)
@@ -125,15 +113,15 @@ def keygen_internal(name, sk_seeds, sk_prfs, pk_seeds, device=0):
 def verify_internal(name, pks, msgs, sigs, device=0):
     """[bool] for each (PK, M, SIG); `pks` is one key (bytes) for all or a list with one key per instance; the messages of one call have one length"""
     sz = sizes(name)
-    sig = _rows(sigs, sz["sig"], "signature")
+    sig = _rows(sigs, sz["sig"], "signature", "slhdsa")
     msgs = [bytes(m) for m in msgs]
     lens = {len(m) for m in msgs}
     if len(lens) > 1:
         raise ValueError("slhdsa.verify_internal: the messages of one call have one length")
     msg_len = lens.pop() if lens else 0
-    msg = _rows(msgs, msg_len, "message")
+    msg = _rows(msgs, msg_len, "message", "slhdsa")
     one = isinstance(pks, (bytes, bytearray))
-    pk = _rows([pks] if one else pks, sz["pk"], "pk")
+    pk = _rows([pks] if one else pks, sz["pk"], "pk", "slhdsa")
     if len(msg) != len(sig) or (not one and len(pk) != len(sig)):
         raise ValueError("slhdsa.verify_internal: as many keys and messages as signatures")
     ok = np.zeros(len(sig), np.uint8)
@@ -152,10 +140,10 @@ def sign_internal(name, sks, msgs, addrnds=None, device=0):
     if len(lens) > 1:
         raise ValueError("slhdsa.sign_internal: the messages of one call have one length")
     msg_len = lens.pop() if lens else 0
-    msg = _rows(msgs, msg_len, "message")
+    msg = _rows(msgs, msg_len, "message", "slhdsa")
     one = isinstance(sks, (bytes, bytearray))
-    sk = _rows([sks] if one else sks, sz["sk"], "sk")
-    rnd = None if addrnds is None else _rows(addrnds, n, "addrnd")
+    sk = _rows([sks] if one else sks, sz["sk"], "sk", "slhdsa")
+    rnd = None if addrnds is None else _rows(addrnds, n, "addrnd", "slhdsa")
     if (not one and len(sk) != len(msg)) or (rnd is not None and len(rnd) != len(msg)):
         raise ValueError("slhdsa.sign_internal: as many keys and addrnd strings as messages")
     sig = np.zeros((len(msg), sz["sig"]), np.uint8)
