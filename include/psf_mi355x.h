@@ -308,6 +308,18 @@ enum { PSF_SHA3_256 = 0, PSF_SHA3_512 = 1, PSF_SHAKE128 = 2, PSF_SHAKE256 = 3 };
 psf_status psf_keccak_dev(int device, int func, size_t count, const uint8_t* d_in, size_t in_len, size_t in_stride, uint8_t* d_out, size_t out_len,
                           size_t out_stride, void* stream);
 psf_status psf_keccak(int device, int func, size_t count, const uint8_t* in, size_t in_len, size_t in_stride, uint8_t* out, size_t out_len, size_t out_stride);
+/* FIPS 180-4 on the device, the twin of psf_keccak: `count` independent messages of in_len bytes, message c at d_in + c * in_stride, the leading
+ * out_len bytes of digest c at d_out + c * out_stride (FIPS 205's Trunc) -- SHA-256 and SHA-512, what the SHA-2 parameter sets of SLH-DSA hash with.
+ * One hash state per lane.  Any in_len (0 included; the padding opens a block of its own when it must); out_len is 1 ... 32 for SHA-256 and 1 ... 64
+ * for SHA-512.  Pointers and strides need no alignment (4-byte groups of a message move as one load when base and stride are multiples of 4).
+ * PSF_ERR_PARAM, in this order: unknown func; out_len = 0 or above the digest size; a stride smaller than its length; a NULL pointer with count > 0
+ * (d_in may be NULL when in_len = 0); a byte count that overflows size_t; an output range that overlaps the input range.  count = 0 is PSF_OK.
+ * Every check runs before the first HIP call; nothing is launched or written on an error.  A valid call without a device is PSF_ERR_HIP (no CPU
+ * fallback).  The device form is ordered on `stream`, allocates nothing and never synchronises; the host form allocates per call. */
+enum { PSF_SHA2_256 = 0, PSF_SHA2_512 = 1 };
+psf_status psf_sha2_dev(int device, int func, size_t count, const uint8_t* d_in, size_t in_len, size_t in_stride, uint8_t* d_out, size_t out_len,
+                        size_t out_stride, void* stream);
+psf_status psf_sha2(int device, int func, size_t count, const uint8_t* in, size_t in_len, size_t in_stride, uint8_t* out, size_t out_len, size_t out_stride);
 /* The byte-exact samplers of FIPS 203 (q = 3329, n = 256), one polynomial per lane, 256 coefficients per polynomial, polynomials contiguous.
  *   sample_ntt  SampleNTT (Algorithm 7): coefficients in [0, q) in the order the algorithm produces them -- FIPS 203's NTT-domain representation
  *               (psf_ntt_image_from_fips203_dev makes it an operand of the *_hat_dev products).  Words: uint16 or uint64 (operand a).
@@ -508,8 +520,8 @@ psf_status psf_sample_bounded_fips204(int device, size_t count, uint32_t eta, co
 psf_status psf_sample_in_ball_fips204(int device, size_t count, uint32_t tau, const uint8_t* ctilde, size_t ctilde_len, size_t ctilde_stride, int64_t* out);
 psf_status psf_ntt_image_from_fips204(int device, size_t count, const uint64_t* fhat, uint32_t* hat);
 /* SLH-DSA (FIPS 205, August 2024), batched, bytes in and bytes out: slh_keygen_internal(SK.seed, SK.prf, PK.seed) (Algorithm 18) and
- * slh_verify_internal(M, SIG, PK) (Algorithm 20) and slh_sign_internal(M, SK, addrnd) (Algorithm 19, below) for the six SHAKE parameter sets; the SHA-2
- * sets and HashSLH-DSA are not here.  The library draws NO randomness: the three seeds and addrnd are the caller's n-byte strings.  (n, h, d, h', a, k, m) = 128s (16, 63, 7, 9, 12, 14, 30), 128f (16, 66, 22, 3, 6, 33, 34),
+ * slh_verify_internal(M, SIG, PK) (Algorithm 20) and slh_sign_internal(M, SK, addrnd) (Algorithm 19, below) for the six SHAKE parameter sets.  KeyGen and Verify
+ * of the six SHA-2 sets are psf_slhdsa_sha2_* (below, a parameter numbering of their own); signing for the SHA-2 sets and HashSLH-DSA are not here.  The library draws NO randomness: the three seeds and addrnd are the caller's n-byte strings.  (n, h, d, h', a, k, m) = 128s (16, 63, 7, 9, 12, 14, 30), 128f (16, 66, 22, 3, 6, 33, 34),
  * 192s (24, 63, 7, 9, 14, 17, 39), 192f (24, 66, 22, 3, 8, 33, 42), 256s (32, 64, 8, 8, 14, 22, 47), 256f (32, 68, 17, 4, 9, 35, 49); lg_w = 4,
  * len = 2 n + 3.  The hash functions are those of section 11.1, all SHAKE256: H_msg = SHAKE256(R || PK.seed || PK.root || M, 8 m), PRF, F, H and
  * T_l = SHAKE256(PK.seed || ADRS || ..., 8 n) with the uncompressed 32-byte ADRS.
@@ -567,6 +579,35 @@ psf_status psf_slhdsa_sign_dev(int device, int param, size_t count, const uint8_
                                const uint8_t* d_addrnd, uint8_t* d_sig, void* d_ws, size_t ws_bytes, void* stream);
 psf_status psf_slhdsa_sign(int device, int param, size_t count, const uint8_t* sk, size_t sk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
                            const uint8_t* addrnd, uint8_t* sig);
+/* SLH-DSA for the six SHA-2 parameter sets of FIPS 205 (section 11.2): slh_keygen_internal (Algorithm 18) and slh_verify_internal (Algorithm 20),
+ * batched, bytes in and bytes out.  slh_sign_internal for these sets (it needs HMAC-SHA-256 / 512 for PRF_msg) and HashSLH-DSA are not here.  The sets
+ * have the SHAKE sets' (n, h, d, h', a, k, m) and sizes, and a `param` numbering of their own: PSF_SLHDSA_SHA2_* below, for these six entry points only.
+ * The hash functions, with the 22-byte compressed address ADRSc = layer 1 byte || tree 8 || type 1 || the last 12 bytes of ADRS:
+ *   n = 16      F, PRF, H, T_l = Trunc_n(SHA-256(PK.seed || toByte(0, 64 - n) || ADRSc || M));
+ *               H_msg = MGF1-SHA-256(R || PK.seed || SHA-256(R || PK.seed || PK.root || M), m)
+ *   n = 24, 32  F, PRF as above; H, T_l = Trunc_n(SHA-512(PK.seed || toByte(0, 128 - n) || ADRSc || M));
+ *               H_msg = MGF1-SHA-512(R || PK.seed || SHA-512(R || PK.seed || PK.root || M), m)
+ * The block PK.seed || zeros is compressed once per lane at kernel entry; F, PRF and H are one compression past that midstate.
+ * Argument lists, strides (pk_stride = 0: one key for all), PSF_SLHDSA_OP_*, the order of the PSF_ERR_PARAM checks, "nothing launched or written on
+ * an error", count = 0, PSF_ERR_UNSUPPORTED above 2^31 - 1 instances and PSF_ERR_HIP without a device are exactly those of psf_slhdsa_sizes,
+ * psf_slhdsa_workspace_bytes, psf_slhdsa_keygen(_dev) and psf_slhdsa_verify(_dev) above; so are the secrecy rules of keygen (WOTS+ secret values and
+ * chain intermediates in registers only, every chain its 15 steps, no secret-dependent branch or address).
+ * d_ws holds public values: keygen the chain ends (2^h' len n bytes per instance) | the leaves (2^h' n), each node as n / 4 big-endian 32-bit words,
+ * and the last thing the call queues on `stream` sets every byte of d_ws to zero; verify the first 64 bytes of the MGF1 mask of H_msg (n > 16: the
+ * inner SHA-512 digest passes through the same 64 bytes first) | the k FORS roots | the current node (32 bytes) | the len chain ends of the current
+ * layer, and is NOT cleared. */
+enum { PSF_SLHDSA_SHA2_128S = 0, PSF_SLHDSA_SHA2_128F = 1, PSF_SLHDSA_SHA2_192S = 2, PSF_SLHDSA_SHA2_192F = 3, PSF_SLHDSA_SHA2_256S = 4,
+       PSF_SLHDSA_SHA2_256F = 5 };
+psf_status psf_slhdsa_sha2_sizes(int param, size_t* pk, size_t* sk, size_t* sig);
+psf_status psf_slhdsa_sha2_workspace_bytes(int param, size_t count, int op, size_t* bytes);
+psf_status psf_slhdsa_sha2_keygen_dev(int device, int param, size_t count, const uint8_t* d_sk_seed, const uint8_t* d_sk_prf, const uint8_t* d_pk_seed,
+                                      uint8_t* d_pk, uint8_t* d_sk, void* d_ws, size_t ws_bytes, void* stream);
+psf_status psf_slhdsa_sha2_verify_dev(int device, int param, size_t count, const uint8_t* d_pk, size_t pk_stride, const uint8_t* d_msg, size_t msg_len,
+                                      size_t msg_stride, const uint8_t* d_sig, uint8_t* d_ok, void* d_ws, size_t ws_bytes, void* stream);
+psf_status psf_slhdsa_sha2_keygen(int device, int param, size_t count, const uint8_t* sk_seed, const uint8_t* sk_prf, const uint8_t* pk_seed, uint8_t* pk,
+                                  uint8_t* sk);
+psf_status psf_slhdsa_sha2_verify(int device, int param, size_t count, const uint8_t* pk, size_t pk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
+                                  const uint8_t* sig, uint8_t* ok);
 /* rot_minus_matrix (rotation_matrix.rs:85-96): mat[rows x cols] -> out[rows x rows*cols] */
 psf_status psf_rot_minus_matrix(const int64_t* mat, size_t rows, size_t cols, int64_t* out);
 

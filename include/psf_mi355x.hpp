@@ -78,6 +78,17 @@ inline std::vector<uint8_t> keccak(int device, int func, size_t count, const std
   check(psf_keccak(device, func, count, in.data(), in_len, in_len, out.data(), out_len, out_len), "keccak");
   return out;
 }
+// SHA-256 / SHA-512 (psf_sha2_dev, psf_sha2): func is PSF_SHA2_256 or PSF_SHA2_512, out_len the leading bytes of the digest
+inline void sha2_dev(int device, int func, size_t count, const uint8_t* d_in, size_t in_len, size_t in_stride, uint8_t* d_out, size_t out_len, size_t out_stride,
+                     void* stream = nullptr) {
+  check(psf_sha2_dev(device, func, count, d_in, in_len, in_stride, d_out, out_len, out_stride, stream), "sha2_dev");
+}
+inline std::vector<uint8_t> sha2(int device, int func, size_t count, const std::vector<uint8_t>& in, size_t in_len, size_t out_len) {
+  if (in.size() != count * in_len) throw PsfError(PSF_ERR_PARAM, "sha2");
+  std::vector<uint8_t> out(count * out_len);
+  check(psf_sha2(device, func, count, in.data(), in_len, in_len, out.data(), out_len, out_len), "sha2");
+  return out;
+}
 // SampleNTT: k = 0 raw form (34-byte inputs), 1 <= k <= 16 matrix form (32-byte rho, count k k polynomials)
 inline void sample_ntt_fips203_dev(int device, size_t count, uint32_t k, const uint8_t* d_seed, size_t seed_stride, void* d_out, int* d_fail = nullptr, int io_bits = 64,
                                    void* stream = nullptr) {
@@ -338,6 +349,47 @@ inline std::vector<uint8_t> slhdsa_sign(int device, int param, size_t count, con
   check(psf_slhdsa_sign(device, param, count, sk.data(), one ? 0 : s.sk, msg.data(), msg_len, msg_len, addrnd.empty() ? nullptr : addrnd.data(), sig.data()),
         "slhdsa_sign");
   return sig;
+}
+
+// ---- SLH-DSA for the SHA-2 parameter sets, batched (psf_slhdsa_sha2_*: KeyGen and Verify; rules in psf_mi355x.h).  `param` is PSF_SLHDSA_SHA2_128S ... _256F
+inline SlhDsaSizes slhdsa_sha2_sizes(int param) {
+  SlhDsaSizes s{};
+  check(psf_slhdsa_sha2_sizes(param, &s.pk, &s.sk, &s.sig), "slhdsa_sha2_sizes");
+  return s;
+}
+inline size_t slhdsa_sha2_workspace_bytes(int param, size_t count, int op) {
+  size_t bytes = 0;
+  check(psf_slhdsa_sha2_workspace_bytes(param, count, op, &bytes), "slhdsa_sha2_workspace_bytes");
+  return bytes;
+}
+inline void slhdsa_sha2_keygen_dev(int device, int param, size_t count, const uint8_t* d_sk_seed, const uint8_t* d_sk_prf, const uint8_t* d_pk_seed, uint8_t* d_pk, uint8_t* d_sk,
+                              void* d_ws, size_t ws_bytes, void* stream = nullptr) {
+  check(psf_slhdsa_sha2_keygen_dev(device, param, count, d_sk_seed, d_sk_prf, d_pk_seed, d_pk, d_sk, d_ws, ws_bytes, stream), "slhdsa_sha2_keygen_dev");
+}
+// pk_stride = 0: one key for all
+inline void slhdsa_sha2_verify_dev(int device, int param, size_t count, const uint8_t* d_pk, size_t pk_stride, const uint8_t* d_msg, size_t msg_len, size_t msg_stride,
+                              const uint8_t* d_sig, uint8_t* d_ok, void* d_ws, size_t ws_bytes, void* stream = nullptr) {
+  check(psf_slhdsa_sha2_verify_dev(device, param, count, d_pk, pk_stride, d_msg, msg_len, msg_stride, d_sig, d_ok, d_ws, ws_bytes, stream), "slhdsa_sha2_verify_dev");
+}
+// host buffers, packed: n = pk / 2 bytes of each seed per instance; returns (pk, sk)
+inline std::pair<std::vector<uint8_t>, std::vector<uint8_t>> slhdsa_sha2_keygen(int device, int param, size_t count, const std::vector<uint8_t>& sk_seed,
+                                                                           const std::vector<uint8_t>& sk_prf, const std::vector<uint8_t>& pk_seed) {
+  const SlhDsaSizes s = slhdsa_sha2_sizes(param);
+  const size_t n = s.pk / 2;
+  if (sk_seed.size() != count * n || sk_prf.size() != count * n || pk_seed.size() != count * n) throw PsfError(PSF_ERR_PARAM, "slhdsa_sha2_keygen");
+  std::vector<uint8_t> pk(count * s.pk), sk(count * s.sk);
+  check(psf_slhdsa_sha2_keygen(device, param, count, sk_seed.data(), sk_prf.data(), pk_seed.data(), pk.data(), sk.data()), "slhdsa_sha2_keygen");
+  return {pk, sk};
+}
+// pk: one key (for all) or count keys, packed; msg: count messages of msg_len bytes, packed; returns ok, one byte per instance
+inline std::vector<uint8_t> slhdsa_sha2_verify(int device, int param, size_t count, const std::vector<uint8_t>& pk, const std::vector<uint8_t>& msg, size_t msg_len,
+                                          const std::vector<uint8_t>& sig) {
+  const SlhDsaSizes s = slhdsa_sha2_sizes(param);
+  const bool one = pk.size() == s.pk && count != 1;
+  if ((!one && pk.size() != count * s.pk) || msg.size() != count * msg_len || sig.size() != count * s.sig) throw PsfError(PSF_ERR_PARAM, "slhdsa_sha2_verify");
+  std::vector<uint8_t> ok(count);
+  check(psf_slhdsa_sha2_verify(device, param, count, pk.data(), one ? 0 : s.pk, msg.data(), msg_len, msg_len, sig.data(), ok.data()), "slhdsa_sha2_verify");
+  return ok;
 }
 
 // ---- PSFPerturbation (mp_perturbation.rs:57-62, :193-403) -------------------------------------------------------------

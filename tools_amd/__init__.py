@@ -6,7 +6,8 @@ trap_gen / samp_d / samp_p / f_a / check_domain; compression (LossyCompressionFI
 rq (MatPolynomialRingZq matrix products, and the products of the cyclic ring X^n - 1), sample (uniform, centred-binomial and
 discrete-Gaussian fills), fips203 (SHA3 / SHAKE, the byte-exact samplers of FIPS 203 and its NTT-domain representation) and mlkem (batched
 ML-KEM KeyGen / Encaps / Decaps and the input checks, bytes in and bytes out), fips204 (the byte-exact samplers of FIPS 204 and its NTT-domain
-order) and mldsa (batched ML-DSA KeyGen, Sign and Verify), slhdsa (batched SLH-DSA KeyGen, Sign and Verify for the SHAKE parameter sets).
+order) and mldsa (batched ML-DSA KeyGen, Sign and Verify), slhdsa (batched SLH-DSA KeyGen, Sign and Verify for the SHAKE parameter sets),
+sha2 (batched SHA-256 / SHA-512) and slhdsa_sha2 (batched SLH-DSA KeyGen and Verify for the SHA-2 parameter sets).
 Everything computes on the GPU through the C ABI.
 """
 from ._ffi import PsfError, LIB_PATH  # noqa: F401
@@ -23,3 +24,5 @@ from . import mlkem  # noqa: F401
 from . import fips204  # noqa: F401
 from . import mldsa  # noqa: F401
 from . import slhdsa  # noqa: F401
+from . import sha2  # noqa: F401
+from . import slhdsa_sha2  # noqa: F401

@@ -1,0 +1,126 @@
+"""SLH-DSA (FIPS 205, August 2024) for the six SHA-2 parameter sets (section 11.2) on the device, batched, through the C ABI (psf_slhdsa_sha2_*,
+include/psf_mi355x.h): bytes in, bytes out.  The twin of tools_amd.slhdsa for KeyGen and Verify, with a parameter numbering of its own.
+
+  sizes / workspace_bytes   the byte sizes of a parameter set and of the workspace of an operation
+  keygen_dev / verify_dev   slh_keygen_internal and slh_verify_internal (Algorithms 18 and 20) over raw device pointers (e.g. torch `data_ptr()`),
+               ordered on `stream`, nothing allocated; the caller supplies the seeds and the workspace
+  keygen_internal / verify_internal   the host forms over lists of bytes (they run on the device too)
+  keygen / verify   slh_keygen (Algorithm 21: the three seeds from os.urandom) and slh_verify(M, SIG, ctx, PK) (Algorithm 24), with
+               M' = 0 || |ctx| || ctx || M.  They exist in Python only; the library itself draws no randomness and formats no message.
+
+A parameter set is named "SLH-DSA-SHA2-128s", "-128f", "-192s", "-192f", "-256s" or "-256f".  Signing for the SHA-2 sets (it needs HMAC for PRF_msg) and
+HashSLH-DSA are not here; the SHAKE sets are tools_amd.slhdsa."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from ._ffi import _rows, _vp, check, lib
+
+PARAM = {"SLH-DSA-SHA2-128s": 0, "SLH-DSA-SHA2-128f": 1, "SLH-DSA-SHA2-192s": 2, "SLH-DSA-SHA2-192f": 3, "SLH-DSA-SHA2-256s": 4, "SLH-DSA-SHA2-256f": 5}
+OP_KEYGEN, OP_VERIFY = range(2)
+OPS = {"keygen": OP_KEYGEN, "verify": OP_VERIFY}
+
+_typed = False
+
+
+def _lib():
+    global _typed
+    L = lib()
+    if not _typed:
+        vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
+        L.psf_slhdsa_sha2_sizes.argtypes = [i] + [C.POINTER(sz)] * 3
+        L.psf_slhdsa_sha2_workspace_bytes.argtypes = [i, sz, i, C.POINTER(sz)]
+        L.psf_slhdsa_sha2_keygen_dev.argtypes = [i, i, sz, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.psf_slhdsa_sha2_verify_dev.argtypes = [i, i, sz, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]
+        L.psf_slhdsa_sha2_keygen.argtypes = [i, i, sz, vp, vp, vp, vp, vp]
+        L.psf_slhdsa_sha2_verify.argtypes = [i, i, sz, vp, sz, vp, sz, sz, vp, vp]
+        _typed = True
+    return L
+
+
+def _param(name):
+    if name in PARAM:
+        return PARAM[name]
+    if not isinstance(name, str) and name in PARAM.values():
+        return name
+    raise ValueError(f"unknown SLH-DSA SHA-2 parameter set {name!r}")
+
+
+def sizes(name):
+    """{"pk": ..., "sk": ..., "sig": ...} in bytes; n is pk / 2"""
+    v = [C.c_size_t(0) for _ in range(3)]
+    check(_lib().psf_slhdsa_sha2_sizes(_param(name), *[C.byref(x) for x in v]), "slhdsa_sha2.sizes")
+    return dict(zip(("pk", "sk", "sig"), (int(x.value) for x in v)))
+
+
+def workspace_bytes(name, count, op):
+    """bytes of the 256-byte aligned device workspace that `op` ("keygen", "verify") needs for `count` instances"""
+    out = C.c_size_t(0)
+    check(_lib().psf_slhdsa_sha2_workspace_bytes(_param(name), count, OPS[op] if op in OPS else op, C.byref(out)), "slhdsa_sha2.workspace_bytes")
+    return int(out.value)
+
+
+def keygen_dev(name, count, d_sk_seed, d_sk_prf, d_pk_seed, d_pk, d_sk, d_ws, ws_bytes, device=0, stream=None):
+    """psf_slhdsa_sha2_keygen_dev: (pk_c, sk_c) = slh_keygen_internal(SK.seed_c, SK.prf_c, PK.seed_c); the workspace is all zero afterwards"""
+    check(_lib().psf_slhdsa_sha2_keygen_dev(device, _param(name), count, d_sk_seed or 0, d_sk_prf or 0, d_pk_seed or 0, d_pk or 0, d_sk or 0, d_ws or 0, ws_bytes, stream or 0),
+          "slhdsa_sha2.keygen_dev")
+
+
+def verify_dev(name, count, d_pk, d_msg, msg_len, d_sig, d_ok, d_ws, ws_bytes, pk_stride=None, msg_stride=None, device=0, stream=None):
+    """psf_slhdsa_sha2_verify_dev: ok[c] = slh_verify_internal(M_c, SIG_c, PK_c).  pk_stride defaults to the pk size (0: one key for all), msg_stride to
+    msg_len."""
+    if pk_stride is None:
+        pk_stride = sizes(name)["pk"]
+    check(_lib().psf_slhdsa_sha2_verify_dev(device, _param(name), count, d_pk or 0, pk_stride, d_msg or 0, msg_len, msg_len if msg_stride is None else msg_stride,
+                                       d_sig or 0, d_ok or 0, d_ws or 0, ws_bytes, stream or 0), "slhdsa_sha2.verify_dev")
+
+
+# ---- host forms ------------------------------------------------------------------------------------------------------------------------------------
+
+def keygen_internal(name, sk_seeds, sk_prfs, pk_seeds, device=0):
+    """[(pk, sk)] for the n-byte (SK.seed, SK.prf, PK.seed) of each instance"""
+    sz = sizes(name)
+    n = sz["pk"] // 2
+    a, b, c = _rows(sk_seeds, n, "SK.seed", "slhdsa_sha2"), _rows(sk_prfs, n, "SK.prf", "slhdsa_sha2"), _rows(pk_seeds, n, "PK.seed", "slhdsa_sha2")
+    if not len(a) == len(b) == len(c):
+        raise ValueError("slhdsa_sha2.keygen_internal: as many SK.prf and PK.seed strings as SK.seed strings")
+    pk, sk = np.empty((len(a), sz["pk"]), np.uint8), np.empty((len(a), sz["sk"]), np.uint8)
+    check(_lib().psf_slhdsa_sha2_keygen(device, _param(name), len(a), _vp(a), _vp(b), _vp(c), _vp(pk), _vp(sk)), "slhdsa_sha2.keygen_internal")
+    return [(bytes(x), bytes(y)) for x, y in zip(pk, sk)]
+
+
+def verify_internal(name, pks, msgs, sigs, device=0):
+    """[bool] for each (PK, M, SIG); `pks` is one key (bytes) for all or a list with one key per instance; the messages of one call have one length"""
+    sz = sizes(name)
+    sig = _rows(sigs, sz["sig"], "signature", "slhdsa_sha2")
+    msgs = [bytes(m) for m in msgs]
+    lens = {len(m) for m in msgs}
+    if len(lens) > 1:
+        raise ValueError("slhdsa_sha2.verify_internal: the messages of one call have one length")
+    msg_len = lens.pop() if lens else 0
+    msg = _rows(msgs, msg_len, "message", "slhdsa_sha2")
+    one = isinstance(pks, (bytes, bytearray))
+    pk = _rows([pks] if one else pks, sz["pk"], "pk", "slhdsa_sha2")
+    if len(msg) != len(sig) or (not one and len(pk) != len(sig)):
+        raise ValueError("slhdsa_sha2.verify_internal: as many keys and messages as signatures")
+    ok = np.zeros(len(sig), np.uint8)
+    check(_lib().psf_slhdsa_sha2_verify(device, _param(name), len(sig), _vp(pk), 0 if one else sz["pk"], _vp(msg), msg_len, msg_len, _vp(sig), _vp(ok)),
+          "slhdsa_sha2.verify_internal")
+    return [bool(a) for a in ok]
+
+
+# ---- Algorithms 21 and 24: the external forms, in Python only ------------------------------------------------------------------------------------------
+
+def keygen(name, count=1, device=0, random=os.urandom):
+    """slh_keygen for `count` fresh key pairs: SK.seed, SK.prf and PK.seed from `random` (os.urandom), then keygen_internal; [(pk, sk)]"""
+    n = sizes(name)["pk"] // 2
+    seeds = [[random(n) for _ in range(count)] for _ in range(3)]
+    return keygen_internal(name, *seeds, device=device)
+
+
+def verify(name, pk, M, sig, ctx=b"", device=0):
+    """slh_verify (Algorithm 24) of one signature: ValueError when ctx is longer than 255 bytes, else slh_verify_internal(0 || |ctx| || ctx || M, SIG, PK)"""
+    if len(ctx) > 255:
+        raise ValueError("slhdsa_sha2.verify: ctx longer than 255 bytes")
+    return verify_internal(name, bytes(pk), [bytes([0, len(ctx)]) + bytes(ctx) + bytes(M)], [sig], device=device)[0]
