@@ -521,7 +521,7 @@ psf_status psf_sample_in_ball_fips204(int device, size_t count, uint32_t tau, co
 psf_status psf_ntt_image_from_fips204(int device, size_t count, const uint64_t* fhat, uint32_t* hat);
 /* SLH-DSA (FIPS 205, August 2024), batched, bytes in and bytes out: slh_keygen_internal(SK.seed, SK.prf, PK.seed) (Algorithm 18) and
  * slh_verify_internal(M, SIG, PK) (Algorithm 20) and slh_sign_internal(M, SK, addrnd) (Algorithm 19, below) for the six SHAKE parameter sets.  KeyGen and Verify
- * of the six SHA-2 sets are psf_slhdsa_sha2_* (below, a parameter numbering of their own); signing for the SHA-2 sets and HashSLH-DSA are not here.  The library draws NO randomness: the three seeds and addrnd are the caller's n-byte strings.  (n, h, d, h', a, k, m) = 128s (16, 63, 7, 9, 12, 14, 30), 128f (16, 66, 22, 3, 6, 33, 34),
+ * and signing of the six SHA-2 sets are psf_slhdsa_sha2_* (below, a parameter numbering of their own); HashSLH-DSA is not here.  The library draws NO randomness: the three seeds and addrnd are the caller's n-byte strings.  (n, h, d, h', a, k, m) = 128s (16, 63, 7, 9, 12, 14, 30), 128f (16, 66, 22, 3, 6, 33, 34),
  * 192s (24, 63, 7, 9, 14, 17, 39), 192f (24, 66, 22, 3, 8, 33, 42), 256s (32, 64, 8, 8, 14, 22, 47), 256f (32, 68, 17, 4, 9, 35, 49); lg_w = 4,
  * len = 2 n + 3.  The hash functions are those of section 11.1, all SHAKE256: H_msg = SHAKE256(R || PK.seed || PK.root || M, 8 m), PRF, F, H and
  * T_l = SHAKE256(PK.seed || ADRS || ..., 8 n) with the uncompressed 32-byte ADRS.
@@ -579,14 +579,15 @@ psf_status psf_slhdsa_sign_dev(int device, int param, size_t count, const uint8_
                                const uint8_t* d_addrnd, uint8_t* d_sig, void* d_ws, size_t ws_bytes, void* stream);
 psf_status psf_slhdsa_sign(int device, int param, size_t count, const uint8_t* sk, size_t sk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
                            const uint8_t* addrnd, uint8_t* sig);
-/* SLH-DSA for the six SHA-2 parameter sets of FIPS 205 (section 11.2): slh_keygen_internal (Algorithm 18) and slh_verify_internal (Algorithm 20),
- * batched, bytes in and bytes out.  slh_sign_internal for these sets (it needs HMAC-SHA-256 / 512 for PRF_msg) and HashSLH-DSA are not here.  The sets
- * have the SHAKE sets' (n, h, d, h', a, k, m) and sizes, and a `param` numbering of their own: PSF_SLHDSA_SHA2_* below, for these six entry points only.
+/* SLH-DSA for the six SHA-2 parameter sets of FIPS 205 (section 11.2): slh_keygen_internal (Algorithm 18), slh_verify_internal (Algorithm 20) and
+ * slh_sign_internal (Algorithm 19, below), batched, bytes in and bytes out.  HashSLH-DSA is not here.  The sets
+ * have the SHAKE sets' (n, h, d, h', a, k, m) and sizes, and a `param` numbering of their own: PSF_SLHDSA_SHA2_* below, for these nine entry points only.
  * The hash functions, with the 22-byte compressed address ADRSc = layer 1 byte || tree 8 || type 1 || the last 12 bytes of ADRS:
  *   n = 16      F, PRF, H, T_l = Trunc_n(SHA-256(PK.seed || toByte(0, 64 - n) || ADRSc || M));
  *               H_msg = MGF1-SHA-256(R || PK.seed || SHA-256(R || PK.seed || PK.root || M), m)
  *   n = 24, 32  F, PRF as above; H, T_l = Trunc_n(SHA-512(PK.seed || toByte(0, 128 - n) || ADRSc || M));
  *               H_msg = MGF1-SHA-512(R || PK.seed || SHA-512(R || PK.seed || PK.root || M), m)
+ *   PRF_msg     Trunc_n(HMAC-SHA-256(SK.prf, opt_rand || M)) at n = 16, Trunc_n(HMAC-SHA-512(SK.prf, opt_rand || M)) at n = 24, 32 (RFC 2104)
  * The block PK.seed || zeros is compressed once per lane at kernel entry; F, PRF and H are one compression past that midstate.
  * Argument lists, strides (pk_stride = 0: one key for all), PSF_SLHDSA_OP_*, the order of the PSF_ERR_PARAM checks, "nothing launched or written on
  * an error", count = 0, PSF_ERR_UNSUPPORTED above 2^31 - 1 instances and PSF_ERR_HIP without a device are exactly those of psf_slhdsa_sizes,
@@ -595,7 +596,19 @@ psf_status psf_slhdsa_sign(int device, int param, size_t count, const uint8_t* s
  * d_ws holds public values: keygen the chain ends (2^h' len n bytes per instance) | the leaves (2^h' n), each node as n / 4 big-endian 32-bit words,
  * and the last thing the call queues on `stream` sets every byte of d_ws to zero; verify the first 64 bytes of the MGF1 mask of H_msg (n > 16: the
  * inner SHA-512 digest passes through the same 64 bytes first) | the k FORS roots | the current node (32 bytes) | the len chain ends of the current
- * layer, and is NOT cleared. */
+ * layer, and is NOT cleared.
+ *   sign     psf_slhdsa_sha2_sign_workspace_bytes, psf_slhdsa_sha2_sign_dev and psf_slhdsa_sha2_sign have the argument lists and the semantics of
+ *            psf_slhdsa_sign_workspace_bytes, psf_slhdsa_sign_dev and psf_slhdsa_sign above, with `param` a PSF_SLHDSA_SHA2_*: Algorithm 19 byte for
+ *            byte; sk_stride = 0 means one key for all; d_addrnd NULL is the deterministic variant (opt_rand = PK.seed read from the key at the key's
+ *            pitch), else n bytes per instance, contiguous; d_msg may be NULL when msg_len = 0; the order of the PSF_ERR_PARAM checks (msg_len must
+ *            leave 3 n + msg_len a bit count that fits 64 bits); nothing launched or written on an error; count = 0 is PSF_OK after the param check;
+ *            PSF_ERR_UNSUPPORTED above 2^31 - 1 instances; PSF_ERR_HIP without a device; the host form zeroes its device copies of sk and addrnd on
+ *            every path out.  The workspace has the SHAKE twin's sections, order and sizes -- psf_slhdsa_sha2_sign_workspace_bytes(param, count)
+ *            equals psf_slhdsa_sign_workspace_bytes of the set with the same (n, s / f) for every count -- each node as n / 4 big-endian 32-bit
+ *            words; at n > 16 the public inner digest of H_msg passes through the instance's 64 digest bytes, as in verify; the last thing the call
+ *            queues on `stream` sets every byte of d_ws to zero.  The two key blocks of HMAC and its inner digest are secret and exist in registers
+ *            only; otherwise the secrecy rules are the twin's: the only stores of secret-derived values are R, the one revealed FORS secret value per
+ *            tree and the WOTS+ value at its digit, and no branch, loop bound or address depends on a secret. */
 enum { PSF_SLHDSA_SHA2_128S = 0, PSF_SLHDSA_SHA2_128F = 1, PSF_SLHDSA_SHA2_192S = 2, PSF_SLHDSA_SHA2_192F = 3, PSF_SLHDSA_SHA2_256S = 4,
        PSF_SLHDSA_SHA2_256F = 5 };
 psf_status psf_slhdsa_sha2_sizes(int param, size_t* pk, size_t* sk, size_t* sig);
@@ -608,6 +621,11 @@ psf_status psf_slhdsa_sha2_keygen(int device, int param, size_t count, const uin
                                   uint8_t* sk);
 psf_status psf_slhdsa_sha2_verify(int device, int param, size_t count, const uint8_t* pk, size_t pk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
                                   const uint8_t* sig, uint8_t* ok);
+psf_status psf_slhdsa_sha2_sign_workspace_bytes(int param, size_t count, size_t* bytes);
+psf_status psf_slhdsa_sha2_sign_dev(int device, int param, size_t count, const uint8_t* d_sk, size_t sk_stride, const uint8_t* d_msg, size_t msg_len,
+                                    size_t msg_stride, const uint8_t* d_addrnd, uint8_t* d_sig, void* d_ws, size_t ws_bytes, void* stream);
+psf_status psf_slhdsa_sha2_sign(int device, int param, size_t count, const uint8_t* sk, size_t sk_stride, const uint8_t* msg, size_t msg_len, size_t msg_stride,
+                                const uint8_t* addrnd, uint8_t* sig);
 /* rot_minus_matrix (rotation_matrix.rs:85-96): mat[rows x cols] -> out[rows x rows*cols] */
 psf_status psf_rot_minus_matrix(const int64_t* mat, size_t rows, size_t cols, int64_t* out);
 

@@ -351,7 +351,7 @@ inline std::vector<uint8_t> slhdsa_sign(int device, int param, size_t count, con
   return sig;
 }
 
-// ---- SLH-DSA for the SHA-2 parameter sets, batched (psf_slhdsa_sha2_*: KeyGen and Verify; rules in psf_mi355x.h).  `param` is PSF_SLHDSA_SHA2_128S ... _256F
+// ---- SLH-DSA for the SHA-2 parameter sets, batched (psf_slhdsa_sha2_*: KeyGen, Verify and signing; rules in psf_mi355x.h).  `param` is PSF_SLHDSA_SHA2_128S ... _256F
 inline SlhDsaSizes slhdsa_sha2_sizes(int param) {
   SlhDsaSizes s{};
   check(psf_slhdsa_sha2_sizes(param, &s.pk, &s.sk, &s.sig), "slhdsa_sha2_sizes");
@@ -390,6 +390,29 @@ inline std::vector<uint8_t> slhdsa_sha2_verify(int device, int param, size_t cou
   std::vector<uint8_t> ok(count);
   check(psf_slhdsa_sha2_verify(device, param, count, pk.data(), one ? 0 : s.pk, msg.data(), msg_len, msg_len, sig.data(), ok.data()), "slhdsa_sha2_verify");
   return ok;
+}
+// signing (Algorithm 19); sk_stride = 0: one key for all; d_addrnd NULL: the deterministic variant
+inline size_t slhdsa_sha2_sign_workspace_bytes(int param, size_t count) {
+  size_t bytes = 0;
+  check(psf_slhdsa_sha2_sign_workspace_bytes(param, count, &bytes), "slhdsa_sha2_sign_workspace_bytes");
+  return bytes;
+}
+inline void slhdsa_sha2_sign_dev(int device, int param, size_t count, const uint8_t* d_sk, size_t sk_stride, const uint8_t* d_msg, size_t msg_len, size_t msg_stride,
+                                 const uint8_t* d_addrnd, uint8_t* d_sig, void* d_ws, size_t ws_bytes, void* stream = nullptr) {
+  check(psf_slhdsa_sha2_sign_dev(device, param, count, d_sk, sk_stride, d_msg, msg_len, msg_stride, d_addrnd, d_sig, d_ws, ws_bytes, stream), "slhdsa_sha2_sign_dev");
+}
+// sk: one key (for all) or count keys, packed; msg: count messages of msg_len bytes, packed; addrnd: empty (deterministic) or count * n bytes; returns
+// the signatures, packed
+inline std::vector<uint8_t> slhdsa_sha2_sign(int device, int param, size_t count, const std::vector<uint8_t>& sk, const std::vector<uint8_t>& msg, size_t msg_len,
+                                             const std::vector<uint8_t>& addrnd = {}) {
+  const SlhDsaSizes s = slhdsa_sha2_sizes(param);
+  const bool one = sk.size() == s.sk && count != 1;
+  if ((!one && sk.size() != count * s.sk) || msg.size() != count * msg_len || (!addrnd.empty() && addrnd.size() != count * (s.pk / 2)))
+    throw PsfError(PSF_ERR_PARAM, "slhdsa_sha2_sign");
+  std::vector<uint8_t> sig(count * s.sig);
+  check(psf_slhdsa_sha2_sign(device, param, count, sk.data(), one ? 0 : s.sk, msg.data(), msg_len, msg_len, addrnd.empty() ? nullptr : addrnd.data(), sig.data()),
+        "slhdsa_sha2_sign");
+  return sig;
 }
 
 // ---- PSFPerturbation (mp_perturbation.rs:57-62, :193-403) -------------------------------------------------------------

@@ -1,5 +1,5 @@
 // psf_call.hpp -- what the bytes-in, bytes-out units (psf_keccak.hip, psf_mlkem.hip, psf_mldsa.hip, psf_mldsa_sign.hip, psf_slhdsa.hip,
-// psf_slhdsa_sign.hip, psf_sha2.hip, psf_slhdsa_sha2.hip) share around their kernels, and nothing of any one scheme: the argument checks and the workspace layout (psf_call_host.hpp, no HIP
+// psf_slhdsa_sign.hip, psf_sha2.hip, psf_slhdsa_sha2.hip, psf_slhdsa_sha2_sign.hip) share around their kernels, and nothing of any one scheme: the argument checks and the workspace layout (psf_call_host.hpp, no HIP
 // in it), the grid-limit helpers, and HostCall, the device copies of a call on host buffers.
 #pragma once
 #include <hip/hip_runtime.h>

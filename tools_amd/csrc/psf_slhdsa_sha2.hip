@@ -18,6 +18,7 @@
 #include "psf_call.hpp"
 #include "psf_hip_util.hpp"
 #include "psf_host.hpp"
+#include "psf_slhdsa_sha2_api.hpp"
 #include "psf_slhdsa_sha2_core.hpp"
 
 namespace psf {

@@ -10,8 +10,8 @@ parameter sets.
                unless deterministic) and slh_verify(M, SIG, ctx, PK) (Algorithm 24), with M' = 0 || |ctx| || ctx || M.  They exist in Python only; the
                library itself draws no randomness and formats no message.
 
-A parameter set is named "SLH-DSA-SHAKE-128s", "-128f", "-192s", "-192f", "-256s" or "-256f".  KeyGen and Verify of the SHA-2 sets are
-tools_amd.slhdsa_sha2; signing for the SHA-2 sets and HashSLH-DSA are not here."""
+A parameter set is named "SLH-DSA-SHAKE-128s", "-128f", "-192s", "-192f", "-256s" or "-256f".  The SHA-2 sets are tools_amd.slhdsa_sha2;
+HashSLH-DSA is not here."""
 import ctypes as C
 import os
 

@@ -1,15 +1,16 @@
 """SLH-DSA (FIPS 205, August 2024) for the six SHA-2 parameter sets (section 11.2) on the device, batched, through the C ABI (psf_slhdsa_sha2_*,
-include/psf_mi355x.h): bytes in, bytes out.  The twin of tools_amd.slhdsa for KeyGen and Verify, with a parameter numbering of its own.
+include/psf_mi355x.h): bytes in, bytes out.  The twin of tools_amd.slhdsa, with a parameter numbering of its own.
 
-  sizes / workspace_bytes   the byte sizes of a parameter set and of the workspace of an operation
-  keygen_dev / verify_dev   slh_keygen_internal and slh_verify_internal (Algorithms 18 and 20) over raw device pointers (e.g. torch `data_ptr()`),
-               ordered on `stream`, nothing allocated; the caller supplies the seeds and the workspace
-  keygen_internal / verify_internal   the host forms over lists of bytes (they run on the device too)
-  keygen / verify   slh_keygen (Algorithm 21: the three seeds from os.urandom) and slh_verify(M, SIG, ctx, PK) (Algorithm 24), with
-               M' = 0 || |ctx| || ctx || M.  They exist in Python only; the library itself draws no randomness and formats no message.
+  sizes / workspace_bytes / sign_workspace_bytes   the byte sizes of a parameter set and of the workspace of an operation
+  keygen_dev / verify_dev / sign_dev   slh_keygen_internal, slh_verify_internal and slh_sign_internal (Algorithms 18, 20 and 19) over raw device
+               pointers (e.g. torch `data_ptr()`), ordered on `stream`, nothing allocated; the caller supplies the seeds, addrnd and the workspace
+  keygen_internal / verify_internal / sign_internal   the host forms over lists of bytes (they run on the device too)
+  keygen / sign / verify   slh_keygen (Algorithm 21: the three seeds from os.urandom), slh_sign(M, ctx, SK) (Algorithm 22: addrnd from os.urandom, or
+               the deterministic variant) and slh_verify(M, SIG, ctx, PK) (Algorithm 24), with M' = 0 || |ctx| || ctx || M.  They exist in Python only;
+               the library itself draws no randomness and formats no message.
 
-A parameter set is named "SLH-DSA-SHA2-128s", "-128f", "-192s", "-192f", "-256s" or "-256f".  Signing for the SHA-2 sets (it needs HMAC for PRF_msg) and
-HashSLH-DSA are not here; the SHAKE sets are tools_amd.slhdsa."""
+A parameter set is named "SLH-DSA-SHA2-128s", "-128f", "-192s", "-192f", "-256s" or "-256f".  HashSLH-DSA is not here; the SHAKE sets are
+tools_amd.slhdsa."""
 import ctypes as C
 import os
 
@@ -35,6 +36,9 @@ def _lib():
         L.psf_slhdsa_sha2_verify_dev.argtypes = [i, i, sz, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]
         L.psf_slhdsa_sha2_keygen.argtypes = [i, i, sz, vp, vp, vp, vp, vp]
         L.psf_slhdsa_sha2_verify.argtypes = [i, i, sz, vp, sz, vp, sz, sz, vp, vp]
+        L.psf_slhdsa_sha2_sign_workspace_bytes.argtypes = [i, sz, C.POINTER(sz)]
+        L.psf_slhdsa_sha2_sign_dev.argtypes = [i, i, sz, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]
+        L.psf_slhdsa_sha2_sign.argtypes = [i, i, sz, vp, sz, vp, sz, sz, vp, vp]
         _typed = True
     return L
 
@@ -76,6 +80,22 @@ def verify_dev(name, count, d_pk, d_msg, msg_len, d_sig, d_ok, d_ws, ws_bytes, p
                                        d_sig or 0, d_ok or 0, d_ws or 0, ws_bytes, stream or 0), "slhdsa_sha2.verify_dev")
 
 
+def sign_workspace_bytes(name, count):
+    """bytes of the 256-byte aligned device workspace that signing needs for `count` instances (the same for every sk_stride)"""
+    out = C.c_size_t(0)
+    check(_lib().psf_slhdsa_sha2_sign_workspace_bytes(_param(name), count, C.byref(out)), "slhdsa_sha2.sign_workspace_bytes")
+    return int(out.value)
+
+
+def sign_dev(name, count, d_sk, d_msg, msg_len, d_addrnd, d_sig, d_ws, ws_bytes, sk_stride=None, msg_stride=None, device=0, stream=None):
+    """psf_slhdsa_sha2_sign_dev: SIG_c = slh_sign_internal(M_c, SK_c, addrnd_c); d_addrnd None: the deterministic variant.  sk_stride defaults to the sk
+    size (0: one key for all), msg_stride to msg_len.  The workspace is all zero afterwards."""
+    if sk_stride is None:
+        sk_stride = sizes(name)["sk"]
+    check(_lib().psf_slhdsa_sha2_sign_dev(device, _param(name), count, d_sk or 0, sk_stride, d_msg or 0, msg_len, msg_len if msg_stride is None else msg_stride,
+                                          d_addrnd or 0, d_sig or 0, d_ws or 0, ws_bytes, stream or 0), "slhdsa_sha2.sign_dev")
+
+
 # ---- host forms ------------------------------------------------------------------------------------------------------------------------------------
 
 def keygen_internal(name, sk_seeds, sk_prfs, pk_seeds, device=0):
@@ -110,13 +130,44 @@ def verify_internal(name, pks, msgs, sigs, device=0):
     return [bool(a) for a in ok]
 
 
-# ---- Algorithms 21 and 24: the external forms, in Python only ------------------------------------------------------------------------------------------
+def sign_internal(name, sks, msgs, addrnds=None, device=0):
+    """[SIG] for each (SK, M, addrnd); `sks` is one key (bytes) for all or a list with one key per instance; the messages of one call have one length;
+    addrnds None: the deterministic variant, else one n-byte string per instance"""
+    sz = sizes(name)
+    n = sz["pk"] // 2
+    msgs = [bytes(m) for m in msgs]
+    lens = {len(m) for m in msgs}
+    if len(lens) > 1:
+        raise ValueError("slhdsa_sha2.sign_internal: the messages of one call have one length")
+    msg_len = lens.pop() if lens else 0
+    msg = _rows(msgs, msg_len, "message", "slhdsa_sha2")
+    one = isinstance(sks, (bytes, bytearray))
+    sk = _rows([sks] if one else sks, sz["sk"], "sk", "slhdsa_sha2")
+    rnd = None if addrnds is None else _rows(addrnds, n, "addrnd", "slhdsa_sha2")
+    if (not one and len(sk) != len(msg)) or (rnd is not None and len(rnd) != len(msg)):
+        raise ValueError("slhdsa_sha2.sign_internal: as many keys and addrnd strings as messages")
+    sig = np.zeros((len(msg), sz["sig"]), np.uint8)
+    check(_lib().psf_slhdsa_sha2_sign(device, _param(name), len(msg), _vp(sk), 0 if one else sz["sk"], _vp(msg), msg_len, msg_len, None if rnd is None else _vp(rnd),
+                                      _vp(sig)), "slhdsa_sha2.sign_internal")
+    return [bytes(x) for x in sig]
+
+
+# ---- Algorithms 21, 22 and 24: the external forms, in Python only ------------------------------------------------------------------------------------------
 
 def keygen(name, count=1, device=0, random=os.urandom):
     """slh_keygen for `count` fresh key pairs: SK.seed, SK.prf and PK.seed from `random` (os.urandom), then keygen_internal; [(pk, sk)]"""
     n = sizes(name)["pk"] // 2
     seeds = [[random(n) for _ in range(count)] for _ in range(3)]
     return keygen_internal(name, *seeds, device=device)
+
+
+def sign(name, sk, M, ctx=b"", deterministic=False, device=0, random=os.urandom):
+    """slh_sign (Algorithm 22) of one message: ValueError when ctx is longer than 255 bytes, else slh_sign_internal(0 || |ctx| || ctx || M, SK, addrnd)
+    with addrnd n bytes from `random` (os.urandom), or none when `deterministic`"""
+    if len(ctx) > 255:
+        raise ValueError("slhdsa_sha2.sign: ctx longer than 255 bytes")
+    addrnd = None if deterministic else [random(sizes(name)["pk"] // 2)]
+    return sign_internal(name, bytes(sk), [bytes([0, len(ctx)]) + bytes(ctx) + bytes(M)], addrnd, device=device)[0]
 
 
 def verify(name, pk, M, sig, ctx=b"", device=0):
