@@ -155,3 +155,36 @@ def gauss_narrow_trace(seed, tag, first_index, count, n, center, s, stats=None):
     if stats is not None:
         stats["groups"] = groups
     return out.reshape(count, n), ties, voids
+
+
+# ---- windows: coefficients [i0, i1) of one polynomial without the rest (fills of up to 2^32 - 1 coefficients) -----------------------------------
+
+def uniform_window(seed, tag, idx, i0, i1, q):
+    """uint64 (i1 - i0,): uniform_fill's coefficients [i0, i1) of polynomial idx"""
+    from oracle import oracle as O
+    f = O.lib().orc_uniform_mod
+    tw, lo = tag_word(tag, idx), idx & M32
+    return np.array([f(seed, tw, i, lo, q) for i in range(i0, i1)], dtype=np.uint64)
+
+
+def cbd_window(seed, tag, idx, i0, i1, eta):
+    """int64 (i1 - i0,): cbd_fill's coefficients [i0, i1) of polynomial idx -- only the Philox blocks that meet the window are drawn"""
+    sw = 16 // eta
+    i = np.arange(i0, i1, dtype=np.uint64)
+    words = philox_np(seed, i // np.uint64(4 * sw), np.uint64(idx & M32), np.uint64(0), np.uint64(tag_word(tag, idx)))
+    sel = ((i // np.uint64(sw)) % np.uint64(4)).astype(np.int64)
+    w = np.choose(sel, list(words))
+    f = (w >> (np.uint64(2 * eta) * (i % np.uint64(sw)))) & np.uint64((1 << (2 * eta)) - 1)
+    return _popcount(f & np.uint64((1 << eta) - 1)) - _popcount(f >> np.uint64(eta))
+
+
+def gauss_window(seed, tag, idx, i0, i1, s, center=0.0, centers=None):
+    """(int64 (i1 - i0,), failed): gauss_fill's coefficients [i0, i1) of polynomial idx; `centers`: the i1 - i0 centres of the window"""
+    from oracle import oracle as O
+    L = O.lib()
+    f = L.orc_sample_z
+    L.orc_sample_z_cap_hits.restype = __import__("ctypes").c_ulong
+    cap0 = L.orc_sample_z_cap_hits()
+    cen = None if centers is None else np.asarray(centers, dtype=np.float64).reshape(i1 - i0)
+    out = np.array([f(seed, tag, idx, i, center if cen is None else float(cen[i - i0]), s) for i in range(i0, i1)], dtype=np.int64)
+    return out, L.orc_sample_z_cap_hits() != cap0
